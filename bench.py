@@ -7,7 +7,9 @@ sequence-parallel Sum all-reduce of the replicated parameter gradients and an Ad
 Synthetic random inputs, random-init weights, bf16 compute, the reference's all-False
 boolean mask (``example.py:29``) is passed and honoured.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3        # the headline figure and nothing else
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full # + numerics check, fp32 steps, N > 1 breakdown
+    python bench.py --steps 10 --warmup 3 --dump-outputs out/   # what the last timed step computed, as .npy
     python bench.py --gpus 8 --steps 20 --warmup 5        # starts the 8-rank torchrun job itself
     python bench.py --sweep 1,2,4,8                        # one line per N + a scaling summary
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
@@ -15,6 +17,12 @@ boolean mask (``example.py:29``) is passed and honoured.
 
 Rank 0 prints one JSON line.  ``value`` = wall ms per step, max over ranks (the job's step
 time); the timed region is bracketed by a barrier and ``torch.cuda.synchronize()``.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line.  Everything else
+the benchmark measures or checks runs only with ``--full``: the T=512 numerics check against
+the dense fp32 module before timing (``--no-check`` skips it), the same step timed in fp32
+under both fp32 kernel families (``--fp32-steps 0`` skips it) and, for N > 1, the breakdown
+into collectives and a compute-only step (``--no-diagnostics`` skips it).
 """
 from __future__ import annotations
 
@@ -43,7 +51,7 @@ def parse(argv=None):
     ap.add_argument("--sweep", default=None,
                     help="comma-separated N list (e.g. 1,2,4,8): run each N in fresh processes, print one "
                          "JSON line per N and a speed-up / efficiency summary line")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
     ap.add_argument("--warmup", type=int, default=10,
                     help="untimed steps first (10: about 1 %% faster timed steps than 3 on the same box, scripts/archive/warm_ab.sh)")
     ap.add_argument("--seq-len", type=int, default=25000, help="global T")
@@ -66,14 +74,21 @@ def parse(argv=None):
     ap.add_argument("--profile-dir", default=None, help="write a torch.profiler trace here")
     ap.add_argument("--no-split-step", dest="split_step", action="store_false",
                     help="(A/B) one optimizer step after every all-reduce instead of splitting it around the last one")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline timing: the pre-timing numerics check, the fp32 timing of the "
+                         "same step and (N > 1) the collectives / compute-only breakdown")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, output rows, parameter "
+                         "gradients, updated parameters) as DIR/<name>.npy in float32; inputs and weights are "
+                         "seeded, so two builds can be compared output for output")
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the T=512 numerics check of the N-rank module against the dense fp32 module")
+                    help="--full: skip the T=512 numerics check of the N-rank module against the dense fp32 module")
     ap.add_argument("--fp32-steps", type=int, default=5,
-                    help="also time this many steps of the same step in fp32 (the reference's precision; "
+                    help="--full: also time this many steps of the same step in fp32 (the reference's precision; "
                          "0 = skip); reported as fp32_ms_per_step")
     ap.add_argument("--fp32-warmup", type=int, default=2)
     ap.add_argument("--no-diagnostics", dest="diagnostics", action="store_false",
-                    help="N > 1: skip the post-timing breakdown (collectives alone, compute-only step)")
+                    help="--full, N > 1: skip the post-timing breakdown (collectives alone, compute-only step)")
     ap.add_argument("--trace", action="store_true",
                     help="print stage / step progress with timestamps to stderr (diagnostics)")
     ap.add_argument("--graph", action="store_true",
@@ -136,7 +151,36 @@ def numerics_check(a, comm, dev, dt, impl, T: int = 512, tol: float = 3e-2) -> f
     return worst
 
 
-def time_step(a, comm, dev, dt, steps, warmup, graph=False, profile_dir=None):
+DUMP_MAX_ROWS = 8192  # output rows kept by --dump-outputs (8192 x 768 fp32 = 25 MB; the whole dump < 64 MB)
+
+
+def dump_outputs(dump_dir, comm, model, loss, out) -> None:
+    """``--dump-outputs``: what a caller of the timed step holds after its last step, as float32
+    ``.npy`` files: the loss, this rank's output rows of the first batch element (a fixed seeded sample of
+    :data:`DUMP_MAX_ROWS` rows, sorted, when there are more; their indices in ``out_rows``), the
+    reduced parameter gradients and the updated parameters.  Ranks > 0 add ``.rank<r>`` to the names."""
+    import numpy as np
+
+    os.makedirs(dump_dir, exist_ok=True)
+    tag = f".rank{comm.rank}" if comm.rank else ""
+
+    def save(name, t):
+        np.save(os.path.join(dump_dir, f"{name}{tag}.npy"), t.detach().to(torch.float32).cpu().numpy())
+
+    save("loss", loss.reshape(1))
+    rows = torch.arange(out.shape[1])
+    if out.shape[1] > DUMP_MAX_ROWS:
+        g = torch.Generator().manual_seed(2024)
+        rows = torch.randperm(out.shape[1], generator=g)[:DUMP_MAX_ROWS].sort().values
+    save("out_rows", rows)
+    save("out", out[:1].index_select(1, rows.to(out.device)))
+    for name, p in model.named_parameters():
+        save("param." + name, p)
+        if p.grad is not None:
+            save("grad." + name, p.grad)
+
+
+def time_step(a, comm, dev, dt, steps, warmup, graph=False, profile_dir=None, dump_dir=None):
     """Build the model/optimizer for ``dt`` and time ``steps`` training steps after
     ``warmup`` untimed ones.  Returns (ms_per_step max over ranks, host enqueue ms, loss, impl)."""
     import xdot
@@ -174,9 +218,13 @@ def time_step(a, comm, dev, dt, steps, warmup, graph=False, profile_dir=None):
         c = torch.arange(T, device=dev)
         mask = ((c[None, :] // 1024) > (r[:, None] // 1024)).unsqueeze(0).expand(a.batch, R, T).contiguous()
 
+    last = {}  # --dump-outputs: the module output of the latest step
+
     def step():
         opt.zero_grad(set_to_none=True)
         out = model(x, x, x, mask)
+        if dump_dir:
+            last["out"] = out
         loss = crit(out, y)
         # == loss.backward(), minus the seed fill / scaling pass, on this thread (XDOT_INLINE_BACKWARD)
         backward(loss, unit_grad(loss))
@@ -192,6 +240,8 @@ def time_step(a, comm, dev, dt, steps, warmup, graph=False, profile_dir=None):
 
         def body():
             out = model(x, x, x, mask)
+            if dump_dir:
+                last["out"] = out
             loss = crit(out, y)
             loss.backward()
             sync.wait()
@@ -240,7 +290,9 @@ def time_step(a, comm, dev, dt, steps, warmup, graph=False, profile_dir=None):
     lossv = float(loss.float().item())
     if not math.isfinite(lossv):
         raise SystemExit(f"non-finite loss {lossv}")
-    del model, opt, sync, x, y, mask
+    if dump_dir and steps > 0:
+        dump_outputs(dump_dir, comm, model, loss, last["out"])
+    del model, opt, sync, x, y, mask, last
     return ms, (th - t0) * 1e3 / max(1, steps), lossv, impl
 
 
@@ -450,18 +502,18 @@ def main(argv=None, comm=None):
 
     check_err = None
     _trace(a, "init done")
-    if not emulated and not a.no_check:
+    if a.full and not emulated and not a.no_check:
         check_err = numerics_check(a, comm, dev, dt, a.impl)
     _trace(a, "numerics check done")
     ms, host_ms, lossv, impl = time_step(a, comm, dev, dt, a.steps, a.warmup, graph=a.graph,
-                                         profile_dir=a.profile_dir)
+                                         profile_dir=a.profile_dir, dump_dir=a.dump_outputs)
     diag = {}
-    if n > 1 and not emulated and a.diagnostics:
+    if a.full and n > 1 and not emulated and a.diagnostics:
         _trace(a, "multi-rank diagnostics start")
         diag = multirank_diagnostics(a, comm, dev, dt, ms, impl)
         _trace(a, "multi-rank diagnostics done")
     fp32 = {}
-    if a.fp32_steps > 0 and dt != torch.float32 and dev.type == "cuda":
+    if a.full and a.fp32_steps > 0 and dt != torch.float32 and dev.type == "cuda":
         # the reference computes in fp32 only (module.py:60-71): time the same step in fp32 too,
         # under both fp32 kernel families (XDOT_FP32_MODE: exact fp32 MFMA default, split-bf16)
         default_mode = FLAGS.fp32_mode

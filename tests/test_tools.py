@@ -47,7 +47,7 @@ def _torchrun(n):
 
 def test_bench_contract_cpu():
     out = _run(["bench.py", "--device", "cpu", "--dtype", "fp32", "--seq-len", "128", "--dim", "64",
-                "--heads", "4", "--steps", "2", "--warmup", "1"])
+                "--heads", "4", "--steps", "2", "--warmup", "1", "--full"])
     recs = _json_lines(out)
     assert len(recs) == 1, out
     r = recs[0]
@@ -62,6 +62,36 @@ def test_bench_contract_cpu():
     assert r["world_size"] == 1 and r["transport"] == "local" and r["rccl_version"] is None
     assert r["gather_chunks"] == 1 and r["local_first"] in (True, False)
     assert 0 <= r["numerics_check_max_rel_err"] < 1e-3  # fp32 on the CPU: the same math
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without ``--full`` nothing but the headline is measured; ``--dump-outputs`` writes what the
+    last timed step computed as float32 ``.npy`` files, identical from run to run (seeded inputs)."""
+    import numpy as np
+
+    args = ["bench.py", "--device", "cpu", "--dtype", "fp32", "--seq-len", "128", "--dim", "64", "--heads", "4",
+            "--steps", "2", "--warmup", "1"]
+    dumps = []
+    for d in ("a", "b"):
+        recs = _json_lines(_run(args + ["--dump-outputs", str(tmp_path / d)]))
+        assert len(recs) == 1
+        r = recs[0]
+        assert r["steps"] == 2 and r["value"] == r["ms_per_step"] > 0 and r["dtype"] == "fp32"
+        assert r["numerics_check_max_rel_err"] is None and "fp32_ms_per_step" not in r
+        files = sorted((tmp_path / d).iterdir())
+        assert all(f.suffix == ".npy" for f in files), files
+        dumps.append({f.stem: np.load(f) for f in files})
+    a, b = dumps
+    names = {"loss", "out", "out_rows"}
+    for w in ("keys", "queries", "values", "composition"):
+        names |= {f"param.{w}.weight", f"grad.{w}.weight"}
+    assert names <= set(a) and set(a) == set(b)
+    assert a["out"].shape == (1, 128, 64) and a["loss"].shape == (1,) and a["loss"][0] == pytest.approx(r["loss"])
+    assert list(a["out_rows"]) == list(range(128))
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), k
+        assert np.array_equal(v, b[k]), k
+    assert sum(v.nbytes for v in a.values()) < 64 << 20
 
 
 def test_bench_rejects_wrong_world_size():
@@ -100,7 +130,7 @@ def test_bench_two_ranks_gloo(impl):
     """The driver's N>1 launch line, on the CPU over gloo: ONE JSON line, from rank 0."""
     out = _run(_torchrun(2) + ["bench.py", "--gpus", "2", "--device", "cpu", "--backend", "gloo", "--dtype", "fp32",
                                "--seq-len", "128", "--dim", "64", "--heads", "4", "--steps", "2", "--warmup", "1",
-                               "--impl", impl])
+                               "--impl", impl, "--full"])
     recs = _json_lines(out)
     assert len(recs) == 1, out
     assert recs[0]["n_gpus"] == 2 and recs[0]["config"]["parallelism"] == "sp2"
