@@ -14,6 +14,10 @@
 //         wave-uniform scalar load (s_load_dword), which does not wait on the vector-memory
 //         counter that tracks their prefetched K/V tiles.
 // An all-False mask (the reference example/benchmark) therefore costs the kernels nothing.
+//
+// mask_gen_kernel writes the same three tensors from a description of the mask (causal /
+// sliding window / key lengths: xdot.StructuredMask) without any (B, R, T) input; both kernels
+// share everything that follows a lane's two 64-bit words (mask_words_out).
 #include "common.h"
 
 namespace xdot {
@@ -33,6 +37,52 @@ __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
 
 // 4 bool bytes (each 0 or 1: torch's bool storage) -> 4 bits, byte k -> bit k
 __device__ __forceinline__ uint32_t pack4(uint32_t x) { return (x * 0x10204080u) >> 28; }
+
+// The part both producers share, entered once lane i holds row i's two 64-bit words of the
+// block (rows past R: zero): the kt-major bits store, the 32-row flag ballots and the 6-step
+// butterfly transpose into bits_t.
+__device__ __forceinline__ void mask_words_out(const uint64_t (&wv)[2], uint64_t* __restrict__ bits,
+                                               uint64_t* __restrict__ bt, uint8_t* __restrict__ flags, int lane, int b,
+                                               int rt, int kt0, int R, int T, int NKT, int NKT4, int NRT, int Tpad) {
+  const int r = rt * 64 + lane;
+  const bool row_ok = r < R;
+  if (row_ok && kt0 < NKT) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+      if (kt0 + h < NKT) bits[((int64_t)b * NKT + kt0 + h) * R + r] = wv[h];  // kt-major: coalesced
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int kt = kt0 + h;
+    uint64_t w = wv[h];
+    // flags of the two 32-row halves (rows past R count as neither)
+    if (kt < NKT4) {
+      const int n = kt < NKT ? min(64, T - kt * 64) : 0;
+      const uint64_t full = n == 64 ? ~0ull : ((1ull << n) - 1);
+      const uint64_t any = __ballot(w != 0);
+      const uint64_t all = __ballot(!row_ok || w == full);
+      if ((lane & 31) == 0) {
+        const int half = lane >> 5, rb = rt * 2 + half;
+        if (rb < (R + 31) / 32) {
+          const uint32_t a = (uint32_t)(any >> (32 * half)), l = (uint32_t)(all >> (32 * half));
+          flags[((int64_t)b * ((R + 31) / 32) + rb) * NKT4 + kt] = kt >= NKT ? 1 : (a == 0 ? 0 : (l == 0xffffffffu ? 1 : 2));
+        }
+      }
+    }
+    // 64 x 64 bit transpose: lane c ends up with column c (bit i = row i)
+    if (kt * 64 < Tpad) {
+      const uint64_t M[6] = {0x00000000ffffffffull, 0x0000ffff0000ffffull, 0x00ff00ff00ff00ffull,
+                             0x0f0f0f0f0f0f0f0full, 0x3333333333333333ull, 0x5555555555555555ull};
+#pragma unroll
+      for (int s = 0; s < 6; ++s) {
+        const int j = 32 >> s;
+        const uint64_t o = shfl_xor64(w, j);
+        w = (lane & j) ? (((o >> j) & M[s]) | (w & ~M[s])) : ((w & M[s]) | ((o & M[s]) << j));
+      }
+      bt[((int64_t)b * NRT + rt) * Tpad + (int64_t)kt * 64 + lane] = w;
+    }
+  }
+}
 
 __global__ __launch_bounds__(256) void mask_pack_kernel(const uint8_t* __restrict__ m, uint64_t* __restrict__ bits,
                                                          uint64_t* __restrict__ bt, uint8_t* __restrict__ flags,
@@ -93,42 +143,64 @@ __global__ __launch_bounds__(256) void mask_pack_kernel(const uint8_t* __restric
     const int n = min(128, T - c0);
     for (int k = 0; k < n; ++k) wv[k >> 6] |= (uint64_t)(p[k] != 0) << (k & 63);
   }
-  if (row_ok && kt0 < NKT) {
+  mask_words_out(wv, bits, bt, flags, lane, b, rt, kt0, R, T, NKT, NKT4, NRT, Tpad);
+}
+
+// The same three outputs from a DESCRIPTION of the mask (xdot.StructuredMask) instead of a
+// (B, R, T) tensor: nothing R x T sized is read.  Row r of the block is global row
+// gr = row_off + r; its unmasked global columns are one interval [lo, hi]:
+//   causal      hi = gr                      window w    lo = gr - (w - 1), and without causal
+//   lengths     hi = min(hi, lengths[b] - 1)             hi = gr + (w - 1)
+// The packed columns are a concatenation of `nseg` runs (packed_start, length, global_start)
+// of consecutive global columns (global_start < 0: a run that is masked whatever the row), so
+// within a run the interval is again an interval of packed columns: every word starts as "all
+// of its columns below T masked" and each overlapping run clears one shifted range of ones.
+__global__ __launch_bounds__(256) void mask_gen_kernel(uint64_t* __restrict__ bits, uint64_t* __restrict__ bt,
+                                                        uint8_t* __restrict__ flags, const int* __restrict__ lengths,
+                                                        const int* __restrict__ segs, int nseg, int causal,
+                                                        int64_t window, int64_t row_off, int B, int R, int T, int NKT,
+                                                        int NKT4, int NRT, int Tpad, int KT_ALL) {
+  const int lane = threadIdx.x & 63;
+  const int KT2 = (KT_ALL + 1) / 2;
+  const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (blk >= (int64_t)B * NRT * KT2) return;  // whole waves exit together
+  const int kt0 = (int)(blk % KT2) * 2;
+  const int64_t brt = blk / KT2;
+  const int rt = (int)(brt % NRT), b = (int)(brt / NRT);
+  const int r = rt * 64 + lane;
+  uint64_t wv[2] = {0, 0};
+  const int64_t c0 = (int64_t)kt0 * 64;
+  if (r < R && c0 < T) {
+    const int64_t gr = row_off + r;
+    int64_t lo = 0, hi = (int64_t)1 << 60;  // no bound (the run arithmetic below stays in range)
+    if (causal) hi = gr;
+    if (window > 0) {
+      lo = gr - (window - 1);
+      if (!causal) hi = gr + (window - 1);
+    }
+    if (lengths != nullptr) hi = min(hi, (int64_t)lengths[b] - 1);
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
-      if (kt0 + h < NKT) bits[((int64_t)b * NKT + kt0 + h) * R + r] = wv[h];  // kt-major: coalesced
-  }
+    for (int h = 0; h < 2; ++h) {
+      const int64_t n = min((int64_t)64, T - (c0 + 64 * h));
+      wv[h] = n >= 64 ? ~0ull : (n > 0 ? (1ull << n) - 1 : 0ull);
+    }
+    for (int s = 0; s < nseg; ++s) {  // wave-uniform
+      const int64_t ps = segs[3 * s], len = segs[3 * s + 1], gs = segs[3 * s + 2];
+      if (gs < 0 || ps + len <= c0 || ps >= c0 + 128) continue;
+      // unmasked packed columns of this run: global [lo, hi] moved by (ps - gs), cut to the run
+      const int64_t a = max(ps, lo - gs + ps), e = min(ps + len - 1, hi - gs + ps);
 #pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int kt = kt0 + h;
-    uint64_t w = wv[h];
-    // flags of the two 32-row halves (rows past R count as neither)
-    if (kt < NKT4) {
-      const int n = kt < NKT ? min(64, T - kt * 64) : 0;
-      const uint64_t full = n == 64 ? ~0ull : ((1ull << n) - 1);
-      const uint64_t any = __ballot(w != 0);
-      const uint64_t all = __ballot(!row_ok || w == full);
-      if ((lane & 31) == 0) {
-        const int half = lane >> 5, rb = rt * 2 + half;
-        if (rb < (R + 31) / 32) {
-          const uint32_t a = (uint32_t)(any >> (32 * half)), l = (uint32_t)(all >> (32 * half));
-          flags[((int64_t)b * ((R + 31) / 32) + rb) * NKT4 + kt] = kt >= NKT ? 1 : (a == 0 ? 0 : (l == 0xffffffffu ? 1 : 2));
+      for (int h = 0; h < 2; ++h) {
+        const int64_t p0 = c0 + 64 * h;
+        const int64_t a_ = max(a, p0), e_ = min(e, p0 + 63);
+        if (a_ <= e_) {
+          const int cnt = (int)(e_ - a_ + 1);  // 1..64
+          wv[h] &= ~((cnt == 64 ? ~0ull : (1ull << cnt) - 1) << (int)(a_ - p0));
         }
       }
     }
-    // 64 x 64 bit transpose: lane c ends up with column c (bit i = row i)
-    if (kt * 64 < Tpad) {
-      const uint64_t M[6] = {0x00000000ffffffffull, 0x0000ffff0000ffffull, 0x00ff00ff00ff00ffull,
-                             0x0f0f0f0f0f0f0f0full, 0x3333333333333333ull, 0x5555555555555555ull};
-#pragma unroll
-      for (int s = 0; s < 6; ++s) {
-        const int j = 32 >> s;
-        const uint64_t o = shfl_xor64(w, j);
-        w = (lane & j) ? (((o >> j) & M[s]) | (w & ~M[s])) : ((w & M[s]) | ((o & M[s]) << j));
-      }
-      bt[((int64_t)b * NRT + rt) * Tpad + (int64_t)kt * 64 + lane] = w;
-    }
   }
+  mask_words_out(wv, bits, bt, flags, lane, b, rt, kt0, R, T, NKT, NKT4, NRT, Tpad);
 }
 
 }  // namespace xdot
@@ -146,5 +218,20 @@ extern "C" int xdot_mask_pack_launch(const uint8_t* mask, uint64_t* bits, uint64
   if (nblk == 0) return 0;
   hipLaunchKernelGGL(mask_pack_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, st, mask, bits, bt, flags, B, R, T,
                      NKT, NKT4, NRT, Tpad, KT_ALL, va);
+  return 0;
+}
+
+// lengths: (B,) int32 or null; segs: (nseg, 3) int32 (packed_start, length, global_start) covering
+// [0, T); window <= 0: none
+extern "C" int xdot_mask_gen_launch(uint64_t* bits, uint64_t* bt, uint8_t* flags, const int* lengths, const int* segs,
+                                    int nseg, int causal, int64_t window, int64_t row_off, int B, int R, int T,
+                                    hipStream_t st) {
+  using namespace xdot;
+  const int NKT = (T + 63) / 64, NKT4 = (NKT + 3) & ~3, NRT = (R + 63) / 64, Tpad = (T + 127) / 128 * 128;
+  const int KT_ALL = max(NKT4, Tpad / 64);
+  const int64_t nblk = (int64_t)B * NRT * ((KT_ALL + 1) / 2);
+  if (nblk == 0) return 0;
+  hipLaunchKernelGGL(mask_gen_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, st, bits, bt, flags, lengths, segs,
+                     nseg, causal, window, row_off, B, R, T, NKT, NKT4, NRT, Tpad, KT_ALL);
   return 0;
 }

@@ -39,7 +39,10 @@ def main():
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
+    # relaxed, as GraphedStep captures: ProcessGroupNCCL's watchdog thread may still be polling the
+    # warm-up collectives' events when the capture starts, and in the default (global) mode an
+    # event query on any thread during a capture is an error that aborts the process
+    with torch.cuda.graph(g, capture_error_mode="relaxed"):
         body()
     for it in range(3):
         x.copy_(torch.arange(1024, device=dev, dtype=torch.float32) + 1000 * r + it)

@@ -24,6 +24,11 @@ Three execution paths, chosen by ``impl``:
 Extensions over the reference (all backward compatible): ``attn_mask=None`` means no mask,
 ``value_dim`` may differ from ``key_dim`` with several heads (the reference raises), any
 float dtype works, and ``distributed=False`` gives the single-device ground truth.
+``attn_mask`` may also be a :class:`xdot.StructuredMask` (causal / sliding window / key lengths):
+the flash and ring kernels' packed mask is then generated on the GPU from the description
+(``row_offset=None`` resolves to ``rank * R``) and no ``(B, R, T)`` tensor exists; the paths that
+only take a dense mask -- ``'materialized'``, CPU tensors, ``backend='torch'`` -- build
+``StructuredMask.dense(...)`` once per call and so do allocate it.
 
 Keyword-only knobs (each mirrors an environment flag, the argument wins):
 
@@ -49,6 +54,7 @@ from torch import Tensor
 
 from .. import _ext
 from ..ops.linear import linear
+from ..ops.mask import StructuredMask
 from ..ops.softmax import scale_mask_softmax
 from ..parallel.autograd import FullMultiplication, RightTransposeMultiplication
 from ..utils import comm as _comm
@@ -190,7 +196,7 @@ class DistributedDotProductAttn(nn.Module):
                 k = pa.pad_heads(self._proj(self.keys, keys), H, dk, Dp)
                 o = seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm)
                 return self._proj(self.composition, pa.unpad_heads(o, H, dv, Dp))
-            if attn_mask is not None and attn_mask.is_cuda and attn_mask.dim() == 3 and FLAGS.mask_async:
+            if isinstance(attn_mask, Tensor) and attn_mask.is_cuda and attn_mask.dim() == 3 and FLAGS.mask_async:
                 # pack the mask on a side stream while the projection GEMMs run
                 from ..ops import flash
 
@@ -264,6 +270,10 @@ class DistributedDotProductAttn(nn.Module):
             s = RightTransposeMultiplication.apply(k, q, self.offset, comm)
         else:
             s = torch.matmul(k, q.transpose(-1, -2))
+        if isinstance(attn_mask, StructuredMask):
+            # the softmax kernel takes a dense mask: the (B, R, T) tensor is built here, once
+            rank = comm.rank if self.distributed else 0
+            attn_mask = attn_mask.dense(B, R, s.shape[-1], rank * R, s.device)
         p = scale_mask_softmax(s, attn_mask, scale)
         if self.distributed:
             o = FullMultiplication.apply(p, v, self.offset, comm)

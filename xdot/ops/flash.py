@@ -15,6 +15,7 @@ import torch
 
 from .. import _ext
 from ..utils.env import FLAGS
+from .mask import StructuredMask, segments_of
 
 
 class PackedMask:
@@ -42,12 +43,49 @@ def prepare_mask(mask: Optional[torch.Tensor], B: int, R: int, T: int) -> Option
     return PackedMask(bits, flags, bits_t, mask.shape)
 
 
+def generate_mask(spec: StructuredMask, B: int, R: int, T: int, row_offset: Optional[int] = None, segments=None,
+                  device=None) -> PackedMask:
+    """The packed form of ``spec`` for ``R`` local rows starting at global row ``row_offset`` and
+    ``T`` packed columns, generated on the GPU (``mask_gen`` in ``csrc/mask_pack.hip``): bitwise
+    what :func:`prepare_mask` gives for ``spec.dense(...)``, with nothing R x T sized allocated.
+
+    ``segments``: the packed columns as runs ``(packed_start, length, global_start)`` of
+    consecutive global columns (``global_start = -1``: a run that is always masked); None: the
+    identity, packed column = global column.  ``row_offset`` is used where ``spec`` has none;
+    ``device``: default the device of ``spec.lengths`` when on a GPU, else the current one."""
+    spec.check(B)
+    ro = spec.row_offset if spec.row_offset is not None else row_offset
+    if ro is None:
+        raise ValueError("generate_mask: row_offset is not set")
+    if device is None:
+        ln = spec.lengths
+        device = ln.device if ln is not None and ln.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    segs = [(0, T, 0)] if segments is None else [tuple(int(x) for x in sg) for sg in segments]
+    if sorted((p, p + n) for p, n, _g in segs if n > 0) != _tiling(segs, T):
+        raise ValueError(f"generate_mask: the segments must tile the {T} packed columns exactly, got {segs}")
+    table = torch.tensor(segs or [(0, 0, 0)], dtype=torch.int32).reshape(-1, 3).to(device, non_blocking=True)
+    bits, flags, bits_t = _ext.ops().mask_gen(int(B), int(R), int(T), spec.causal, int(spec.window or 0), int(ro),
+                                              spec.device_lengths(device), table)
+    return PackedMask(bits, flags, bits_t, (B, R, T))
+
+
+def _tiling(segs, T: int):
+    """[(start, end)] of the non-empty segments if they cover [0, T) back to back, else None."""
+    out, at = [], 0
+    for p, e in sorted((p, p + n) for p, n, _g in segs if n > 0):
+        if p != at:
+            return None
+        out.append((p, e))
+        at = e
+    return out if at == T else None
+
+
 class _MaskEntry:
     __slots__ = ("ref", "version", "packed", "none_ev", "none_host")
 
 
 class MaskCache:
-    """Packed masks keyed on the boolean tensor that produced them.
+    """Packed masks keyed on the boolean tensor (or :class:`StructuredMask`) that produced them.
 
     A training loop passes the same mask object every step (the reference's ``example.py``
     builds it once); re-packing it costs a full read of the (B, R, T) bool tensor per step
@@ -109,9 +147,18 @@ MASK_CACHE = MaskCache()
 
 def prepare_mask_cached(mask: Optional[torch.Tensor], B: int, R: int, T: int, tag=None,
                         view=None) -> Optional[PackedMask]:
-    """:func:`prepare_mask` through :data:`MASK_CACHE` (``view(mask)``: the slice to pack)."""
+    """:func:`prepare_mask` through :data:`MASK_CACHE` (``view(mask)``: the slice to pack).
+
+    ``mask`` may be a bound :class:`StructuredMask` (``StructuredMask.bind``: row offset resolved,
+    global column count known): the packed mask is then generated, ``view`` giving the column
+    segment table (:func:`xdot.ops.mask.segments_of`) instead of a sliced tensor."""
     if mask is None:
         return None
+    if isinstance(mask, StructuredMask):
+        if mask._T is None:
+            raise ValueError("prepare_mask_cached: bind() the StructuredMask first (row offset, global columns)")
+        # (one description serves any batch / row count, unlike a tensor: the shape is part of the key)
+        return MASK_CACHE.get(mask, (tag, B, R, T), lambda: generate_mask(mask, B, R, T, segments=segments_of(view, mask._T)))
     return MASK_CACHE.get(mask, tag, lambda: prepare_mask(mask if view is None else view(mask), B, R, T))
 
 

@@ -1,0 +1,166 @@
+"""Attention masks given as a description (causal / sliding window / key lengths) instead of a
+dense ``(B, R, T)`` boolean tensor.
+
+The flash kernels consume a packed mask (:class:`xdot.ops.flash.PackedMask`);
+``csrc/mask_pack.hip`` generates it straight from a :class:`StructuredMask`
+(:func:`xdot.ops.flash.generate_mask`), so nothing ``R x T`` sized is ever built.  Paths that
+only take a dense mask (the torch reference paths, CPU tensors, ``impl="materialized"``) get
+:meth:`StructuredMask.dense` once at their entry: those DO allocate the ``(B, R, T)`` tensor.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple, Union
+
+import torch
+
+Segment = Tuple[int, int, int]  # (packed_start, length, global_start); global_start -1: always masked
+
+
+class StructuredMask:
+    """``StructuredMask(causal=False, window=None, lengths=None, row_offset=None)``
+
+    True = masked, as everywhere in this package.  With ``gr = row_offset + r`` the global index
+    of local row ``r`` and ``gc`` the global column in ``[0, T)``, an element is masked iff
+
+    * ``causal`` and ``gc > gr``, or
+    * ``window = w`` (int >= 1) and ``gc < gr - (w - 1)`` -- without ``causal`` also
+      ``gc > gr + (w - 1)`` --, or
+    * ``lengths`` is given and ``gc >= lengths[b]``.
+
+    ``lengths``: a ``(B,)`` integer tensor (kept by reference: a device tensor is read by the
+    kernel with no host synchronisation, and an in-place edit re-generates the cached packed
+    mask) or a sequence of ints.  ``row_offset=None``: this rank's first row, ``rank * R``,
+    resolved by the attention entry points from the communicator.
+
+    The object is immutable and is not a tensor; pass it where a mask tensor goes
+    (``attn_mask`` of :class:`xdot.DistributedDotProductAttn`, ``mask`` of
+    :func:`xdot.seq_parallel_attention` / the ring ops)."""
+
+    __slots__ = ("causal", "window", "lengths", "row_offset", "_T", "_bound", "__weakref__")
+
+    def __init__(self, causal: bool = False, window: Optional[int] = None,
+                 lengths: Union[None, torch.Tensor, Sequence[int]] = None, row_offset: Optional[int] = None):
+        if window is not None:
+            if isinstance(window, bool) or not isinstance(window, int):
+                raise TypeError(f"StructuredMask: window must be an int or None, got {type(window).__name__}")
+            if window < 1:
+                raise ValueError(f"StructuredMask: window must be >= 1, got {window}")
+        if lengths is not None:
+            if not isinstance(lengths, torch.Tensor):
+                lengths = torch.tensor([int(x) for x in lengths], dtype=torch.int64)
+            if lengths.dim() != 1 or lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+                raise ValueError("StructuredMask: lengths must be a (B,) integer tensor or a sequence of ints")
+        if row_offset is not None:
+            row_offset = int(row_offset)
+            if row_offset < 0:
+                raise ValueError(f"StructuredMask: row_offset must be >= 0, got {row_offset}")
+        s = object.__setattr__
+        s(self, "causal", bool(causal))
+        s(self, "window", window)
+        s(self, "lengths", lengths)
+        s(self, "row_offset", row_offset)
+        s(self, "_T", None)      # global column count, set on the copies bind() hands out
+        s(self, "_bound", {})
+
+    def __setattr__(self, name, value):
+        raise AttributeError("StructuredMask is immutable")
+
+    def __repr__(self):
+        ln = None if self.lengths is None else f"<{self.lengths.numel()} lengths on {self.lengths.device}>"
+        return (f"StructuredMask(causal={self.causal}, window={self.window}, lengths={ln}, "
+                f"row_offset={self.row_offset})")
+
+    @property
+    def _version(self) -> int:
+        """What :class:`xdot.ops.flash.MaskCache` compares besides the object's identity."""
+        return 0 if self.lengths is None else self.lengths._version
+
+    def check(self, B: int) -> None:
+        if self.lengths is not None and self.lengths.numel() != B:
+            raise ValueError(f"StructuredMask: lengths has {self.lengths.numel()} entries, the batch is {B}")
+
+    def bind(self, row_offset: int, T: int) -> "StructuredMask":
+        """The description with its row offset resolved (``row_offset`` is used only where the
+        object has none) and the global column count ``T`` noted: the object the cached packed
+        masks are keyed on.  The same arguments give the same object back."""
+        ro = int(row_offset) if self.row_offset is None else self.row_offset
+        key = (ro, int(T))
+        b = self._bound.get(key)
+        if b is None:
+            if len(self._bound) >= 8:
+                self._bound.pop(next(iter(self._bound)))
+            b = StructuredMask(self.causal, self.window, self.lengths, ro)
+            object.__setattr__(b, "_T", int(T))
+            self._bound[key] = b
+        return b
+
+    def device_lengths(self, device) -> Optional[torch.Tensor]:
+        """``lengths`` as the kernel reads them: contiguous int32 on ``device`` (no host sync for a
+        device tensor)."""
+        if self.lengths is None:
+            return None
+        ln = self.lengths.to(device=device, non_blocking=True)
+        return ln.clamp(min=0, max=2**31 - 1).to(torch.int32).contiguous()
+
+    def dense(self, B: int, R: int, T: int, row_offset: Optional[int] = None, device=None) -> torch.Tensor:
+        """The equivalent ``(B, R, T)`` boolean tensor, built with plain torch ops (it allocates
+        ``B * R * T`` bytes).  ``row_offset`` is used where the object has none."""
+        self.check(B)
+        ro = self.row_offset if self.row_offset is not None else row_offset
+        if ro is None:
+            raise ValueError("StructuredMask.dense: row_offset is not set")
+        gr = (int(ro) + torch.arange(R, device=device, dtype=torch.int64)).view(R, 1)
+        gc = torch.arange(T, device=device, dtype=torch.int64).view(1, T)
+        m = torch.zeros(R, T, dtype=torch.bool, device=device)
+        if self.causal:
+            m |= gc > gr
+        if self.window is not None:
+            m |= gc < gr - (self.window - 1)
+            if not self.causal:
+                m |= gc > gr + (self.window - 1)
+        m = m.unsqueeze(0).expand(B, R, T)
+        if self.lengths is not None:
+            m = m | (gc.view(1, 1, T) >= self.lengths.to(device=device, dtype=torch.int64).view(B, 1, 1))
+        return m.contiguous()
+
+
+def resolve(mask, B: int, R: int, T: int, rank: int, packed: bool, device):
+    """What an attention entry point does with its mask argument: a :class:`StructuredMask` is
+    checked against the batch and bound to ``row_offset = rank * R`` (``packed``: a path that
+    generates the packed mask from it), or turned into its dense tensor once (every other
+    path); anything else passes through."""
+    if not isinstance(mask, StructuredMask):
+        return mask
+    mask.check(B)
+    if packed:
+        return mask.bind(rank * R, T)
+    return mask.dense(B, R, T, rank * R, device)
+
+
+def run_lengths(idx: torch.Tensor) -> List[Segment]:
+    """Run-length encoding of a row of global column indices (-1: always masked) into the
+    generator's segment table: maximal runs of consecutive indices, or of -1."""
+    v = idx.reshape(-1).to("cpu", torch.int64)
+    n = v.numel()
+    if n == 0:
+        return []
+    cont = ((v[1:] - v[:-1] == 1) & (v[:-1] >= 0)) | ((v[1:] < 0) & (v[:-1] < 0))
+    starts = torch.cat([torch.zeros(1, dtype=torch.int64), torch.nonzero(~cont).reshape(-1) + 1])
+    ends = torch.cat([starts[1:], torch.tensor([n], dtype=torch.int64)])
+    g = v[starts]
+    return [(int(s), int(e - s), int(x) if x >= 0 else -1) for s, e, x in zip(starts.tolist(), ends.tolist(), g.tolist())]
+
+
+def segments_of(view, T: int) -> List[Segment]:
+    """The segment table of ``view`` (a function of a ``(B, R, T)`` mask giving the columns a
+    kernel launch sees, or None for all of them in order): the same function applied to a
+    ``(1, 1, T)`` row of column indices, run-length encoded."""
+    idx = torch.arange(T, dtype=torch.int32).view(1, 1, T)
+    return run_lengths(idx if view is None else view(idx))
+
+
+def expand_segments(segs: Sequence[Segment]) -> torch.Tensor:
+    """Inverse of :func:`run_lengths`: the int64 index row of a segment table."""
+    parts = [torch.full((ln,), -1, dtype=torch.int64) if g < 0 else torch.arange(g, g + ln, dtype=torch.int64)
+             for _p, ln, g in segs]
+    return torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64)

@@ -18,6 +18,7 @@ from typing import Optional
 import torch
 
 from .. import _ext
+from .mask import StructuredMask
 
 
 def _mask_map(scores: torch.Tensor, mask: torch.Tensor):
@@ -86,4 +87,7 @@ def scale_mask_softmax(scores: torch.Tensor, mask: Optional[torch.Tensor] = None
     """Differentiable fused softmax.  ``scale`` defaults to ``1/sqrt(head_dim)`` if given."""
     if scale is None:
         scale = 1.0 / math.sqrt(head_dim) if head_dim else 1.0
+    if isinstance(mask, StructuredMask):  # this path only takes a dense mask: (B, R, T) bools allocated
+        mask = mask.dense(scores.shape[0] if scores.dim() > 2 else 1, scores.shape[-2], scores.shape[-1],
+                          None, scores.device)
     return ScaleMaskSoftmax.apply(scores, mask, float(scale))

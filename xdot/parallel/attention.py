@@ -32,6 +32,7 @@ import torch
 from torch import Tensor
 
 from .. import _ext
+from ..ops.mask import StructuredMask, resolve as resolve_mask
 from ..utils import comm as _comm
 from ..utils.checks import check_consistent
 from ..utils.env import FLAGS
@@ -178,9 +179,9 @@ class _PendingGather:
 
 def _perm_cols(B: int, R: int, n: int, chunks: List[Tuple[int, int]]):
     """Mask columns in the (chunk, source rank, row) order of :meth:`_PendingGather.permuted`."""
-    def view(m):
-        m4 = m.reshape(B, R, n, R)
-        return torch.cat([m4[..., r0:r0 + rc].reshape(B, R, n * rc) for r0, rc in chunks], dim=-1)
+    def view(m):  # leading dims from m: also applied to a (1, 1, T) row of column indices
+        m4 = m.reshape(*m.shape[:-1], n, R)
+        return torch.cat([m4[..., r0:r0 + rc].reshape(*m.shape[:-1], n * rc) for r0, rc in chunks], dim=-1)
     return view
 
 
@@ -291,7 +292,7 @@ def _segment_plan(n: int, rank: int, nchunks: int, local_first: bool) -> List[Tu
 
 def _mask_cols(B: int, R: int, n: int, j0: int, j1: int, r0: int, rc: int):
     """Mask columns of source ranks j0..j1-1, rows r0..r0+rc of each (global column j*R + r0 + i)."""
-    return lambda m: m.reshape(B, R, n, R)[..., j0:j1, r0:r0 + rc].reshape(B, R, (j1 - j0) * rc)
+    return lambda m: m.reshape(*m.shape[:-1], n, R)[..., j0:j1, r0:r0 + rc].reshape(*m.shape[:-1], (j1 - j0) * rc)
 
 
 def _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescaled, fp32_mode=0):
@@ -363,6 +364,7 @@ def _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescal
 
 
 _OWN_EX = {}
+_NOTHING_MASKED = StructuredMask()
 # False: a middle rank launches one partial per peer range (A/B diagnostics: bench_rank.py --no-seg-merge)
 SEGMENT_MERGE = True
 
@@ -373,9 +375,9 @@ def _own_excluded_mask(mask, B: int, R: int, n: int, rank: int, r0: int, rc: int
     on the user mask (MASK_CACHE) or, without one, per shape."""
     from ..ops import flash
 
-    def own_cols(m):
+    def own_cols(m):  # (a row of column indices: -1 = always masked)
         m = m.clone()
-        m[..., rank * rc:(rank + 1) * rc] = True
+        m[..., rank * rc:(rank + 1) * rc] = True if m.dtype == torch.bool else -1
         return m
 
     if mask is not None:
@@ -387,8 +389,9 @@ def _own_excluded_mask(mask, B: int, R: int, n: int, rank: int, r0: int, rc: int
     if key not in _OWN_EX:
         if len(_OWN_EX) >= 8:
             _OWN_EX.pop(next(iter(_OWN_EX)))
-        _OWN_EX[key] = flash.prepare_mask(own_cols(torch.zeros(B, R, n * rc, dtype=torch.bool, device=dev)),
-                                          B, R, n * rc)
+        # generated (csrc/mask_pack.hip: mask_gen), not packed from a (B, R, n*rc) tensor of zeros
+        segs = [(0, rank * rc, 0), (rank * rc, rc, -1), ((rank + 1) * rc, (n - rank - 1) * rc, (rank + 1) * rc)]
+        _OWN_EX[key] = flash.generate_mask(_NOTHING_MASKED, B, R, n * rc, 0, segments=segs, device=dev)
     return _OWN_EX[key]
 
 
@@ -497,6 +500,9 @@ class SeqParallelAttention(torch.autograd.Function):
                     packed_full = mask.get()
                 mask = mask.raw
         mask = getattr(mask, "raw", mask)
+        # a StructuredMask: bound to this rank's rows for the kernels' generated packed masks; the
+        # torch path below gets its dense tensor, built once here
+        mask = resolve_mask(mask, B, R, n * qv.shape[1], rank, use_hip, k.device)
         segmented = n > 1 and (FLAGS.local_first or len(chunks) > 1)
         sbuf = dsbuf = None
         # a backward can run on this forward (grad mode is off inside Function.forward: autograd's
@@ -757,7 +763,9 @@ def seq_parallel_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor],
     comm = comm or _comm.get_comm()
     if k.dim() != 3 or qv.dim() != 3 or qv.shape[-1] <= k.shape[-1]:
         raise ValueError("seq_parallel_attention_packed expects k (B, R, C) and qv (B, R, C + Cv)")
-    if mask is not None:
+    if isinstance(mask, StructuredMask):
+        mask.check(k.shape[0])
+    elif mask is not None:
         T = qv.shape[1] * comm.world_size
         if tuple(mask.shape) != (k.shape[0], k.shape[1], T):
             raise ValueError(f"mask must be (B, R, T)=({k.shape[0]}, {k.shape[1]}, {T}), got {tuple(mask.shape)}")
@@ -772,7 +780,9 @@ def seq_parallel_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tenso
     """Fused sequence-parallel attention on projected, head-interleaved (B, R, H*d) tensors.
 
     ``k``: row side (local rows), ``q``/``v``: gathered side (local shards), ``mask``: bool
-    (B, R, T) with True = masked, or None.  Returns (B, R, H*dv) in ``k``'s dtype.
+    (B, R, T) with True = masked, a :class:`xdot.StructuredMask` (causal / window / lengths; its
+    packed form is generated on the GPU, the torch path builds its dense tensor), or None.
+    Returns (B, R, H*dv) in ``k``'s dtype.
     """
     if k.dim() != 3 or q.dim() != 3 or v.dim() != 3:
         raise ValueError("seq_parallel_attention expects (B, R, H*d) tensors")

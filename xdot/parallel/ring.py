@@ -40,6 +40,7 @@ import torch
 from torch import Tensor
 
 from .. import _ext
+from ..ops.mask import StructuredMask, resolve as resolve_mask
 from ..utils import comm as _comm
 from ..utils.checks import check_consistent
 from ..utils.env import FLAGS
@@ -200,6 +201,9 @@ class RingAttention(torch.autograd.Function):
         use_hip = (_ext.use_hip(k) and k.dtype in FLASH_DTYPES and qv.shape[-1] == 2 * C
                    and C // H in FLASH_HEAD_DIMS
                    and not (k.dtype == torch.float32 and C // H > WIDE_F32_NEEDS_SCORES))
+        # a StructuredMask: bound to this rank's rows (packed masks generated per block), or its
+        # dense tensor, built once, for the torch path
+        mask = resolve_mask(mask, B, R, n * R, comm.rank, use_hip, k.device)
         qv = qv.contiguous()
         rings = _Rings(comm, qv, _bidir())
         L = len(rings.lanes)
@@ -359,11 +363,13 @@ class RingAttention(torch.autograd.Function):
 def ring_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
                           comm: Optional[_comm.Communicator] = None) -> Tensor:
     """Ring sequence-parallel attention with a packed gathered side ``qv = [q | v]`` (B, R, C + Cv);
-    ``mask``: bool (B, R, T) (True = masked) or None.  Returns (B, R, Cv) in ``k``'s dtype."""
+    ``mask``: bool (B, R, T) (True = masked), a :class:`xdot.StructuredMask`, or None.  Returns (B, R, Cv) in ``k``'s dtype."""
     comm = comm or _comm.get_comm()
     if k.dim() != 3 or qv.dim() != 3 or qv.shape[-1] <= k.shape[-1] or qv.shape[:2] != k.shape[:2]:
         raise ValueError("ring_attention expects k (B, R, C) and qv (B, R, C + Cv) with equal R")
-    if mask is not None:
+    if isinstance(mask, StructuredMask):
+        mask.check(k.shape[0])
+    elif mask is not None:
         T = qv.shape[1] * comm.world_size
         if tuple(mask.shape) != (k.shape[0], k.shape[1], T):
             raise ValueError(f"mask must be (B, R, T)=({k.shape[0]}, {k.shape[1]}, {T}), got {tuple(mask.shape)}")
