@@ -4,71 +4,22 @@
 // header (fast rebuilds); this file only validates arguments on the host, resolves the
 // current HIP stream and calls the C-ABI launchers.  Every launch is bounds-checked on
 // the host against the tensors' storage so a bad stride can never turn into a GPU fault.
-#include <torch/library.h>
-#include <ATen/ATen.h>
-#include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime.h>
-
-#include "kernels.h"
-
-#include <rocprofiler-sdk-roctx/roctx.h>
+// The flash-attention ops are implemented (and bound to their schemas below) in bindings_flash.cpp.
+#include "bindings_common.h"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
 // sha256 of csrc/* + flags, compiled in by xdot/build.py (build/xdot/build_id.cpp)
 extern "C" const char xdot_build_id[];
 
+using namespace xdot::bind;
+
 namespace {
 
 std::string build_id() { return std::string(xdot_build_id + 14); }  // after "XDOT_BUILD_ID="
-
-// roctx ranges around every op (visible in rocprofv3 --marker-trace timelines); enabled by
-// XDOT_ROCTX=1 so the default path pays one predictable branch.
-bool roctx_on() {
-  static const bool v = [] {
-    const char* e = std::getenv("XDOT_ROCTX");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-struct Range {
-  bool on;
-  explicit Range(const char* name) : on(roctx_on()) {
-    if (on) roctxRangePushA(name);
-  }
-  ~Range() {
-    if (on) roctxRangePop();
-  }
-};
-
-
-
-int dt_code(at::ScalarType t) {
-  switch (t) {
-    case at::kFloat: return xdot::DT_F32;
-    case at::kBFloat16: return xdot::DT_BF16;
-    case at::kHalf: return xdot::DT_F16;
-    default: TORCH_CHECK(false, "xdot: unsupported dtype ", t);
-  }
-  return -1;
-}
-
-hipStream_t cur_stream(const at::Tensor& t) {
-  return c10::hip::getCurrentHIPStream(t.device().index()).stream();
-}
-
-// elements addressable from t.data_ptr() to the end of its storage
-int64_t avail_elems(const at::Tensor& t) {
-  const int64_t bytes = (int64_t)t.storage().nbytes() - t.storage_offset() * (int64_t)t.element_size();
-  return bytes / (int64_t)t.element_size();
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // XDOT_GEMM_LIB: which plain large products may take the library GEMM (at::baddbmm ->
 // hipBLASLt) on in-place strided views.  Default (unset / 0) = none: 16-bit products run gemm3
@@ -167,10 +118,6 @@ bool gemm_library(const at::Tensor& A, const at::Tensor& B, at::Tensor& C, int64
     at::baddbmm_out(c, c, a, b, beta, alpha);
   }
   return true;
-}
-
-void check_launch(hipError_t e, const char* what) {
-  TORCH_CHECK(e == hipSuccess, "xdot: ", what, " launch failed: ", hipGetErrorString(e));
 }
 
 // ------------------------------------------------------------------------------------
@@ -440,8 +387,7 @@ at::Tensor softmax_fwd(const at::Tensor& x, const c10::optional<at::Tensor>& mas
   }
   TORCH_CHECK(rows <= 0x7fffffff, "xdot.softmax_fwd: too many rows");
   c10::DeviceGuard guard(x.device());
-  TORCH_CHECK(xdot_softmax_fwd_launch(&a, dt_code(x.scalar_type()), vec, cur_stream(x)) == 0, "xdot.softmax_fwd: dtype");
-  check_launch(hipGetLastError(), "softmax_fwd");
+  launched(xdot_softmax_fwd_launch(&a, dt_code(x.scalar_type()), vec, cur_stream(x)), "softmax_fwd", "dtype");
   return y;
 }
 
@@ -457,8 +403,7 @@ at::Tensor softmax_bwd(const at::Tensor& y, const at::Tensor& dy, double scale) 
   a.scale = (float)scale; a.mdiv = 1; a.mmul = 0; a.mmod = 1;
   const bool vec = (T % 8 == 0) && aligned16(y.data_ptr()) && aligned16(dy.data_ptr()) && aligned16(dx.data_ptr());
   c10::DeviceGuard guard(y.device());
-  TORCH_CHECK(xdot_softmax_bwd_launch(&a, dt_code(y.scalar_type()), vec, cur_stream(y)) == 0, "xdot.softmax_bwd: dtype");
-  check_launch(hipGetLastError(), "softmax_bwd");
+  launched(xdot_softmax_bwd_launch(&a, dt_code(y.scalar_type()), vec, cur_stream(y)), "softmax_bwd", "dtype");
   return dx;
 }
 
@@ -509,336 +454,6 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> mask_gen(int64_t B, int64_t R, in
                        cur_stream(segs));
   check_launch(hipGetLastError(), "mask_gen");
   return {bits, flags, bitsT};
-}
-
-struct FlashGeom {
-  int64_t B, R, C, T, D, ld;
-};
-
-// rows: contiguous (B, R, C).  kc / vc: (B, T, C) views with unit inner stride and a common
-// row stride `ld` (C for separate tensors, 2C for the two halves of a packed [q | v]).
-// `bits`: the kt-major (B, NKT, R) words, or with colmajor the (B, NRT, Tpad) words of the
-// backward column kernel (mask_pack's third output)
-FlashGeom flash_check(const at::Tensor& rows, const at::Tensor& kc, const at::Tensor& vc, int64_t H,
-                      const c10::optional<at::Tensor>& bits, const c10::optional<at::Tensor>& flags,
-                      bool colmajor = false) {
-  TORCH_CHECK(rows.is_cuda() && kc.is_cuda() && vc.is_cuda(), "xdot.flash: GPU tensors required");
-  TORCH_CHECK(rows.is_contiguous(), "xdot.flash: rows must be contiguous");
-  TORCH_CHECK(rows.scalar_type() == kc.scalar_type() && rows.scalar_type() == vc.scalar_type(), "xdot.flash: dtype mismatch");
-  TORCH_CHECK(rows.scalar_type() == at::kBFloat16 || rows.scalar_type() == at::kHalf || rows.scalar_type() == at::kFloat,
-              "xdot.flash: bf16/fp16/fp32 only");
-  TORCH_CHECK(rows.dim() == 3 && kc.dim() == 3 && vc.sizes() == kc.sizes(), "xdot.flash: rows (B,R,C), cols (B,T,C)");
-  FlashGeom g{rows.size(0), rows.size(1), rows.size(2), kc.size(1), 0, kc.stride(1)};
-  TORCH_CHECK(kc.size(0) == g.B && kc.size(2) == g.C, "xdot.flash: batch / feature mismatch");
-  TORCH_CHECK(g.T > 0, "xdot.flash: empty key side");
-  for (const at::Tensor* t : {&kc, &vc}) {
-    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == g.ld && (g.B == 1 || t->stride(0) == g.T * g.ld),
-                "xdot.flash: key/value side must be (B, T, C) rows with a common row stride");
-    TORCH_CHECK((g.B - 1) * g.T * g.ld + (g.T - 1) * g.ld + g.C <= avail_elems(*t), "xdot.flash: key/value out of bounds");
-  }
-  TORCH_CHECK(g.ld % 8 == 0 && g.ld >= g.C, "xdot.flash: row stride must be a multiple of 8 elements");
-  TORCH_CHECK(H > 0 && g.C % H == 0, "xdot.flash: C not divisible by heads");
-  g.D = g.C / H;
-  TORCH_CHECK(g.D == 32 || g.D == 64 || g.D == 96 || g.D == 128 || g.D == 160 || g.D == 192 || g.D == 256 ||
-                  g.D == 384,
-              "xdot.flash: head dim must be 32/64/96/128 or (flash_wide.hip) 160/192/256/384");
-  TORCH_CHECK(g.T < (1LL << 31) && g.R < (1LL << 31) && g.B * H * ((g.R + 127) / 128) * 8 < (1LL << 31), "xdot.flash: too large");
-  TORCH_CHECK(aligned16(rows.data_ptr()) && aligned16(kc.data_ptr()) && aligned16(vc.data_ptr()), "xdot.flash: 16-byte alignment");
-  const bool hb = bits.has_value() && bits->defined(), hf = flags.has_value() && flags->defined();
-  TORCH_CHECK(hb == hf, "xdot.flash: mask bits and flags go together");
-  if (hb) {
-    const int64_t NKT = (g.T + 63) / 64;
-    const int64_t nwords = colmajor ? g.B * ((g.R + 63) / 64) * ((g.T + 127) / 128 * 128) : g.B * g.R * NKT;
-    TORCH_CHECK(bits->is_contiguous() && bits->numel() == nwords && bits->element_size() == 8,
-                colmajor ? "xdot.flash_bwd_cols: mask needs the column-major bits (mask_pack output 3)"
-                         : "xdot.flash: mask bits shape");
-    TORCH_CHECK(flags->is_contiguous() && flags->numel() == g.B * ((g.R + 31) / 32) * ((NKT + 3) & ~3),
-                "xdot.flash: mask flags shape");
-    TORCH_CHECK((reinterpret_cast<uintptr_t>(flags->data_ptr()) & 3) == 0, "xdot.flash: flags alignment");
-  }
-  return g;
-}
-
-// Column split of the row-block grid.  Every workgroup of a flash kernel does the same
-// work, so the launch runs in ceil(workgroups / slots) equal rounds (slots = 2 per CU x 256
-// CUs) and a last round that is barely occupied costs a whole round: T = 25000, H = 8 gives
-// 1568 row blocks = 3.06 rounds -> 24 % idle.  Pick the split s (<= 8, >= 8 column tiles per
-// split) minimising rounds(s) x (tiles / s + fixed per-workgroup cost ~ 8 tiles: prologue,
-// epilogue, the combine pass); ties keep fewer splits.
-int pick_split(int64_t blocks, int64_t T, int64_t slots, int64_t req) {
-  const int64_t nkt = (T + 63) / 64;
-  if (req > 0) return (int)std::max<int64_t>(1, std::min<int64_t>(req, nkt));
-  int best = 1;
-  double best_cost = 1e300;
-  for (int s = 1; s <= 8; ++s) {
-    if (s > 1 && nkt / s < 8) break;
-    const int64_t rounds = (blocks * s + slots - 1) / slots;
-    const double cost = (double)rounds * ((double)nkt / s + 8.0);
-    if (cost < best_cost * 0.985) { best_cost = cost; best = s; }
-  }
-  return best;
-}
-
-// Column splits of the row-side backward kernel.  It runs concurrently with the gathered-side
-// kernel (which has stream priority and owns the GPU while it runs): splitting the row kernel's
-// column sweep until its workgroups are no longer than the column kernel's (36 vs 48 MFMAs per
-// 64-tile step; R/64 tiles per column workgroup) lets it pack into that kernel's tail instead of
-// running a long tail of its own.  Measured at the N = 8 rank shape (R = 3125, T = 25000, one
-// MI355X, cols||rows): 2 splits 0.989, 3: 0.943, 4: 0.911, 6: 0.888 ms (profiles/r3_masked.md).
-int rows_split(int64_t B, int64_t R, int64_t T, int64_t H) {
-  const int64_t nkt = (T + 63) / 64, nrt = (R + 63) / 64;
-  const int base = pick_split(((R + 127) / 128) * B * H, T, 512, 0);
-  int64_t conc = (nkt * 36 + nrt * 48 - 1) / (nrt * 48);
-  conc = std::min<int64_t>(8, std::max<int64_t>(1, std::min<int64_t>(conc, nkt / 8)));
-  return std::max(base, (int)conc);
-}
-
-// Head-heavy forward grid (16-bit, whole-GPU launches).  A uniform column split makes every row
-// block pay the partial writes and a combine pass, and still ends on a part-full round: at N=1
-// (1568 row blocks, 512 slots) the auto split is 3 -> 10 rounds of 1/3 blocks plus a 3-slot
-// combine.  Instead each XCD (64 slots: 32 CUs x 2 workgroups, blockIdx % 8) runs its row blocks
-// whole and splits only its last `rem` blocks into enough column pieces to fill one more round;
-// only those tail rows go through partials and the (compact) combine.  Chosen when the round
-// model says it beats the uniform split; -> (whole, rem, split) per XCD, or false.
-// S: resident workgroups per XCD (64: 32 CUs x 2; the exact-fp32 forward runs 3 per CU); su: the
-// uniform split to beat (0: the 16-bit forward's pick_split)
-bool head_heavy_plan(int64_t NB, int64_t T, int* whole, int* rem, int* split, int64_t S = 64, int su = 0) {
-  if (NB % 8) return false;
-  const int64_t m = NB / 8, nkt = (T + 63) / 64;
-  const int64_t full = m / S, r = m % S;
-  if (r == 0 || full == 0) return false;
-  if (su <= 0) su = pick_split(NB, T, 8 * S, 0);
-  const double cu = (double)((NB * su + 8 * S - 1) / (8 * S)) * ((double)nkt / su + 8.0);
-  double best = 1e300;
-  int bs = 0;
-  for (int s = 1; s <= 16; ++s) {
-    if (s > 1 && nkt / s < 8) break;
-    const double c = (double)full * ((double)nkt + 8.0) + (double)((r * s + S - 1) / S) * ((double)nkt / s + 8.0);
-    if (c < best * 0.985) { best = c; bs = s; }
-  }
-  if (bs < 2 || best >= cu * 0.97) return false;
-  *whole = (int)(full * S);
-  *rem = (int)r;
-  *split = bs;
-  return true;
-}
-
-// fp32 score buffer (flash_f32.hip exact, flash_x3.hip split): (B*H, ceil(R/32), ceil(T/32)) blocks
-// of 1024 floats
-float* sbuf_ptr(const c10::optional<at::Tensor>& sbuf, const FlashGeom& g, int64_t H, const at::Tensor& rows,
-                int64_t fp32_mode, const char* what) {
-  if (!sbuf.has_value() || !sbuf->defined()) return nullptr;
-  const auto& t = *sbuf;
-  TORCH_CHECK(rows.scalar_type() == at::kFloat && (fp32_mode == 0 || fp32_mode == 1), what,
-              ": the score buffer is an fp32 (exact or split) feature");
-  const int64_t need = (g.B * H * ((g.R + 31) / 32) * ((g.T + 31) / 32) + 1) * 1024;  // + the dump block
-  TORCH_CHECK(t.is_cuda() && t.device() == rows.device() && t.scalar_type() == at::kFloat && t.is_contiguous() &&
-                  t.numel() == need && aligned16(t.data_ptr()),
-              what, ": score buffer must be a contiguous fp32 device tensor of ", need, " elements");
-  return t.data_ptr<float>();
-}
-
-std::tuple<at::Tensor, at::Tensor> flash_fwd(const at::Tensor& rows, const at::Tensor& kc, const at::Tensor& vc,
-                                             const c10::optional<at::Tensor>& bits, const c10::optional<at::Tensor>& flags,
-                                             int64_t H, double scale, int64_t nsplit, bool prescaled, int64_t fp32_mode,
-                                             const c10::optional<at::Tensor>& sbuf) {
-  Range rr_("xdot.flash_fwd");
-  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags);
-  float* sb = sbuf_ptr(sbuf, g, H, rows, fp32_mode, "xdot.flash_fwd");
-  auto out = at::empty_like(rows);
-  auto lse = at::empty({g.B, H, g.R}, rows.options().dtype(at::kFloat));
-  const int rpw = xdot_flash_fwd_rows_per_wg();
-  const int64_t NB = ((g.R + rpw - 1) / rpw) * g.B * H;
-  int hw = 0, hr = 0, hs = 0;
-  bool heavy = nsplit == 0 && rows.scalar_type() != at::kFloat && g.D <= 128 && head_heavy_plan(NB, g.T, &hw, &hr, &hs);
-  int ns = heavy ? hs : pick_split(NB, g.T, 512, nsplit);
-  if (nsplit == 0 && rows.scalar_type() == at::kFloat) {  // fp32 kernels: their own occupancy / tile model
-    const int f = xdot_flash_f32_row_splits(0, (int)fp32_mode, (int)g.D, sb != nullptr, NB, g.T);
-    if (f > 0) ns = f;
-    // exact fp32 (D <= 128): the head-heavy grid when the round model prefers it over that split
-    const int occ = fp32_mode == 0 && g.D <= 128 && xdot_flash_f32_heavy() ? xdot_flash_f32_fwd_occ((int)g.D, sb != nullptr) : 0;
-    if (occ > 0 && head_heavy_plan(NB, g.T, &hw, &hr, &hs, (int64_t)occ * (xdot_num_cus() / 8), ns)) {
-      heavy = true;
-      ns = hs;
-    }
-  }
-  if (nsplit == 0 && g.D > 128) {  // wide kernels (one workgroup per CU): their own occupancy
-    const int f = xdot_flash_wide_splits(0, dt_code(rows.scalar_type()), (int)g.D, sb != nullptr, NB, (g.T + 31) / 32);
-    if (f > 0) ns = f;
-  }
-  at::Tensor opart, lpart;
-  if (heavy) {  // compact partials of the split tail blocks only
-    opart = at::empty({(int64_t)hs * 8 * hr * 128 * g.D}, rows.options().dtype(at::kFloat));
-    lpart = at::empty({(int64_t)hs * 8 * hr * 128}, rows.options().dtype(at::kFloat));
-  } else if (ns > 1) {
-    opart = at::empty({ns, g.B, g.R, g.C}, rows.options().dtype(at::kFloat));
-    lpart = at::empty({ns, g.B, H, g.R}, rows.options().dtype(at::kFloat));
-  }
-  xdot::fa::FwdArgs a{};
-  if (heavy) {
-    a.xrbs = (int)(NB / 8);
-    a.xwhole = hw;
-    a.xrem = hr;
-  }
-  a.rows = rows.data_ptr(); a.kc = kc.data_ptr(); a.vc = vc.data_ptr(); a.out = out.data_ptr();
-  a.lse = lse.data_ptr<float>();
-  const bool hb = bits.has_value() && bits->defined();
-  a.mbits = hb ? reinterpret_cast<const uint64_t*>(bits->data_ptr()) : nullptr;
-  a.mflags = hb ? flags->data_ptr<uint8_t>() : nullptr;
-  a.B = (int)g.B; a.H = (int)H; a.R = (int)g.R; a.T = (int)g.T; a.scale = (float)scale;
-  a.ldkv = g.ld;
-  a.nsplit = ns;
-  a.opart = ns > 1 ? opart.data_ptr<float>() : nullptr;
-  a.lpart = ns > 1 ? lpart.data_ptr<float>() : nullptr;
-  a.prescaled = prescaled ? 1 : 0;
-  a.fp32_mode = (int)fp32_mode;
-  a.sbuf = sb;
-  c10::DeviceGuard guard(rows.device());
-  TORCH_CHECK(xdot_flash_fwd_launch(&a, dt_code(rows.scalar_type()), (int)g.D, cur_stream(rows)) == 0, "xdot.flash_fwd: config");
-  check_launch(hipGetLastError(), "flash_fwd");
-  return {out, lse};
-}
-
-xdot::fa::BwdArgs bwd_args(const FlashGeom& g, const at::Tensor& dout, const at::Tensor& rows, const at::Tensor& kc,
-                           const at::Tensor& vc, const at::Tensor& lse, const c10::optional<at::Tensor>& bits,
-                           const c10::optional<at::Tensor>& flags, int64_t H, double scale) {
-  TORCH_CHECK(dout.sizes() == rows.sizes() && dout.is_contiguous() && dout.scalar_type() == rows.scalar_type(),
-              "xdot.flash_bwd: dout shape/dtype");
-  TORCH_CHECK(lse.is_contiguous() && lse.scalar_type() == at::kFloat && lse.numel() == g.B * H * g.R, "xdot.flash_bwd: lse");
-  xdot::fa::BwdArgs a{};
-  a.rows = rows.data_ptr(); a.kc = kc.data_ptr(); a.vc = vc.data_ptr(); a.dout = dout.data_ptr();
-  a.lse = lse.data_ptr<float>();
-  const bool hb = bits.has_value() && bits->defined();
-  a.mbits = hb ? reinterpret_cast<const uint64_t*>(bits->data_ptr()) : nullptr;
-  a.mflags = hb ? flags->data_ptr<uint8_t>() : nullptr;
-  a.B = (int)g.B; a.H = (int)H; a.R = (int)g.R; a.T = (int)g.T; a.scale = (float)scale;
-  a.ldkv = g.ld;
-  a.nsplit = 1;
-  return a;
-}
-
-// gathered-side grads, packed fp32 (B, T, 2C) = [dq | dv] partials for ONE reduce-scatter,
-// + δ = rowsum(dO·O)
-std::tuple<at::Tensor, at::Tensor> flash_bwd_cols(const at::Tensor& dout, const at::Tensor& rows,
-                                                              const at::Tensor& kc, const at::Tensor& vc,
-                                                              const at::Tensor& out, const at::Tensor& lse,
-                                                              const c10::optional<at::Tensor>& bits,
-                                                              const c10::optional<at::Tensor>& flags, int64_t H,
-                                                              double scale, const c10::optional<at::Tensor>& delta_in,
-                                                              bool fp32_out, bool prescaled,
-                                                              const c10::optional<at::Tensor>& lse2_in,
-                                                              int64_t fp32_mode,
-                                                              const c10::optional<at::Tensor>& sbuf,
-                                                              const c10::optional<at::Tensor>& dsbuf, int64_t passes,
-                                                              const c10::optional<at::Tensor>& dkv_out) {
-  Range rr_("xdot.flash_bwd_cols");
-  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags, /*colmajor=*/true);
-  float* sb = sbuf_ptr(sbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_cols");
-  float* dsb = sbuf_ptr(dsbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_cols (dS buffer)");
-  // a dS buffer alone: dS-only mode (the recomputing column kernel stores dS, D <= 128)
-  TORCH_CHECK(!dsb || sb || g.D <= 128, "xdot.flash_bwd_cols: a dS buffer without the score buffer needs D <= 128");
-  // passes 4: the fused exact-fp32 column pass (dQ and dV in one kernel); other families run both
-  // passes (3) instead
-  if (passes == 4 && (!sb || fp32_mode != 0 || g.D > 128 || rows.scalar_type() != at::kFloat)) passes = 3;
-  TORCH_CHECK(passes >= 1 && passes <= 4 && (passes >= 3 || (sb && dsb)),
-              "xdot.flash_bwd_cols: single passes (1 = dV, 2 = dQ) need the score and dS buffers");
-  TORCH_CHECK(out.sizes() == rows.sizes() && out.is_contiguous() && out.scalar_type() == rows.scalar_type(),
-              "xdot.flash_bwd_cols: out shape/dtype");
-  auto a = bwd_args(g, dout, rows, kc, vc, lse, bits, flags, H, scale);
-  a.prescaled = prescaled ? 1 : 0;
-  a.fp32_mode = (int)fp32_mode;
-  at::Tensor dkv;
-  if (dkv_out.has_value() && dkv_out->defined()) {  // the other pass's output, completed in place
-    dkv = *dkv_out;
-    TORCH_CHECK(dkv.is_contiguous() && dkv.sizes() == at::IntArrayRef({g.B, g.T, 2 * g.C}) &&
-                    dkv.scalar_type() == (fp32_out ? at::kFloat : kc.scalar_type()) && dkv.device() == rows.device(),
-                "xdot.flash_bwd_cols: dkv_out");
-  } else {
-    dkv = at::empty({g.B, g.T, 2 * g.C}, fp32_out ? kc.options().dtype(at::kFloat) : kc.options());
-  }
-  const bool have_delta = delta_in.has_value() && delta_in->defined();
-  at::Tensor delta;
-  if (have_delta) {
-    delta = *delta_in;
-    TORCH_CHECK(delta.is_contiguous() && delta.scalar_type() == at::kFloat && delta.numel() == g.B * H * g.R &&
-                    delta.device() == rows.device(), "xdot.flash_bwd_cols: delta");
-  } else {
-    delta = at::empty({g.B, H, g.R}, rows.options().dtype(at::kFloat));
-  }
-  a.dkc = dkv.data_ptr(); a.dvc = static_cast<char*>(dkv.data_ptr()) + g.C * dkv.element_size(); a.ldg = 2 * g.C;
-  a.dkv16 = (fp32_out || rows.scalar_type() == at::kFloat) ? 0 : 1;
-  a.delta = delta.data_ptr<float>();
-  // lse2 = lse * log2 e: given (from flash_bwd_prep, together with δ), or one prep pass here
-  const bool have_lse2 = have_delta && lse2_in.has_value() && lse2_in->defined();
-  at::Tensor lse2;
-  if (have_lse2) {
-    lse2 = *lse2_in;
-    TORCH_CHECK(lse2.is_contiguous() && lse2.scalar_type() == at::kFloat && lse2.numel() == g.B * H * g.R &&
-                    lse2.device() == rows.device(), "xdot.flash_bwd_cols: lse2");
-  } else {
-    lse2 = at::empty({g.B, H, g.R}, rows.options().dtype(at::kFloat));
-  }
-  a.lse2 = lse2.data_ptr<float>();
-  a.sbuf = sb;
-  a.dsbuf = dsb;
-  a.sb_passes = (int)passes;
-  c10::DeviceGuard guard(rows.device());
-  const int dt = dt_code(rows.scalar_type());
-  // prep: lse2 (+ δ unless given)
-  if (!have_lse2)
-    TORCH_CHECK(xdot_flash_bwd_delta_launch(&a, out.data_ptr(), have_delta ? nullptr : delta.data_ptr<float>(), dt,
-                                            (int)g.D, cur_stream(rows)) == 0,
-                "xdot.flash_bwd_cols: config");
-  // column kernels: row splits against the last-round tail (fp32 partials summed in the launcher;
-  // the exact / split fp32 kernels and the pipelined 16-bit kernel, else 1)
-  at::Tensor cpq, cpv;
-  if (dt != xdot::DT_F32 || g.D > 128 || (!a.prescaled && !a.dkv16)) {
-    int sq = 1, sv = 1;  // (the single-pass recompute kernels use sq for both halves: sv == sq there)
-    TORCH_CHECK(xdot_flash_cols_splits(&a, dt, (int)g.D, &sq, &sv) == 0, "xdot.flash_bwd_cols: split config");
-    const bool run_q = !sb || passes == 4 || (passes & 2), run_v = !sb || passes == 4 || (passes & 1);
-    int hw = 0, hr = 0, hs = 0;
-    if (dt == xdot::DT_F32 && xdot_flash_f32_cols_heavy(&a, (int)g.D, sq, &hw, &hr, &hs)) {
-      // head-heavy fused column pass: compact partials of the XCDs' tail blocks only
-      const int64_t W = ((g.T + 127) / 128) * g.B * H;
-      cpq = at::empty({(int64_t)hs * 8 * hr * 128 * g.D}, rows.options().dtype(at::kFloat));
-      cpv = at::empty({(int64_t)hs * 8 * hr * 128 * g.D}, rows.options().dtype(at::kFloat));
-      a.cpq = cpq.data_ptr<float>();
-      a.cpv = cpv.data_ptr<float>();
-      a.csq = a.csv = hs;
-      a.xcb = (int)(W / 8);
-      a.xwhole = hw;
-      a.xrem = hr;
-    }
-    if (a.xcb == 0 && run_q && sq > 1) {
-      cpq = at::empty({sq, g.B, g.T, g.C}, rows.options().dtype(at::kFloat));
-      a.cpq = cpq.data_ptr<float>();
-      a.csq = sq;
-    }
-    if (a.xcb == 0 && run_v && sv > 1) {
-      cpv = at::empty({sv, g.B, g.T, g.C}, rows.options().dtype(at::kFloat));
-      a.cpv = cpv.data_ptr<float>();
-      a.csv = sv;
-    }
-  }
-  TORCH_CHECK(xdot_flash_bwd_cols_launch(&a, dt, (int)g.D, cur_stream(rows)) == 0, "xdot.flash_bwd_cols: config");
-  check_launch(hipGetLastError(), "flash_bwd_cols");
-  return {dkv, delta};
-}
-
-// Σ over the leading (split) dim of fp32 partials, cast to out_dtype, one pass
-at::Tensor sum_partials(const at::Tensor& part, at::ScalarType out_dtype) {
-  Range rr_("xdot.sum_partials");
-  TORCH_CHECK(part.is_cuda() && part.is_contiguous() && part.scalar_type() == at::kFloat && part.dim() >= 2,
-              "xdot.sum_partials: contiguous fp32 (S, ...) device tensor");
-  std::vector<int64_t> shape(part.sizes().begin() + 1, part.sizes().end());
-  auto out = at::empty(shape, part.options().dtype(out_dtype));
-  const int64_t n = out.numel();
-  TORCH_CHECK(n % 4 == 0 && aligned16(part.data_ptr()), "xdot.sum_partials: numel % 4 and 16-byte alignment");
-  c10::DeviceGuard guard(part.device());
-  TORCH_CHECK(xdot_sum_partials_launch(part.data_ptr<float>(), out.data_ptr(), (int)part.size(0), n, dt_code(out_dtype),
-                                       cur_stream(part)) == 0, "xdot.sum_partials: unsupported dtype");
-  check_launch(hipGetLastError(), "sum_partials");
-  return out;
 }
 
 // Projection GEMM (csrc/gemm_proj.hip): nn = false: y = x Wᵀ (+ bias), W (N, K); nn = true:
@@ -1008,25 +623,10 @@ std::tuple<at::Tensor, at::Tensor> mse_fwd(const at::Tensor& y, const at::Tensor
   auto part = at::empty({nparts}, y.options().dtype(at::kFloat));
   auto loss = at::empty({}, y.options());
   c10::DeviceGuard guard(y.device());
-  TORCH_CHECK(xdot_mse_fwd_launch(y.data_ptr(), t.data_ptr(), dy.data_ptr(), part.data_ptr<float>(), nparts,
-                                  loss.data_ptr(), y.numel(), dt_code(st_), cur_stream(y)) == 0,
-              "xdot.mse_fwd: launch rejected");
-  check_launch(hipGetLastError(), "mse_fwd");
+  launched(xdot_mse_fwd_launch(y.data_ptr(), t.data_ptr(), dy.data_ptr(), part.data_ptr<float>(), nparts, loss.data_ptr(),
+                               y.numel(), dt_code(st_), cur_stream(y)),
+           "mse_fwd", "launch rejected");
   return {loss, dy};
-}
-
-// row side of the flash kernels pre-multiplied by scale * log2(e), in the input dtype
-at::Tensor flash_prescale(const at::Tensor& x, double scale) {
-  Range rr_("xdot.flash_prescale");
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf) &&
-                  x.numel() % 8 == 0 && aligned16(x.data_ptr()),
-              "xdot.flash_prescale: contiguous 16-byte aligned bf16/fp16 device tensor, numel % 8 == 0");
-  auto out = at::empty_like(x);
-  c10::DeviceGuard guard(x.device());
-  TORCH_CHECK(xdot_prescale_rows_launch(x.data_ptr(), out.data_ptr(), x.numel(), (float)scale, dt_code(x.scalar_type()),
-                                        cur_stream(x)) == 0, "xdot.flash_prescale: dtype");
-  check_launch(hipGetLastError(), "flash_prescale");
-  return out;
 }
 
 // dst[i] <- src[i] converted to dst[i]'s dtype (fp32 / bf16 / fp16), every pair in one launch per
@@ -1063,8 +663,7 @@ void cast_multi(at::TensorList src, at::TensorList dst) {
       blk += (int)nb;
     }
     a.blk0[a.nt] = blk;
-    TORCH_CHECK(xdot_cast_multi_launch(&a, cur_stream(dst[0])) == 0, "xdot.cast_multi: dtype");
-    check_launch(hipGetLastError(), "cast_multi");
+    launched(xdot_cast_multi_launch(&a, cur_stream(dst[0])), "cast_multi", "dtype");
   }
 }
 
@@ -1131,241 +730,9 @@ void adamw_step(at::TensorList params, at::TensorList grads, at::TensorList exp_
     a.dev_state = dev_state ? 1 : 0;
     a.lr_dev = dev_state ? lr_t->data_ptr<float>() : nullptr;
     a.g32 = g32 ? 1 : 0;
-    TORCH_CHECK(xdot_adamw_launch(&a, dt_code(dtype), cur_stream(params[0])) == 0, "xdot.adamw_step: dtype");
-    check_launch(hipGetLastError(), "adamw_step");
+    launched(xdot_adamw_launch(&a, dt_code(dtype), cur_stream(params[0])), "adamw_step", "dtype");
   }
 }
-
-// δ = rowsum(dO ⊙ O) per (b, h, row), fp32 (B, H, R)
-at::Tensor flash_bwd_delta(const at::Tensor& dout, const at::Tensor& out, int64_t H) {
-  Range rr_("xdot.flash_bwd_delta");
-  TORCH_CHECK(dout.is_cuda() && dout.dim() == 3 && dout.is_contiguous() && out.sizes() == dout.sizes() &&
-                  out.is_contiguous() && out.scalar_type() == dout.scalar_type() && out.device() == dout.device(),
-              "xdot.flash_bwd_delta: dout/out must be matching contiguous (B, R, H*D) device tensors");
-  TORCH_CHECK(H > 0 && dout.size(2) % H == 0, "xdot.flash_bwd_delta: H");
-  xdot::fa::BwdArgs a{};
-  a.dout = dout.data_ptr();
-  a.B = (int)dout.size(0); a.R = (int)dout.size(1); a.H = (int)H;
-  auto delta = at::empty({dout.size(0), H, dout.size(1)}, dout.options().dtype(at::kFloat));
-  c10::DeviceGuard guard(dout.device());
-  TORCH_CHECK(xdot_flash_bwd_delta_launch(&a, out.data_ptr(), delta.data_ptr<float>(), dt_code(dout.scalar_type()),
-                                          (int)(dout.size(2) / H), cur_stream(dout)) == 0,
-              "xdot.flash_bwd_delta: unsupported dtype/head dim");
-  check_launch(hipGetLastError(), "flash_bwd_delta");
-  return delta;
-}
-
-// δ = rowsum(dO ⊙ O) and lse2 = lse * log2 e, both fp32 (B, H, R), in ONE pass: the fused
-// backward's prep (flash_bwd_cols then takes both and launches no prep of its own)
-std::tuple<at::Tensor, at::Tensor> flash_bwd_prep(const at::Tensor& dout, const at::Tensor& out, const at::Tensor& lse,
-                                                  int64_t H) {
-  Range rr_("xdot.flash_bwd_prep");
-  TORCH_CHECK(dout.is_cuda() && dout.dim() == 3 && dout.is_contiguous() && out.sizes() == dout.sizes() &&
-                  out.is_contiguous() && out.scalar_type() == dout.scalar_type() && out.device() == dout.device(),
-              "xdot.flash_bwd_prep: dout/out must be matching contiguous (B, R, H*D) device tensors");
-  TORCH_CHECK(H > 0 && dout.size(2) % H == 0, "xdot.flash_bwd_prep: H");
-  TORCH_CHECK(lse.is_contiguous() && lse.scalar_type() == at::kFloat && lse.device() == dout.device() &&
-                  lse.numel() == dout.size(0) * H * dout.size(1), "xdot.flash_bwd_prep: lse (B, H, R) fp32");
-  xdot::fa::BwdArgs a{};
-  a.dout = dout.data_ptr();
-  a.B = (int)dout.size(0); a.R = (int)dout.size(1); a.H = (int)H;
-  auto delta = at::empty({dout.size(0), H, dout.size(1)}, dout.options().dtype(at::kFloat));
-  auto lse2 = at::empty_like(delta);
-  a.lse = lse.data_ptr<float>();
-  a.lse2 = lse2.data_ptr<float>();
-  c10::DeviceGuard guard(dout.device());
-  TORCH_CHECK(xdot_flash_bwd_delta_launch(&a, out.data_ptr(), delta.data_ptr<float>(), dt_code(dout.scalar_type()),
-                                          (int)(dout.size(2) / H), cur_stream(dout)) == 0,
-              "xdot.flash_bwd_prep: unsupported dtype/head dim");
-  check_launch(hipGetLastError(), "flash_bwd_prep");
-  return {delta, lse2};
-}
-
-// row-side grad (this rank's rows), column-split when the row count is small
-at::Tensor flash_bwd_rows(const at::Tensor& dout, const at::Tensor& rows, const at::Tensor& kc, const at::Tensor& vc,
-                          const at::Tensor& lse, const at::Tensor& delta, const c10::optional<at::Tensor>& bits,
-                          const c10::optional<at::Tensor>& flags, int64_t H, double scale, int64_t nsplit,
-                          bool prescaled, int64_t fp32_mode, const c10::optional<at::Tensor>& sbuf,
-                          const c10::optional<at::Tensor>& dsbuf) {
-  Range rr_("xdot.flash_bwd_rows");
-  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags);
-  float* sb = sbuf_ptr(sbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_rows");
-  float* dsb = sbuf_ptr(dsbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_rows (dS buffer)");
-  TORCH_CHECK(!dsb || sb || g.D <= 128, "xdot.flash_bwd_rows: a dS buffer without the score buffer needs D <= 128");
-  TORCH_CHECK(delta.is_contiguous() && delta.scalar_type() == at::kFloat && delta.numel() == g.B * H * g.R,
-              "xdot.flash_bwd_rows: delta");
-  auto a = bwd_args(g, dout, rows, kc, vc, lse, bits, flags, H, scale);
-  auto drows = at::empty_like(rows);
-  int ns = nsplit > 0 ? pick_split(1, g.T, 1, nsplit) : rows_split(g.B, g.R, g.T, H);
-  if (nsplit == 0 && rows.scalar_type() == at::kFloat) {
-    const int f = xdot_flash_f32_row_splits(1, (int)fp32_mode, (int)g.D, sb != nullptr || dsb != nullptr,
-                                            ((g.R + 127) / 128) * g.B * H, g.T);
-    if (f > 0) ns = f;
-  }
-  if (nsplit == 0 && g.D > 128) {
-    const int f = xdot_flash_wide_splits(1, dt_code(rows.scalar_type()), (int)g.D, sb != nullptr,
-                                         ((g.R + 127) / 128) * g.B * H, (g.T + 31) / 32);
-    if (f > 0) ns = f;
-  }
-  at::Tensor dpart;
-  if (ns > 1) dpart = at::empty({ns, g.B, g.R, g.C}, rows.options().dtype(at::kFloat));
-  a.delta = delta.data_ptr<float>(); a.drows = drows.data_ptr();
-  a.nsplit = ns; a.dpart = ns > 1 ? dpart.data_ptr<float>() : nullptr;
-  a.prescaled = prescaled ? 1 : 0;
-  a.fp32_mode = (int)fp32_mode;
-  a.sbuf = sb;
-  a.dsbuf = dsb;
-  c10::DeviceGuard guard(rows.device());
-  TORCH_CHECK(xdot_flash_bwd_rows_launch(&a, dt_code(rows.scalar_type()), (int)g.D, cur_stream(rows)) == 0,
-              "xdot.flash_bwd_rows: config");
-  check_launch(hipGetLastError(), "flash_bwd_rows");
-  return drows;
-}
-
-// ---- chunked launches (gather / reduce-scatter pipelining) ----------------------------
-// column splits the row-block kernels would use for (R rows, T columns) — the caller sizes the
-// partial buffers with it
-int64_t flash_splits(int64_t B, int64_t R, int64_t T, int64_t H, bool rows_kernel) {
-  if (rows_kernel) return rows_split(B, R, T, H);
-  return pick_split(((R + 127) / 128) * B * H, T, 512, 0);
-}
-
-void check_part(const at::Tensor& t, int64_t slots_needed, int64_t per_slot, const char* what) {
-  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kFloat && t.dim() >= 1 &&
-                  t.size(0) >= slots_needed && t.numel() == t.size(0) * per_slot,
-              "xdot: partial buffer ", what, " has the wrong shape/dtype");
-}
-
-// forward over this column chunk into partial slots [sp0, sp0 + nsplit) of opart / lpart
-void flash_fwd_partial(const at::Tensor& rows, const at::Tensor& kc, const at::Tensor& vc,
-                       const c10::optional<at::Tensor>& bits, const c10::optional<at::Tensor>& flags, int64_t H,
-                       double scale, at::Tensor& opart, at::Tensor& lpart, int64_t sp0, int64_t nsplit,
-                       bool prescaled, int64_t fp32_mode) {
-  Range rr_("xdot.flash_fwd_partial");
-  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags);
-  TORCH_CHECK(sp0 >= 0 && nsplit >= 1, "xdot.flash_fwd_partial: slots");
-  const int ns = pick_split(1, g.T, 1, nsplit);  // clamps nsplit to the column tiles
-  check_part(opart, sp0 + ns, g.B * g.R * g.C, "opart");
-  check_part(lpart, sp0 + ns, g.B * H * g.R, "lpart");
-  xdot::fa::FwdArgs a{};
-  a.rows = rows.data_ptr(); a.kc = kc.data_ptr(); a.vc = vc.data_ptr();
-  const bool hb = bits.has_value() && bits->defined();
-  a.mbits = hb ? reinterpret_cast<const uint64_t*>(bits->data_ptr()) : nullptr;
-  a.mflags = hb ? flags->data_ptr<uint8_t>() : nullptr;
-  a.B = (int)g.B; a.H = (int)H; a.R = (int)g.R; a.T = (int)g.T; a.scale = (float)scale;
-  a.ldkv = g.ld;
-  a.nsplit = ns; a.sp0 = (int)sp0; a.force_partial = 1;
-  a.opart = opart.data_ptr<float>(); a.lpart = lpart.data_ptr<float>();
-  a.prescaled = prescaled ? 1 : 0;
-  a.fp32_mode = (int)fp32_mode;
-  c10::DeviceGuard guard(rows.device());
-  TORCH_CHECK(xdot_flash_fwd_launch(&a, dt_code(rows.scalar_type()), (int)g.D, cur_stream(rows)) == 0,
-              "xdot.flash_fwd_partial: config");
-  check_launch(hipGetLastError(), "flash_fwd_partial");
-}
-
-// merge all slots of opart / lpart -> (out in like's dtype, lse)
-std::tuple<at::Tensor, at::Tensor> flash_fwd_combine(const at::Tensor& opart, const at::Tensor& lpart, int64_t H,
-                                                     const at::Tensor& like) {
-  Range rr_("xdot.flash_fwd_combine");
-  TORCH_CHECK(like.dim() == 3 && like.is_cuda(), "xdot.flash_fwd_combine: like (B, R, C)");
-  const int64_t B = like.size(0), R = like.size(1), C = like.size(2), S = opart.size(0);
-  TORCH_CHECK(H > 0 && C % H == 0, "xdot.flash_fwd_combine: H");
-  check_part(opart, S, B * R * C, "opart");
-  check_part(lpart, S, B * H * R, "lpart");
-  auto out = at::empty_like(like);
-  auto lse = at::empty({B, H, R}, like.options().dtype(at::kFloat));
-  xdot::fa::FwdArgs a{};
-  a.out = out.data_ptr(); a.lse = lse.data_ptr<float>();
-  a.B = (int)B; a.H = (int)H; a.R = (int)R; a.nsplit = (int)S;
-  a.opart = opart.data_ptr<float>(); a.lpart = lpart.data_ptr<float>();
-  c10::DeviceGuard guard(like.device());
-  TORCH_CHECK(xdot_flash_fwd_combine_launch(&a, dt_code(like.scalar_type()), (int)(C / H), cur_stream(like)) == 0,
-              "xdot.flash_fwd_combine: config");
-  check_launch(hipGetLastError(), "flash_fwd_combine");
-  return {out, lse};
-}
-
-// merge all slots of opart / lpart into slot 0 in fp32 (the running partial of the ring
-// forward: two slots of memory per block instead of one per ring step).  O is merged in place
-// (each element is read and written by one thread); the merged LSE goes to lrun (lpart slot 0
-// is still read by the other threads of its row) and is copied back by the caller.
-void flash_fwd_merge(at::Tensor& opart, const at::Tensor& lpart, at::Tensor& lrun, int64_t H) {
-  Range rr_("xdot.flash_fwd_merge");
-  TORCH_CHECK(opart.dim() == 4 && opart.is_cuda(), "xdot.flash_fwd_merge: opart (S, B, R, C)");
-  const int64_t S = opart.size(0), B = opart.size(1), R = opart.size(2), C = opart.size(3);
-  TORCH_CHECK(H > 0 && C % H == 0 && (C / H) % 32 == 0, "xdot.flash_fwd_merge: H");
-  check_part(opart, S, B * R * C, "opart");
-  check_part(lpart, S, B * H * R, "lpart");
-  TORCH_CHECK(lrun.is_cuda() && lrun.is_contiguous() && lrun.scalar_type() == at::kFloat && lrun.numel() == B * H * R,
-              "xdot.flash_fwd_merge: lrun (B, H, R) fp32");
-  xdot::fa::FwdArgs a{};
-  a.out32 = opart.data_ptr<float>(); a.lse = lrun.data_ptr<float>();
-  a.B = (int)B; a.H = (int)H; a.R = (int)R; a.nsplit = (int)S;
-  a.opart = opart.data_ptr<float>(); a.lpart = lpart.data_ptr<float>();
-  c10::DeviceGuard guard(opart.device());
-  // dtype only selects the (unused) 16-bit output path
-  TORCH_CHECK(xdot_flash_fwd_combine_launch(&a, xdot::DT_BF16, (int)(C / H), cur_stream(opart)) == 0,
-              "xdot.flash_fwd_merge: config");
-  check_launch(hipGetLastError(), "flash_fwd_merge");
-}
-
-// out = Σ_s part[s] in fp32; out may be part[0] (running sums: each element is read and
-// written by one thread)
-void sum_partials_into(const at::Tensor& part, at::Tensor& out) {
-  Range rr_("xdot.sum_partials_into");
-  TORCH_CHECK(part.is_cuda() && part.is_contiguous() && part.scalar_type() == at::kFloat && part.dim() >= 2,
-              "xdot.sum_partials_into: contiguous fp32 (S, ...) device tensor");
-  const int64_t n = part.numel() / part.size(0);
-  TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.scalar_type() == at::kFloat && out.numel() == n,
-              "xdot.sum_partials_into: out must be a contiguous fp32 slot");
-  TORCH_CHECK(n % 4 == 0 && aligned16(part.data_ptr()) && aligned16(out.data_ptr()),
-              "xdot.sum_partials_into: numel % 4 and 16-byte alignment");
-  c10::DeviceGuard guard(part.device());
-  TORCH_CHECK(xdot_sum_partials_launch(part.data_ptr<float>(), out.data_ptr(), (int)part.size(0), n, xdot::DT_F32,
-                                       cur_stream(part)) == 0, "xdot.sum_partials_into");
-  check_launch(hipGetLastError(), "sum_partials_into");
-}
-
-// row-side grads of this column chunk into partial slots [sp0, sp0 + nsplit) of dpart
-void flash_bwd_rows_partial(const at::Tensor& dout, const at::Tensor& rows, const at::Tensor& kc, const at::Tensor& vc,
-                            const at::Tensor& lse, const at::Tensor& delta, const c10::optional<at::Tensor>& bits,
-                            const c10::optional<at::Tensor>& flags, int64_t H, double scale, at::Tensor& dpart,
-                            int64_t sp0, int64_t nsplit, bool prescaled, int64_t fp32_mode) {
-  Range rr_("xdot.flash_bwd_rows_partial");
-  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags);
-  TORCH_CHECK(delta.is_contiguous() && delta.scalar_type() == at::kFloat && delta.numel() == g.B * H * g.R,
-              "xdot.flash_bwd_rows_partial: delta");
-  TORCH_CHECK(sp0 >= 0 && nsplit >= 1, "xdot.flash_bwd_rows_partial: slots");
-  const int ns = pick_split(1, g.T, 1, nsplit);
-  check_part(dpart, sp0 + ns, g.B * g.R * g.C, "dpart");
-  auto a = bwd_args(g, dout, rows, kc, vc, lse, bits, flags, H, scale);
-  a.delta = delta.data_ptr<float>();
-  a.nsplit = ns; a.sp0 = (int)sp0; a.force_partial = 1; a.dpart = dpart.data_ptr<float>();
-  a.prescaled = prescaled ? 1 : 0;
-  a.fp32_mode = (int)fp32_mode;
-  c10::DeviceGuard guard(rows.device());
-  TORCH_CHECK(xdot_flash_bwd_rows_launch(&a, dt_code(rows.scalar_type()), (int)g.D, cur_stream(rows)) == 0,
-              "xdot.flash_bwd_rows_partial: config");
-  check_launch(hipGetLastError(), "flash_bwd_rows_partial");
-}
-
-// Σ of all dpart slots -> (B, R, C) in like's dtype
-at::Tensor flash_bwd_rows_sum(const at::Tensor& dpart, int64_t H, const at::Tensor& like) {
-  Range rr_("xdot.flash_bwd_rows_sum");
-  const int64_t B = like.size(0), R = like.size(1), C = like.size(2), S = dpart.size(0);
-  check_part(dpart, S, B * R * C, "dpart");
-  auto out = at::empty_like(like);
-  xdot::fa::BwdArgs a{};
-  a.drows = out.data_ptr(); a.dpart = dpart.data_ptr<float>();
-  a.B = (int)B; a.H = (int)H; a.R = (int)R; a.nsplit = (int)S;
-  c10::DeviceGuard guard(like.device());
-  TORCH_CHECK(xdot_flash_bwd_rows_sum_launch(&a, dt_code(like.scalar_type()), (int)(C / H), cur_stream(like)) == 0,
-              "xdot.flash_bwd_rows_sum: config");
-  check_launch(hipGetLastError(), "flash_bwd_rows_sum");
-  return out;
-}
-
 
 // ---- native xGMI pull collectives (csrc/ipc.hip; driven by xdot/utils/ipc.py) ----
 void ipc_ok(int rc, const char* what) { TORCH_CHECK(rc == 0, "xdot.", what, ": HIP error ", rc); }
@@ -1435,8 +802,7 @@ void ipc_all_gather(const at::Tensor& inp, at::Tensor& out, at::IntArrayRef stag
   TORCH_CHECK(out.numel() * out.element_size() == bytes * a.n && bytes % 16 == 0, "xdot.ipc_all_gather: sizes");
   a.shard = bytes;
   c10::DeviceGuard guard(inp.device());
-  TORCH_CHECK(xdot_ipc_all_gather_launch(&a, cur_stream(inp)) == 0, "xdot.ipc_all_gather: config");
-  check_launch(hipGetLastError(), "ipc_all_gather");
+  launched(xdot_ipc_all_gather_launch(&a, cur_stream(inp)), "ipc_all_gather");
 }
 
 // out <- Σ over ranks (rank order, fp32) of block `rank` of the rank-major inp
@@ -1450,8 +816,7 @@ void ipc_reduce_scatter(const at::Tensor& inp, at::Tensor& out, at::IntArrayRef 
   a.shard = bytes;
   a.dt = dt_code(inp.scalar_type());
   c10::DeviceGuard guard(inp.device());
-  TORCH_CHECK(xdot_ipc_reduce_scatter_launch(&a, cur_stream(inp)) == 0, "xdot.ipc_reduce_scatter: config");
-  check_launch(hipGetLastError(), "ipc_reduce_scatter");
+  launched(xdot_ipc_reduce_scatter_launch(&a, cur_stream(inp)), "ipc_reduce_scatter");
 }
 
 // ---- HIP graph node priorities: diagnostics (benchmarks/micro/graph_prio_probe.py) ----
@@ -1524,6 +889,9 @@ TORCH_LIBRARY(xdot, m) {
   m.def("flash_bwd_delta(Tensor dout, Tensor out, int H) -> Tensor");
   m.def("sum_partials(Tensor part, ScalarType out_dtype) -> Tensor");
   m.def("flash_splits(int B, int R, int T, int H, bool rows_kernel) -> int");
+  m.def("flash_fwd_plan(int B, int R, int T, int H, int D, ScalarType dtype, int fp32_mode, bool sbuf, int nsplit) -> int[]");
+  m.def("flash_cols_plan(int B, int R, int T, int H, int D, ScalarType dtype, int fp32_mode, bool sbuf, bool dsbuf, "
+        "int passes, bool prescaled, bool fp32_out) -> int[]");
   m.def("flash_fwd_partial(Tensor rows, Tensor kc, Tensor vc, Tensor? bits, Tensor? flags, int H, float scale, "
         "Tensor(a!) opart, Tensor(b!) lpart, int sp0, int nsplit, bool prescaled=False, int fp32_mode=0) -> ()");
   m.def("flash_fwd_combine(Tensor opart, Tensor lpart, int H, Tensor like) -> (Tensor, Tensor)");
@@ -1566,7 +934,6 @@ TORCH_LIBRARY_IMPL(xdot, CompositeExplicitAutograd, m) {
   m.impl("build_id", &build_id);
   m.impl("graph_kernel_priorities", &graph_kernel_priorities);
   m.impl("graph_set_kernel_priority", &graph_set_kernel_priority);
-  m.impl("flash_splits", &flash_splits);
   m.impl("ipc_info", &ipc_info);
   m.impl("ipc_alloc", &ipc_alloc);
   m.impl("ipc_free", &ipc_free);
@@ -1584,23 +951,10 @@ TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("softmax_bwd", &softmax_bwd);
   m.impl("mask_pack", &mask_pack);
   m.impl("mask_gen", &mask_gen);
-  m.impl("flash_fwd", &flash_fwd);
-  m.impl("flash_bwd_cols", &flash_bwd_cols);
-  m.impl("flash_bwd_rows", &flash_bwd_rows);
-  m.impl("flash_bwd_delta", &flash_bwd_delta);
-  m.impl("flash_bwd_prep", &flash_bwd_prep);
-  m.impl("sum_partials", &sum_partials);
-  m.impl("flash_prescale", &flash_prescale);
   m.impl("mse_fwd", &mse_fwd);
   m.impl("proj", &proj);
   m.impl("wgrad", &wgrad);
   m.impl("wgrad2", &wgrad2);
-  m.impl("flash_fwd_partial", &flash_fwd_partial);
-  m.impl("flash_fwd_combine", &flash_fwd_combine);
-  m.impl("flash_bwd_rows_partial", &flash_bwd_rows_partial);
-  m.impl("flash_bwd_rows_sum", &flash_bwd_rows_sum);
-  m.impl("flash_fwd_merge", &flash_fwd_merge);
-  m.impl("sum_partials_into", &sum_partials_into);
   m.impl("adamw_step", &adamw_step);
   m.impl("cast_multi", &cast_multi);
   m.impl("ipc_all_gather", &ipc_all_gather);

@@ -760,8 +760,7 @@ extern "C" int xdot_flash_f32_row_splits(int kernel, int fp32_mode, int D, bool 
   if (!dflt && !std::strcmp(e, "fwd")) {
     if (kernel == 1) return 0;
   } else if (!dflt) {
-    const int n = std::atoi(e);
-    return n > 0 ? std::min<int64_t>(n, (T + 31) / 32) : 0;
+    return (int)std::min<int64_t>(xdot::fa::env_int("XDOT_F32_SPLIT", 0), (T + 31) / 32);
   }
   return fp32_mode ? xdot_flash_f32_row_splits_x3(kernel, D, sbuf, W, T)
                    : xdot_flash_f32_row_splits_exact(kernel, D, sbuf, W, T);

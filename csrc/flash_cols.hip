@@ -336,20 +336,13 @@ extern "C" int xdot_flash_bwd_cols2_launch(const xdot::fa::BwdArgs* a, int dt, i
   return -1;
 }
 
-namespace {
-int cols2_csplit_env() {  // XDOT_CSPLIT, as in flash_f32.hip
-  const char* e = std::getenv("XDOT_CSPLIT");
-  return (!e || !*e || !std::strcmp(e, "auto")) ? -1 : std::max(1, std::min(4, std::atoi(e)));
-}
-}  // namespace
-
 // row splits of the pipelined column kernel: XDOT_CSPLIT=n only (opt-in)
 extern "C" int xdot_flash_cols_splits_cols2(const xdot::fa::BwdArgs* a, int dt, int D, int* sq) {
   using namespace xdot;
   using namespace xdot::fa;
   *sq = 1;
   const int NRT = (a->R + 63) / 64;
-  const int e = cols2_csplit_env();
+  const int e = env_int("XDOT_CSPLIT", 1, 4);  // as in flash_f32.hip, <= 4
   if (e >= 0) {
     *sq = (NRT + 1) / 2 / e >= 1 ? e : 1;
     return 0;

@@ -1117,11 +1117,6 @@ extern "C" int xdot_flash_bwd_cols_f32_launch(const xdot::fa::BwdArgs* a, int D,
 }
 
 namespace {
-// XDOT_CSPLIT: unset / "auto" = occupancy round model, "0" / "1" = no split, n = n splits (<= 8)
-int csplit_env() {
-  const char* e = std::getenv("XDOT_CSPLIT");  // read per call (tests switch it)
-  return (!e || !*e || !std::strcmp(e, "auto")) ? -1 : std::max(1, std::min(8, std::atoi(e)));
-}
 template <int D> void f32_splits(const xdot::fa::BwdArgs* a, int* sq, int* sv) {
   using namespace xdot::fa32;
   const int64_t W = (int64_t)((a->T + 127) / 128) * a->B * a->H;
@@ -1145,20 +1140,15 @@ template <int D> void f32_splits(const xdot::fa::BwdArgs* a, int* sq, int* sv) {
 
 extern "C" int xdot_flash_cols_splits_f32(const xdot::fa::BwdArgs* a, int D, int* sq, int* sv) {
   *sq = *sv = 1;
-  const int e = csplit_env();
+  // XDOT_CSPLIT: unset / "auto" = occupancy round model, "0" / "1" = no split, n = n splits (<= 8)
+  const int e = xdot::fa::env_int("XDOT_CSPLIT", 1, 8);
   if (e >= 0) {
-    const int NRT = (a->R + 31) / 32;
-    *sq = *sv = NRT / e >= 1 ? e : 1;
+    *sq = *sv = (a->R + 31) / 32 / e >= 1 ? e : 1;
     return 0;
   }
-  switch (D) {
-    case 32: f32_splits<32>(a, sq, sv); break;
-    case 64: f32_splits<64>(a, sq, sv); break;
-    case 96: f32_splits<96>(a, sq, sv); break;
-    case 128: f32_splits<128>(a, sq, sv); break;
-    default: return -1;
-  }
-  return 0;
+#define L(DV) f32_splits<DV>(a, sq, sv)
+  XF32_DISPATCH(L)
+#undef L
 }
 
 extern "C" int xdot_flash_rows_sum_f32_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st) {
@@ -1168,42 +1158,17 @@ extern "C" int xdot_flash_rows_sum_f32_launch(const xdot::fa::BwdArgs* a, int D,
   return 0;
 }
 
-// column splits of the exact-fp32 forward (kernel 0) / row-side backward (1), see kernels.h
+// head-heavy grid of the fused column pass (see kernels.h): the round model over 64-row tiles, against sq
 extern "C" int xdot_flash_f32_cols_heavy(const xdot::fa::BwdArgs* a, int D, int sq, int* whole, int* rem, int* split) {
   using namespace xdot::fa32;
-  if (!xdot_flash_f32_heavy() || !a->sbuf || a->sb_passes != 4 || a->fp32_mode || D > 128) return 0;
+  if (!xdot::fa::f32_heavy() || !a->sbuf || a->sb_passes != 4 || a->fp32_mode || D > 128) return 0;
   int occ = 0;
 #define OC(DV) \
   if (D == DV) occ = xdot::fa::wg_per_cu(bwd_cols_kernel<DV, true, true, true>, lds_bytes_ds<DV>());
   OC(32) OC(64) OC(96) OC(128)
 #undef OC
   const int64_t W = (int64_t)((a->T + 127) / 128) * a->B * a->H, S = (int64_t)occ * (xdot_num_cus() / 8);
-  if (occ <= 0 || S <= 0 || W % 8) return 0;
-  // the forward's round model (bindings.cpp head_heavy_plan) over 64-row tiles of the row sweep
-  const int64_t m = W / 8, n = (a->R + 63) / 64, full = m / S, r = m % S;
-  if (r == 0 || full == 0) return 0;
-  const int su = sq > 1 ? sq : 1;
-  const double cu = (double)((W * su + 8 * S - 1) / (8 * S)) * ((double)n / su + 8.0);
-  double best = 1e300;
-  int bs = 0;
-  for (int s = 1; s <= 16; ++s) {
-    if (s > 1 && n / s < 8) break;
-    const double c = (double)full * ((double)n + 8.0) + (double)((r * s + S - 1) / S) * ((double)n / s + 8.0);
-    if (c < best * 0.985) { best = c; bs = s; }
-  }
-  if (bs < 2 || best >= cu * 0.97) return 0;
-  *whole = (int)(full * S);
-  *rem = (int)r;
-  *split = bs;
-  return 1;
-}
-
-extern "C" int xdot_flash_f32_heavy() {
-  static const int v = [] {
-    const char* e = std::getenv("XDOT_F32_HEAVY");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return v;
+  return occ > 0 && xdot::fa::head_heavy_plan(W, (a->R + 63) / 64, S, std::max(sq, 1), whole, rem, split);
 }
 
 // resident forward workgroups per CU of the exact-fp32 forward the launcher would pick (0: none)
@@ -1220,22 +1185,20 @@ extern "C" int xdot_flash_f32_fwd_occ(int D, bool sbuf) {
   return occ;
 }
 
+// column splits of the exact-fp32 forward (kernel 0) / row-side backward (1), see kernels.h
 extern "C" int xdot_flash_f32_row_splits_exact(int kernel, int D, bool sbuf, int64_t W, int64_t T) {
   using namespace xdot::fa32;
-  int occ = 0;
-#define OC(DV)                                                                                                   \
-  if (D == DV)                                                                                                   \
-    occ = kernel == 0 ? (sbuf ? (fwd_direct_store() ? xdot::fa::wg_per_cu(fwd_kernel<DV, true, true>, lds_bytes<DV>()) \
-                                                    : xdot::fa::wg_per_cu(fwd_kernel<DV, true>, lds_bytes_sb<DV>())) \
-                              : xdot::fa::wg_per_cu(fwd_kernel<DV, false>, lds_bytes<DV>()))                   \
-                      : (sbuf ? xdot::fa::wg_per_cu(bwd_rows_ds_kernel<DV>, 2 * Cfg<DV>::IMG * 4)              \
-                              : xdot::fa::wg_per_cu(bwd_rows_kernel<DV>, lds_bytes<DV>()));
+  int occ = kernel == 0 ? xdot_flash_f32_fwd_occ(D, sbuf) : 0;
+#define OC(DV)                                                                                      \
+  if (kernel != 0 && D == DV)                                                                       \
+    occ = sbuf ? xdot::fa::wg_per_cu(bwd_rows_ds_kernel<DV>, 2 * Cfg<DV>::IMG * 4)                  \
+               : xdot::fa::wg_per_cu(bwd_rows_kernel<DV>, lds_bytes<DV>());
   OC(32) OC(64) OC(96) OC(128)
 #undef OC
   if (!occ) return 0;
   // the forward's workgroups are long (a 32-column fp32 tile is ~16x a 16-bit one), so a split
   // costs little beside a part-full last round: up to 32 splits at 0.1 % each (the N=8 rank's 200
-  // row blocks: 23 splits fill six rounds of 768 slots instead of 7 splits in two part-full ones)
+  // row blocks: 19 splits fill five rounds of 768 slots instead of 7 splits in two part-full ones)
   if (kernel == 0) return xdot::fa::pick_csplit(W, (int)((T + 31) / 32), occ * xdot_num_cus(), 32, 0.001);
   return xdot::fa::pick_csplit(W, (int)((T + 31) / 32), occ * xdot_num_cus(), 8, 0.004);
 }

@@ -895,20 +895,13 @@ extern "C" int xdot_flash_wide_cols_launch(const xdot::fa::BwdArgs* a, int dt, i
 #undef L
 }
 
-namespace {
-int wide_split_env() {  // XDOT_WIDE_SPLIT: unset / auto = the round model, 0 = the caller's old model, n = forced
-  const char* e = std::getenv("XDOT_WIDE_SPLIT");
-  if (!e || !*e || !std::strcmp(e, "auto")) return -1;
-  return std::max(0, std::atoi(e));
-}
-}  // namespace
-
 // Split counts of the wide kernels from their own occupancy (one workgroup per CU at these
 // widths): kernel 0 / 1 column splits of the forward / row side (0: the caller's model), kernel
 // 2 / 3 row splits of the column side's dQ / dV pass.  W = unsplit workgroups, n = tiles (32 wide)
 // of the split dimension.
 extern "C" int xdot_flash_wide_splits(int kernel, int dt, int D, bool sbuf, int64_t W, int64_t n) {
-  const int e = wide_split_env();
+  // XDOT_WIDE_SPLIT: unset / auto = the round model, 0 = the caller's old model, n = forced
+  const int e = xdot::fa::env_int("XDOT_WIDE_SPLIT", 0);
   if (e == 0) return kernel >= 2 ? 1 : 0;
   if (e > 0) return (int)std::min<int64_t>(e, n);
   int occ = 0;

@@ -870,10 +870,6 @@ extern "C" int xdot_flash_bwd_cols_x3_launch(const xdot::fa::BwdArgs* a, int D, 
 }
 
 namespace {
-int x3_csplit_env() {  // XDOT_CSPLIT, as in flash_f32.hip
-  const char* e = std::getenv("XDOT_CSPLIT");  // read per call (tests switch it)
-  return (!e || !*e || !std::strcmp(e, "auto")) ? -1 : std::max(1, std::min(4, std::atoi(e)));
-}
 template <int D> void x3_splits(const xdot::fa::BwdArgs* a, int* sq, int* sv) {
   using namespace xdot::fa3;
   const int64_t W = (int64_t)((a->T + 127) / 128) * a->B * a->H;
@@ -892,19 +888,14 @@ template <int D> void x3_splits(const xdot::fa::BwdArgs* a, int* sq, int* sv) {
 
 extern "C" int xdot_flash_cols_splits_x3(const xdot::fa::BwdArgs* a, int D, int* sq, int* sv) {
   *sq = *sv = 1;
-  const int e = x3_csplit_env();
+  const int e = xdot::fa::env_int("XDOT_CSPLIT", 1, 4);  // as in flash_f32.hip, <= 4
   if (e >= 0) {
     *sq = *sv = (a->R + 31) / 32 / e >= 1 ? e : 1;
     return 0;
   }
-  switch (D) {
-    case 32: x3_splits<32>(a, sq, sv); break;
-    case 64: x3_splits<64>(a, sq, sv); break;
-    case 96: x3_splits<96>(a, sq, sv); break;
-    case 128: x3_splits<128>(a, sq, sv); break;
-    default: return -1;
-  }
-  return 0;
+#define L(DV) x3_splits<DV>(a, sq, sv)
+  X3_DISPATCH(L)
+#undef L
 }
 
 // column splits of the split-bf16 forward (kernel 0) / row-side backward (1), see kernels.h

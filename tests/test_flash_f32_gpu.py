@@ -521,15 +521,23 @@ def test_module_fp32_ds_only_mode(gpu, monkeypatch, mode):
 
 
 @pytest.mark.parametrize("mask_kind", ["none", "random"])
-def test_flash_f32_head_heavy_forward(gpu, mask_kind):
+def test_flash_f32_head_heavy_forward(gpu, mask_kind, monkeypatch):
     """Exact-fp32 forward on the head-heavy grid (R = 97 row blocks x 8 heads = 776 blocks: each
     XCD's 96 resident slots run its first 96 blocks whole, its last block in column pieces merged
     by the tail combine): vs fp64 (<= 2e-6) and vs a forced uniform column split (<= 1e-6); a
-    fully masked row inside a tail block gives NaN output and -inf LSE like the reference."""
+    fully masked row inside a tail block gives NaN output and -inf LSE like the reference.  The
+    plan query asserts that the launch really takes that grid (and not with XDOT_F32_HEAVY=0)."""
+    from xdot import _ext
     from xdot.ops import flash
 
     B, R, H, D, T = 1, 97 * 128, 8, 96, 1024
     C = H * D
+    with torch.cuda.device(gpu):
+        split, heavy, _, rem = _ext.ops().flash_fwd_plan(B, R, T, H, D, torch.float32, 0, True, 0)
+        assert heavy == 1 and rem >= 1 and split >= 2, (split, heavy, rem)
+        monkeypatch.setenv("XDOT_F32_HEAVY", "0")
+        assert _ext.ops().flash_fwd_plan(B, R, T, H, D, torch.float32, 0, True, 0)[1] == 0
+        monkeypatch.delenv("XDOT_F32_HEAVY")
     g = torch.Generator(device="cpu").manual_seed(11)
     rows = torch.randn(B, R, C, generator=g).to(gpu)
     kc = torch.randn(1, B, T, C, generator=g).to(gpu)
@@ -558,15 +566,24 @@ def test_flash_f32_head_heavy_forward(gpu, mask_kind):
 
 
 @pytest.mark.parametrize("mask_kind", ["none", "random"])
-def test_flash_f32_fused_cols_head_heavy(gpu, mask_kind):
+def test_flash_f32_fused_cols_head_heavy(gpu, mask_kind, monkeypatch):
     """The fused exact-fp32 column pass on its head-heavy grid (T = 65 column blocks x 8 heads =
     520 blocks: each XCD's 64 resident slots sweep 64 blocks whole, its last block in row pieces
     whose compact partials the tail sum adds) == the two-pass score-buffer path (uniform splits)
-    to fp32 summation order, and the row side that reads its dS likewise."""
+    to fp32 summation order, and the row side that reads its dS likewise.  The plan query asserts
+    that the fused launch really takes that grid (and not with XDOT_F32_HEAVY=0)."""
+    from xdot import _ext
     from xdot.ops import flash
 
     B, R, H, D, T = 1, 2048, 8, 96, 65 * 128
     C = H * D
+    with torch.cuda.device(gpu):
+        query = (B, R, T, H, D, torch.float32, 0, True, False, 4, False, True)  # as the passes = 4 launch below
+        _, _, heavy, _, rem, split = _ext.ops().flash_cols_plan(*query)
+        assert heavy == 1 and rem >= 1 and split >= 2, (heavy, rem, split)
+        monkeypatch.setenv("XDOT_F32_HEAVY", "0")
+        assert _ext.ops().flash_cols_plan(*query)[2] == 0
+        monkeypatch.delenv("XDOT_F32_HEAVY")
     g = torch.Generator(device="cpu").manual_seed(13)
     rows = torch.randn(B, R, C, generator=g).to(gpu)
     kc = torch.randn(1, B, T, C, generator=g).to(gpu)

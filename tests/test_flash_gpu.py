@@ -317,7 +317,7 @@ def test_bf16_reduction_of_gathered_grads_bounded(gpu):
 
 @pytest.mark.parametrize("prescaled", [False, True])
 def test_flash_head_heavy_grid(gpu, prescaled):
-    """Whole-GPU forward with the head-heavy grid (bindings.cpp head_heavy_plan): each XCD runs
+    """Whole-GPU forward with the head-heavy grid (flash_plan.h head_heavy_plan): each XCD runs
     its row blocks whole and splits only its last ones into column pieces (compact partials +
     flash_fwd_combine_tail).  R = 65 row blocks per head, 8 heads: 64 whole + 1 split tail block
     per XCD.  Checked against the fp32 reference, against the uniform nsplit = 1 launch, and a
@@ -351,6 +351,35 @@ def test_flash_head_heavy_grid(gpu, prescaled):
     # whole blocks are bitwise the uniform launch's; tail rows agree to bf16 rounding
     assert torch.equal(out[:, : 64 * 128], o1[:, : 64 * 128])
     assert (out[:, keep].float() - o1[:, keep].float()).abs().max().item() < 2e-2
+
+
+def test_flash_plan_query_is_what_the_launch_uses(gpu):
+    """flash_fwd_plan / flash_splits return what the automatic launches choose: forcing the
+    returned split gives bitwise the automatic launch's output (a uniform split at this size; the
+    head-heavy grid has no forced equivalent)."""
+    from xdot import _ext
+    from xdot.ops import flash
+
+    B, R, T, H, D = 1, 256, 2048, 8, 96
+    C = H * D
+    g = torch.Generator(device="cpu").manual_seed(5)
+    rows = torch.randn(B, R, C, generator=g).to(gpu, torch.bfloat16)
+    kc = torch.randn(1, B, T, C, generator=g).to(gpu, torch.bfloat16)
+    vc = torch.randn(1, B, T, C, generator=g).to(gpu, torch.bfloat16)
+    do = torch.randn(B, R, C, generator=g).to(gpu, torch.bfloat16)
+    scale = 1.0 / math.sqrt(D)
+    kb, vb = flash.gathered_to_btc(kc), flash.gathered_to_btc(vc)
+    with torch.cuda.device(gpu):
+        ns, heavy, _, _ = _ext.ops().flash_fwd_plan(B, R, T, H, D, torch.bfloat16, 0, False, 0)
+    assert heavy == 0 and ns >= 1
+    out, lse = flash.fwd(rows, kb, vb, None, H, scale)
+    of, lf = flash.fwd(rows, kb, vb, None, H, scale, nsplit=ns)
+    assert torch.equal(out, of) and torch.equal(lse, lf)
+    delta = flash.bwd_delta(do, out, H)
+    nr = _ext.ops().flash_splits(B, R, T, H, True)
+    dr = flash.bwd_rows(do, rows, kb, vb, lse, delta, None, H, scale)
+    drf = flash.bwd_rows(do, rows, kb, vb, lse, delta, None, H, scale, nsplit=nr)
+    assert torch.equal(dr, drf)
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])

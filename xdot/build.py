@@ -2,7 +2,7 @@
 
 There is no hipify step and no JIT cache: ``hipcc --offload-arch=gfx950`` compiles every
 ``csrc/*.hip`` kernel translation unit (no torch headers, seconds each) plus the torch
-binding ``csrc/bindings.cpp`` and links them into one shared object that lives next to this
+bindings ``csrc/*.cpp`` and links them into one shared object that lives next to this
 file, so it travels with the repository snapshot to the GPU box.
 
 Usage::
@@ -135,17 +135,17 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 4) -> str:
         key = _dep_hash(src, hdrs, common)
         if force or _stale(obj, key):
             jobs_list.append(([HIPCC] + common + ["-c", src, "-o", obj], obj, key))
-    bind = os.path.join(CSRC, "bindings.cpp")
-    bobj = os.path.join(BUILD, "bindings.o")
-    objs.append(bobj)
-    bkey = _dep_hash(bind, hdrs, common)
-    if force or _stale(bobj, bkey):
-        tinc = []
-        for d in inc:
-            tinc += ["-isystem", d]
-        py_inc = sysconfig.get_paths()["include"]
-        jobs_list.append(([HIPCC] + common + tinc + ["-isystem", py_inc, "-x", "hip", "-c", bind, "-o", bobj],
-                          bobj, bkey))
+    tinc = []
+    for d in inc:
+        tinc += ["-isystem", d]
+    py_inc = sysconfig.get_paths()["include"]
+    for bind in sorted(glob.glob(os.path.join(CSRC, "*.cpp"))):
+        bobj = os.path.join(BUILD, os.path.splitext(os.path.basename(bind))[0] + ".o")
+        objs.append(bobj)
+        bkey = _dep_hash(bind, hdrs, common)
+        if force or _stale(bobj, bkey):
+            jobs_list.append(([HIPCC] + common + tinc + ["-isystem", py_inc, "-x", "hip", "-c", bind, "-o", bobj],
+                              bobj, bkey))
     # the provenance string: a one-line translation unit, so a source edit recompiles only it
     bid = tree_hash()
     idsrc = os.path.join(BUILD, "build_id.cpp")

@@ -100,7 +100,10 @@ variable                    default   effect
 ``XDOT_F32_SPLIT`` (C++)     auto      column splits of the fp32 forward / row-side kernels: auto =
                                       occupancy round model of the fp32 instantiation (up to 8);
                                       fwd = forward only; old = the 16-bit model; n = forced
-``XDOT_F32_FWD_DIRECT`` (C++) 1        the score-storing exact-fp32 forward scatters S straight to the
+``XDOT_F32_HEAVY`` (C++)     1         head-heavy grid of the exact-fp32 forward and fused column pass
+                                      where the round model prefers it (``csrc/flash_plan.h``);
+                                      0 = uniform splits for both (read per call: A/B in one process)
+``XDOT_F32_FWD_DIRECT`` (C++) 1       the score-storing exact-fp32 forward scatters S straight to the
                                       buffer (no LDS transpose tile: three workgroups per CU at
                                       D <= 96); 0 = the LDS-transposed store at two per CU
 ``XDOT_WIDE_SPLIT`` (C++)    auto      split counts of the wide-head (D > 128) kernels from their own
