@@ -908,6 +908,8 @@ TORCH_LIBRARY(xdot, m) {
         "Tensor? flags, int H, float scale, int nsplit=0, bool prescaled=False, int fp32_mode=0, Tensor? sbuf=None, "
         "Tensor? dsbuf=None) -> Tensor");
   m.def("flash_prescale(Tensor x, float scale) -> Tensor");
+  m.def("rope_table(int R, int D, int offset, Tensor inv_freq) -> (Tensor, Tensor)");
+  m.def("rope_apply(Tensor x, Tensor cos, Tensor sin, int H, bool inverse, float alpha, Tensor(a!) out) -> ()");
   m.def("mse_fwd(Tensor y, Tensor t) -> (Tensor, Tensor)");
   m.def("proj(Tensor x, Tensor w, Tensor? bias, bool nn, Tensor(a!)? out=None, int force=0, float alpha=1.0) -> Tensor");
   m.def("wgrad(Tensor dy, Tensor x, ScalarType out_dtype, int splits=0) -> Tensor");

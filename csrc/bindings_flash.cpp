@@ -387,6 +387,79 @@ at::Tensor flash_prescale(const at::Tensor& x, double scale) {
   return out;
 }
 
+// rotary table: cos / sin (R, D/2) fp32 of double(offset + row) * inv_freq[i] (csrc/rope.hip)
+std::tuple<at::Tensor, at::Tensor> rope_table(int64_t R, int64_t D, int64_t offset, const at::Tensor& inv_freq) {
+  Range rr_("xdot.rope_table");
+  TORCH_CHECK(D >= 2 && D % 2 == 0 && D < (1LL << 31), "xdot.rope_table: head dim must be even, got ", D);
+  TORCH_CHECK(R >= 0 && offset >= 0 && offset + R <= 2147483647LL, "xdot.rope_table: positions must stay below 2^31");
+  TORCH_CHECK(inv_freq.is_cuda() && inv_freq.scalar_type() == at::kDouble && inv_freq.is_contiguous() &&
+                  inv_freq.numel() == D / 2,
+              "xdot.rope_table: inv_freq must be a contiguous fp64 device tensor of D/2 entries");
+  auto cosb = at::empty({R, D / 2}, inv_freq.options().dtype(at::kFloat));
+  auto sinb = at::empty_like(cosb);
+  c10::DeviceGuard guard(inv_freq.device());
+  launched(xdot_rope_table_launch(cosb.data_ptr<float>(), sinb.data_ptr<float>(), inv_freq.data_ptr<double>(), (int)R,
+                                  (int)(D / 2), offset, cur_stream(inv_freq)),
+           "rope_table", "shape");
+  return {cosb, sinb};
+}
+
+// out = alpha * rotate(x): x, out (B, R, H*D) with unit inner stride and any row / batch strides
+// (the q half of a packed [q|v] buffer, a rank slot of the gather buffer); out may be x itself
+void rope_apply(const at::Tensor& x, const at::Tensor& cosb, const at::Tensor& sinb, int64_t H, bool inverse,
+                double alpha, at::Tensor& out) {
+  Range rr_("xdot.rope_apply");
+  TORCH_CHECK(x.is_cuda() && out.is_cuda() && cosb.is_cuda() && sinb.is_cuda() && out.device() == x.device() &&
+                  cosb.device() == x.device() && sinb.device() == x.device(),
+              "xdot.rope_apply: tensors of one GPU required");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf || x.scalar_type() == at::kFloat,
+              "xdot.rope_apply: bf16/fp16/fp32 only");
+  TORCH_CHECK(x.dim() == 3 && out.sizes() == x.sizes() && out.scalar_type() == x.scalar_type(),
+              "xdot.rope_apply: x and out must be (B, R, H*D) of one dtype");
+  const int64_t B = x.size(0), R = x.size(1), C = x.size(2);
+  TORCH_CHECK(H > 0 && C % H == 0 && (C / H) % 2 == 0, "xdot.rope_apply: H*D with an even head dim D, got C=", C, " H=", H);
+  TORCH_CHECK(B < (1LL << 31) && R < (1LL << 31) && C < (1LL << 31) && B * H < (1LL << 31), "xdot.rope_apply: too large");
+  const int64_t D = C / H;
+  TORCH_CHECK(cosb.scalar_type() == at::kFloat && sinb.scalar_type() == at::kFloat && cosb.is_contiguous() &&
+                  sinb.is_contiguous() && cosb.dim() == 2 && cosb.size(0) == R && cosb.size(1) == D / 2 &&
+                  sinb.sizes() == cosb.sizes(),
+              "xdot.rope_apply: cos / sin must be contiguous fp32 (R, D/2)");
+  if (x.numel() == 0) return;
+  const int64_t V = 16 / (int64_t)x.element_size();
+  int64_t st[4];  // x batch, x row, out batch, out row (a stride of a size-1 dim is never used)
+  bool vec = aligned16(x.data_ptr()) && aligned16(out.data_ptr()) && aligned16(cosb.data_ptr()) && aligned16(sinb.data_ptr());
+  int k = 0;
+  for (const at::Tensor* t : {&x, static_cast<const at::Tensor*>(&out)}) {
+    TORCH_CHECK(t->stride(2) == 1 || C == 1, "xdot.rope_apply: the last dimension must have stride 1");
+    const int64_t sb = B > 1 ? t->stride(0) : 0, sr = R > 1 ? t->stride(1) : 0;
+    TORCH_CHECK(sb >= 0 && sr >= 0, "xdot.rope_apply: negative strides");
+    TORCH_CHECK((B - 1) * sb + (R - 1) * sr + C <= avail_elems(*t), "xdot.rope_apply: view out of bounds");
+    vec = vec && sb % V == 0 && sr % V == 0;
+    st[k++] = sb;
+    st[k++] = sr;
+  }
+  // in place (the same view) or disjoint: a lane reads only the pairs it writes
+  if (x.data_ptr() == out.data_ptr()) {
+    TORCH_CHECK(st[0] == st[2] && st[1] == st[3], "xdot.rope_apply: an in-place out must be the same view as x");
+  } else {
+    const char* xb = static_cast<const char*>(x.data_ptr());
+    const char* ob = static_cast<const char*>(out.data_ptr());
+    const int64_t es = (int64_t)x.element_size();
+    const int64_t xe = ((B - 1) * st[0] + (R - 1) * st[1] + C) * es, oe = ((B - 1) * st[2] + (R - 1) * st[3] + C) * es;
+    TORCH_CHECK(xb + xe <= ob || ob + oe <= xb, "xdot.rope_apply: x and out overlap");
+  }
+  xdot::RopeArgs a{};
+  a.x = x.data_ptr(); a.out = out.data_ptr();
+  a.cos = cosb.data_ptr<float>(); a.sin = sinb.data_ptr<float>();
+  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D;
+  a.xs_b = st[0]; a.xs_r = st[1]; a.os_b = st[2]; a.os_r = st[3];
+  a.alpha = (float)alpha; a.inverse = inverse ? 1 : 0;
+  const int64_t half = D / 2;
+  const int mode = !vec ? 0 : (half % V == 0 ? 1 : (half > V ? 2 : 0));
+  c10::DeviceGuard guard(x.device());
+  launched(xdot_rope_apply_launch(&a, dt_code(x.scalar_type()), mode, cur_stream(x)), "rope_apply", "shape");
+}
+
 // δ = rowsum(dO ⊙ O) per (b, h, row), fp32 (B, H, R)
 at::Tensor flash_bwd_delta(const at::Tensor& dout, const at::Tensor& out, int64_t H) {
   Range rr_("xdot.flash_bwd_delta");
@@ -543,6 +616,8 @@ TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("sum_partials", &sum_partials);
   m.impl("sum_partials_into", &sum_partials_into);
   m.impl("flash_prescale", &flash_prescale);
+  m.impl("rope_table", &rope_table);
+  m.impl("rope_apply", &rope_apply);
   m.impl("flash_fwd_partial", &flash_fwd_partial);
   m.impl("flash_fwd_combine", &flash_fwd_combine);
   m.impl("flash_fwd_merge", &flash_fwd_merge);

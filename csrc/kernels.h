@@ -167,6 +167,19 @@ struct ProjArgs {
   int64_t lda, ldb, ldc;
   float alpha;       // C = alpha * (A . op(B) + bias)
 };
+// rotary position embedding (csrc/rope.hip) of x (B, R, H*D) -> out, same shape: unit inner stride,
+// row / batch strides in elements (out == x with the same strides: in place)
+struct RopeArgs {
+  const void* x;
+  void* out;
+  const float* cos;        // (R, D/2) fp32 table (xdot_rope_table_launch)
+  const float* sin;
+  int B, R, H, D;          // D even
+  int64_t xs_b, xs_r;      // x strides
+  int64_t os_b, os_r;      // out strides
+  float alpha;             // out = alpha * rotate(x)
+  int inverse;             // 1: rotate by -theta
+};
 namespace ipc {
 constexpr int MAXR = 8;     // ranks of one node
 constexpr int MAXG = 256;   // workgroups (byte ranges) per collective
@@ -245,6 +258,14 @@ int xdot_sum_partials2_launch(const float* pa, void* oa, int Sa, int64_t na, con
 // out = (16-bit) (x * (scale * log2 e)) elementwise, n % 8 == 0: the pre-scaled row side of the
 // flash kernels (the factor is formed in fp32 exactly as the kernels form it)
 int xdot_prescale_rows_launch(const void* x, void* out, int64_t n, float scale, int dt, hipStream_t st);
+// cos / sin (R, half) fp32 of the angles double(offset + row) * inv_freq[i]: product and sincos in
+// fp64, one rounding to fp32 (csrc/rope.hip)
+int xdot_rope_table_launch(float* cos, float* sin, const double* inv_freq, int R, int half, int64_t offset,
+                           hipStream_t st);
+// out = alpha * rotate(x) by the table's angles, half-split pairs (i, i + D/2) in every head.
+// mode 1: 16-byte vectors (D/2 a multiple of the vector width, pointers and strides 16-byte
+// aligned), 2: unaligned vectors plus a scalar tail (D/2 not a multiple), 0: scalar
+int xdot_rope_apply_launch(const xdot::RopeArgs* a, int dt, int mode, hipStream_t st);
 // rows per workgroup of the forward kernel (128)
 int xdot_flash_fwd_rows_per_wg();
 // one AdamW step over a->nt tensors of dtype dt (params/grads), fp32 moments

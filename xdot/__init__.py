@@ -15,4 +15,5 @@ from .parallel import (distributed_matmul_nt, distributed_matmul_all, distribute
                        LeftTransposeMultiplication, seq_parallel_attention, broadcast_parameters,
                        allreduce_gradients, GradSync, gather_sequence)
 from .models import DistributedDotProductAttn  # noqa: E402,F401
-from .ops import scale_mask_softmax, linear, FusedAdamW, MSELoss, mse_loss, StructuredMask  # noqa: E402,F401
+from .ops import (scale_mask_softmax, linear, FusedAdamW, MSELoss, mse_loss, StructuredMask,  # noqa: E402,F401
+                  Rotary, rope)

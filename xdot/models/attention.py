@@ -41,7 +41,11 @@ Keyword-only knobs (each mirrors an environment flag, the argument
                 dtype.  ``None``: compute in the input dtype;
 ``chunk_plan``  row chunks of the fused path's all-gather / reduce-scatter pipeline
                 (``XDOT_GATHER_CHUNKS``); the materialised path's chunking is ``offset``;
-``comm``        communicator (default: the process group of :func:`xdot.init`).
+``comm``        communicator (default: the process group of :func:`xdot.init`);
+``rope``        an :class:`xdot.Rotary`: ``k`` and ``q`` are rotated (rotary position embedding,
+                :mod:`xdot.ops.rope`) after their projections, at this rank's global positions
+                (``rank * R`` unless the object carries an offset; 0 with ``distributed=False``),
+                on every path; ``v`` is untouched.  ``None`` (default): no rotation, no launch.
 """
 from __future__ import annotations
 
@@ -55,12 +59,15 @@ from torch import Tensor
 from .. import _ext
 from ..ops.linear import linear
 from ..ops.mask import StructuredMask
+from ..ops.rope import Rotary, rope as _rope, rope_packed
 from ..ops.softmax import scale_mask_softmax
 from ..parallel.autograd import FullMultiplication, RightTransposeMultiplication
 from ..utils import comm as _comm
 from ..utils.env import FLAGS
 
 __all__ = ["DistributedDotProductAttn"]
+
+_LOG2E = 1.4426950408889634  # as xdot.models.fused: the row side's pre-scale is scale * log2 e
 
 
 def _adjacent(a: Tensor, b: Tensor) -> bool:
@@ -111,7 +118,7 @@ class DistributedDotProductAttn(nn.Module):
                  num_heads: int = 1, add_bias: bool = False, offset: Optional[int] = 32,
                  distributed: bool = True, *, impl: str = "auto", fused: Optional[bool] = None,
                  backend: str = "auto", dtype: Optional[torch.dtype] = None, chunk_plan: Optional[int] = None,
-                 comm: Optional[_comm.Communicator] = None):
+                 comm: Optional[_comm.Communicator] = None, rope: Optional[Rotary] = None):
         super().__init__()
         if fused is not None:
             if impl not in ("auto", "flash" if fused else "materialized"):
@@ -131,6 +138,11 @@ class DistributedDotProductAttn(nn.Module):
             raise ValueError(f"value_dim {value_dim} not divisible by num_heads {num_heads}")
         if impl not in ("auto", "flash", "materialized", "ring"):
             raise ValueError(f"impl must be auto|flash|materialized|ring, got {impl!r}")
+        if rope is not None:
+            if not isinstance(rope, Rotary):
+                raise TypeError(f"rope must be an xdot.Rotary or None, got {type(rope).__name__}")
+            if (key_dim // num_heads) % 2:
+                raise ValueError(f"rope needs an even head dim, got {key_dim // num_heads}")
         self.num_heads = num_heads
         self.value_dim = value_dim
         self.offset = offset
@@ -141,6 +153,7 @@ class DistributedDotProductAttn(nn.Module):
         self.compute_dtype = dtype
         self.chunk_plan = None if chunk_plan is None else int(chunk_plan)
         self.comm = comm
+        self.rope = rope
         self.keys = nn.Linear(key_dim, key_dim, bias=add_bias)
         self.queries = nn.Linear(query_dim, key_dim, bias=add_bias)
         self.values = nn.Linear(value_dim, value_dim, bias=add_bias)
@@ -191,9 +204,12 @@ class DistributedDotProductAttn(nn.Module):
                 # head dims the kernels do not take (or value width != key width): every head
                 # zero-padded to the next kernel dim, same scale 1/sqrt(dk)
                 qv = self._project_qv(queries, values)
-                qv = torch.cat([pa.pad_heads(qv[..., :H * dk], H, dk, Dp), pa.pad_heads(qv[..., H * dk:], H, dv, Dp)],
-                               dim=-1)
-                k = pa.pad_heads(self._proj(self.keys, keys), H, dk, Dp)
+                q, k = qv[..., :H * dk], self._proj(self.keys, keys)
+                if self.rope is not None:  # at width dk, before the zero padding
+                    off = self.rope.resolve(comm.rank, k.shape[1])
+                    q, k = _rope(q, H, self.rope, offset=off), _rope(k, H, self.rope, offset=off)
+                qv = torch.cat([pa.pad_heads(q, H, dk, Dp), pa.pad_heads(qv[..., H * dk:], H, dv, Dp)], dim=-1)
+                k = pa.pad_heads(k, H, dk, Dp)
                 o = seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm)
                 return self._proj(self.composition, pa.unpad_heads(o, H, dv, Dp))
             if isinstance(attn_mask, Tensor) and attn_mask.is_cuda and attn_mask.dim() == 3 and FLAGS.mask_async:
@@ -221,12 +237,22 @@ class DistributedDotProductAttn(nn.Module):
                     sync = (gs, id(self))
                 return AttnBlockFn.apply(keys, queries, attn_mask, self.keys.weight, self.keys.bias, wq, bq, wv, bv,
                                          self.composition.weight, self.composition.bias, self.num_heads, scale, comm,
-                                         self.chunk_plan, sync, torch.is_grad_enabled())
+                                         self.chunk_plan, sync, torch.is_grad_enabled(), self.rope)
             # gathered side first: its all-gather runs while the row-side GEMM computes
             qv = self._project_qv(queries, values)
+            pre = False
+            if self.rope is not None:  # q rotated before the gather is issued
+                off = self.rope.resolve(comm.rank, qv.shape[1])
+                qv = rope_packed(qv, H * dk, H, self.rope, off)
             pending = start_gather(qv, comm, chunks=self.chunk_plan)
             k = self._proj(self.keys, keys)
-            o = seq_parallel_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm, pending=pending)
+            if self.rope is not None:
+                # the row side's pre-scale rides in the rotation pass (its gradient comes back
+                # w.r.t. the unscaled rows: no factor in the backward)
+                pre = pa.prescale_wanted(k, qv, H)
+                k = rope_packed(k, H * dk, H, self.rope, off, alpha=scale * _LOG2E if pre else 1.0, bwd_alpha=1.0)
+            o = seq_parallel_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm, pending=pending,
+                                              k_prescaled=pre)
             return self._proj(self.composition, o)
         if self._pick_impl(keys) == "ring":
             from ..parallel.ring import ring_attention_packed
@@ -234,11 +260,19 @@ class DistributedDotProductAttn(nn.Module):
             comm = (self.comm or _comm.get_comm()) if self.distributed else _comm.LocalComm()
             qv = self._project_qv(queries, values)
             k = self._proj(self.keys, keys)
+            if self.rope is not None:
+                off = self.rope.resolve(comm.rank, k.shape[1])
+                qv = rope_packed(qv, self.num_heads * self.dim, self.num_heads, self.rope, off)
+                k = rope_packed(k, k.shape[-1], self.num_heads, self.rope, off)
             o = ring_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm)
             return self._proj(self.composition, o)
         k = self._proj(self.keys, keys)
         q = self._proj(self.queries, queries)
         v = self._proj(self.values, values)
+        if self.rope is not None:
+            rank = (self.comm or _comm.get_comm()).rank if self.distributed else 0
+            off = self.rope.resolve(rank, k.shape[1])
+            k, q = _rope(k, self.num_heads, self.rope, offset=off), _rope(q, self.num_heads, self.rope, offset=off)
         return self._proj(self.composition, self._materialized(k, q, v, attn_mask, scale))
 
     def _proj(self, layer: nn.Linear, x: Tensor) -> Tensor:
@@ -286,4 +320,5 @@ class DistributedDotProductAttn(nn.Module):
     def extra_repr(self) -> str:
         return (f"heads={self.num_heads}, head_dim={self.dim}, value_dim={self.value_dim}, "
                 f"offset={self.offset}, distributed={self.distributed}, impl={self.impl}, backend={self.backend}, "
-                f"dtype={self.compute_dtype}, chunk_plan={self.chunk_plan}")
+                f"dtype={self.compute_dtype}, chunk_plan={self.chunk_plan}"
+                + (f", rope={self.rope!r}" if self.rope is not None else ""))

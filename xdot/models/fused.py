@@ -18,6 +18,9 @@ GPU step is only ~1.4 ms.  :class:`AttnBlockFn` runs
 
 with the same kernels, streams and numerics as the per-op graph (``XDOT_FUSED_MODULE=0``
 restores it), and hands back the eight parameter gradients and the input gradients in one go.
+With ``rope`` (an :class:`xdot.Rotary`) q is rotated in place in ``[q|v]`` before the gather is
+issued and k after its projection; the backward inverse-rotates ``dk`` and ``dq`` in place before
+the projections' gradients read them (``csrc/rope.hip``: two launches each way).
 """
 from __future__ import annotations
 
@@ -25,8 +28,9 @@ import torch
 
 from .. import _ext
 from ..ops.linear import linear_backward, native_wgrad, proj, weight_grad_pair
+from ..ops.rope import _table_dtype, rope_apply
 from ..utils.env import FLAGS
-from ..parallel.attention import SeqParallelAttention, gather_plan, prescale_wanted, start_gather
+from ..parallel.attention import SeqParallelAttention, _on_stream, gather_plan, prescale_wanted, start_gather
 
 _LOG2E = 1.4426950408889634  # as the kernels' scale * log2 e (csrc/flash_common.h, csrc/reduce.hip)
 
@@ -75,7 +79,7 @@ class AttnBlockFn(torch.autograd.Function):
     @staticmethod
     @_ext.pinned
     def forward(ctx, xk, xqv, mask, wk, bk, wq, bq, wv, bv, wc, bc, H, scale, comm, chunk_plan, sync=None,
-                grad_on=True):
+                grad_on=True, rope=None):
         wqv = _rows(wq, wv)
         bqv = _rows(bq, bv) if bq is not None else None
         n = comm.world_size
@@ -91,11 +95,20 @@ class AttnBlockFn(torch.autograd.Function):
             proj(xqv, wqv, bqv, out=qv.view(-1, qv.shape[-1]))
         else:
             qv = proj(xqv, wqv, bqv)
+        nq = wq.shape[0]
+        tab = None
+        if rope is not None:
+            # q rotated at this rank's global positions, in place and BEFORE the gather is issued
+            # (with the in-place gather this block is what the peers pull); v is untouched
+            tab = rope.table(R, nq // H, rope.resolve(comm.rank, R), qv.device, _table_dtype(qv))
+            rope_apply(qv[..., :nq], H, *tab, out=qv[..., :nq])
         pending = start_gather(qv, comm, chunks=chunk_plan, out=gbuf)  # in flight under the row-side GEMM
         # the row side's pre-scale (scale * log2 e) folded into the k projection: one rounding, no
         # separate pass (the attention backward's dk is w.r.t. the unscaled k either way)
         pre = xk.shape[-1] == wk.shape[1] and prescale_wanted(qv[..., :wk.shape[0]], qv, H)
         k = proj(xk, wk, bk, alpha=scale * _LOG2E if pre else 1.0)
+        if tab is not None:  # the pre-scale sits in the projection: a rotation commutes with a scalar
+            rope_apply(k, H, *tab, out=k)
         actx = _Ctx()
         actx.needs_input_grad = (any(ctx.needs_input_grad),) * 2  # a backward can run (score buffers)
         o = SeqParallelAttention.forward(actx, k, qv, mask, H, scale, comm, pending, pre, grad_on)  # k_prescaled
@@ -103,7 +116,8 @@ class AttnBlockFn(torch.autograd.Function):
         ctx.actx = actx
         ctx.sync = sync  # (GradSync, module key) or None
         ctx.params = (wk, bk, wq, bq, wv, bv, wc, bc)
-        ctx.nq = wq.shape[0]
+        ctx.nq = nq
+        ctx.rope_tab, ctx.H = tab, H
         ctx.has_b = (bk is not None, bq is not None, bc is not None)
         # the attention's tensors go through save_for_backward too (version checks, and a graph
         # retained for a second backward keeps them)
@@ -146,6 +160,20 @@ class AttnBlockFn(torch.autograd.Function):
             sync.deliver([(wc_, dwc), (bc_, dbc)], stream=side)
             dwc = dbc = None
         dk, dqv = SeqParallelAttention.backward(ctx.actx, do)[:2]
+        if ctx.rope_tab is not None:
+            # gradients w.r.t. the rotated k / q -> w.r.t. the projections' outputs: the inverse
+            # rotation, in place, before anything below reads them.  d[q|v] may be handed on with
+            # ``_xdot_ready_on`` (its weight gradient then runs on that stream without waiting for
+            # this one): it is rotated on that same stream, and this stream waits for it
+            rope_apply(dk, ctx.H, *ctx.rope_tab, inverse=True, out=dk)
+            dq, on = dqv[..., :ctx.nq], getattr(dqv, "_xdot_ready_on", None)
+            if on is None:
+                rope_apply(dq, ctx.H, *ctx.rope_tab, inverse=True, out=dq)
+            else:
+                here = torch.cuda.current_stream(dqv.device)
+                with _on_stream(on, here):
+                    rope_apply(dq, ctx.H, *ctx.rope_tab, inverse=True, out=dq)
+                here.wait_stream(on)
         # the row-side weight gradient also runs beside the input-gradient GEMMs that follow
         # d[q|v] may be ready on the backward's priority stream (``_xdot_ready_on``): its weight
         # gradient runs there, under the row-side kernel (linear_backward)
@@ -189,4 +217,4 @@ class AttnBlockFn(torch.autograd.Function):
         # the attention's tensors were only borrowed from ctx.saved_tensors (rebuilt from there by
         # every backward): do not keep them alive through the node after this backward
         ctx.actx._saved = None
-        return (dxk, dxqv, None, dwk, dbk, dwq, dbq, dwv, dbv, dwc, dbc, None, None, None, None, None, None)
+        return (dxk, dxqv, None, dwk, dbk, dwq, dbq, dwv, dbv, dwc, dbc, None, None, None, None, None, None, None)

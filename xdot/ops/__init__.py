@@ -6,3 +6,4 @@ from .linear import linear, weight_grad  # noqa: F401
 from .optim import FusedAdamW  # noqa: F401
 from .loss import mse_loss, MSELoss  # noqa: F401
 from .mask import StructuredMask  # noqa: F401
+from .rope import Rotary, rope  # noqa: F401

@@ -1,0 +1,210 @@
+"""Rotary position embedding (RoPE) of the projected ``k`` / ``q``.
+
+The rotation is a pass of its own between the projections and the attention
+(``csrc/rope.hip``): the flash kernels, :class:`xdot.parallel.attention.SeqParallelAttention`
+and the ring know nothing about positions.  Under sequence parallelism rank ``r`` holds rows
+``[rR, (r+1)R)`` and rotates them at their GLOBAL positions before the all-gather: the same
+``rank * R`` convention as ``StructuredMask(row_offset=None)``.
+
+Convention: half-split pairs.  In a head of width ``D`` element ``i`` pairs with ``i + D/2``
+(``i < D/2``), the angle at position ``p`` is ``θ(p, i) = p · base^(−2i/D)`` and
+
+    out[i]       = x[i]·cos θ − x[i + D/2]·sin θ
+    out[i + D/2] = x[i + D/2]·cos θ + x[i]·sin θ
+
+All batches and heads share the positions.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from .. import _ext
+
+__all__ = ["Rotary", "rope", "rope_apply", "rope_packed"]
+
+_HIP_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
+_MAX_POS = 2**31 - 1
+
+
+class Rotary:
+    """``Rotary(base=10000.0, offset=None)``: a description, like :class:`xdot.StructuredMask`.
+
+    ``offset`` is the global position of this rank's first row; ``None`` resolves to
+    ``rank * R`` at the call (0 with ``distributed=False``).  Pass it as ``rope=`` to
+    :class:`xdot.DistributedDotProductAttn` / :func:`xdot.seq_parallel_attention`, or to
+    :func:`xdot.rope`.  The ``(cos, sin)`` tables are cached on the object."""
+
+    __slots__ = ("base", "offset", "_tables", "__weakref__")
+
+    def __init__(self, base: float = 10000.0, offset: Optional[int] = None):
+        base = float(base)
+        if not base > 0.0:
+            raise ValueError(f"Rotary: base must be positive, got {base}")
+        if offset is not None:
+            offset = int(offset)
+            if offset < 0:
+                raise ValueError(f"Rotary: offset must be >= 0, got {offset}")
+        self.base = base
+        self.offset = offset
+        self._tables = {}
+
+    def __repr__(self):
+        return f"Rotary(base={self.base:g}, offset={self.offset})"
+
+    def resolve(self, rank: int, R: int) -> int:
+        """This rank's first global position: ``offset``, or ``rank * R`` where it is None."""
+        return int(rank) * int(R) if self.offset is None else self.offset
+
+    def inv_freq(self, D: int) -> list:
+        """``base ** (-2 i / D)`` for ``i < D/2`` as Python floats: the doubles both the CPU and
+        the GPU table multiply the positions with."""
+        return [self.base ** (-2.0 * i / D) for i in range(D // 2)]
+
+    def table(self, R: int, D: int, offset: int, device, dtype: torch.dtype = torch.float32) -> Tuple[Tensor, Tensor]:
+        """``(cos, sin)``, each ``(R, D/2)``, of the angles ``(offset + row) * inv_freq[i]``:
+        product and sin / cos in fp64, rounded once to ``dtype`` (fp32 for the kernels; fp64
+        tensors rotate with the unrounded table).  Cached on the object, keyed on
+        ``(device, R, D, offset)`` and the dtype.  GPU: ``rope_table`` (``csrc/rope.hip``);
+        CPU, or ``backend='torch'``: torch fp64."""
+        R, D, offset = int(R), int(D), int(offset)
+        if D < 2 or D % 2:
+            raise ValueError(f"Rotary: the head dim must be even, got {D}")
+        if offset < 0 or offset + R > _MAX_POS:
+            raise ValueError(f"Rotary: positions must stay below 2^31 (offset {offset} + {R} rows)")
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        key = (device, R, D, offset, dtype)
+        tab = self._tables.get(key)
+        if tab is None:
+            if len(self._tables) >= 8:
+                self._tables.pop(next(iter(self._tables)))
+            inv = torch.tensor(self.inv_freq(D), dtype=torch.float64).to(device)
+            if dtype == torch.float32 and _ext.use_hip(inv):
+                tab = tuple(_ext.ops().rope_table(R, D, offset, inv))
+            else:
+                ang = torch.arange(offset, offset + R, dtype=torch.float64, device=device).view(R, 1) * inv.view(1, -1)
+                tab = (torch.cos(ang).to(dtype), torch.sin(ang).to(dtype))
+            self._tables[key] = tab
+        return tab
+
+
+def _table_dtype(x: Tensor) -> torch.dtype:
+    return torch.float64 if x.dtype == torch.float64 else torch.float32
+
+
+def rope_apply(x: Tensor, num_heads: int, cos: Tensor, sin: Tensor, inverse: bool = False, alpha: float = 1.0,
+               out: Optional[Tensor] = None) -> Tensor:
+    """``out = alpha * rotate(x)`` with a table of :meth:`Rotary.table`; no autograd.  ``x`` is
+    ``(B, R, H*D)``; ``out`` may be ``x`` (in place), another tensor, or None (a new contiguous
+    one).  GPU bf16 / fp16 / fp32 tensors with unit last stride run ``csrc/rope.hip`` on the view
+    as it is (any row / batch strides); everything else is the torch reference math."""
+    if x.dim() != 3:
+        raise ValueError(f"rope expects (B, R, H*D), got {tuple(x.shape)}")
+    B, R, C = x.shape
+    H = int(num_heads)
+    if H < 1 or C % H or (C // H) % 2:
+        raise ValueError(f"rope: {C} features over {H} heads is not an even head dim")
+    h = C // H // 2
+    if tuple(cos.shape) != (R, h) or tuple(sin.shape) != (R, h):
+        raise ValueError(f"rope: table {tuple(cos.shape)} does not fit (R, D/2) = ({R}, {h})")
+    if _ext.use_hip(x) and x.dtype in _HIP_DTYPES:
+        if C > 1 and x.stride(-1) != 1:
+            if out is x:
+                raise ValueError("rope: in place needs a unit last stride")
+            x = x.contiguous()
+        if out is None:
+            out = torch.empty((B, R, C), dtype=x.dtype, device=x.device)
+        _ext.ops().rope_apply(x, cos, sin, H, bool(inverse), float(alpha), out)
+        return out
+    cdt = _table_dtype(x)
+    xv = x.reshape(B, R, H, 2 * h).to(cdt)
+    x1, x2 = xv[..., :h], xv[..., h:]
+    c = cos.to(cdt).view(1, R, 1, h)
+    s = sin.to(cdt).view(1, R, 1, h)
+    if inverse:
+        s = -s
+    o = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
+    if alpha != 1.0:
+        o = o * alpha
+    o = o.reshape(B, R, C).to(x.dtype)
+    if out is None:
+        return o
+    out.copy_(o)
+    return out
+
+
+class _RopeFn(torch.autograd.Function):
+    """The first ``ncols`` features of ``x`` rotated (``ncols`` = all of them but for a packed
+    ``[q | v]``, whose rest is copied).  ``mode``: 0 a new tensor, 1 in place on ``x``, 2 into
+    ``out``.  Backward: the inverse rotation of the incoming gradient times ``bwd_alpha``; only
+    the table is kept."""
+
+    @staticmethod
+    @_ext.pinned
+    def forward(ctx, x, out, ncols, H, cos, sin, inverse, alpha, bwd_alpha, mode):
+        ctx.tab, ctx.args = (cos, sin), (ncols, H, inverse, bwd_alpha)
+        if mode == 0:
+            if ncols == x.shape[-1]:
+                return rope_apply(x, H, cos, sin, inverse, alpha)
+            new = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+            rope_apply(x[..., :ncols], H, cos, sin, inverse, alpha, out=new[..., :ncols])
+            new[..., ncols:].copy_(x[..., ncols:])
+            return new
+        dst = x if mode == 1 else out
+        rope_apply(x[..., :ncols], H, cos, sin, inverse, alpha, out=dst[..., :ncols])
+        ctx.mark_dirty(dst)
+        return dst
+
+    @staticmethod
+    @_ext.pinned
+    def backward(ctx, g):
+        ncols, H, inverse, bwd_alpha = ctx.args
+        cos, sin = ctx.tab
+        if ncols == g.shape[-1]:
+            gx = rope_apply(g, H, cos, sin, not inverse, bwd_alpha)
+        else:
+            gx = torch.empty(g.shape, dtype=g.dtype, device=g.device)
+            rope_apply(g[..., :ncols], H, cos, sin, not inverse, bwd_alpha, out=gx[..., :ncols])
+            gx[..., ncols:].copy_(g[..., ncols:])
+        return gx, None, None, None, None, None, None, None, None, None
+
+
+def rope(x: Tensor, num_heads: int, rotary: Rotary, *, offset: Optional[int] = None, inverse: bool = False,
+         alpha: float = 1.0, out: Optional[Tensor] = None) -> Tensor:
+    """``alpha * rotate(x)`` for ``x`` ``(B, R, H*D)`` whose row ``r`` sits at position
+    ``offset + r`` (``offset=None``: ``rotary.offset``, else 0).  Autograd-aware: the backward is
+    the inverse rotation of the incoming gradient times ``alpha``.  ``x`` may be a strided view
+    with unit last stride (the ``q`` half of a packed ``[q | v]`` buffer, a rank slot of a gather
+    buffer); ``out=x`` rotates in place."""
+    if not isinstance(rotary, Rotary):
+        raise TypeError(f"rope: rotary must be an xdot.Rotary, got {type(rotary).__name__}")
+    if x.dim() != 3:
+        raise ValueError(f"rope expects (B, R, H*D), got {tuple(x.shape)}")
+    H = int(num_heads)
+    if H < 1 or x.shape[-1] % H or (x.shape[-1] // H) % 2:
+        raise ValueError(f"rope: {x.shape[-1]} features over {H} heads is not an even head dim")
+    if offset is None:
+        offset = rotary.offset if rotary.offset is not None else 0
+    cos, sin = rotary.table(x.shape[1], x.shape[-1] // H, offset, x.device, _table_dtype(x))
+    if out is not None and (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device):
+        raise ValueError("rope: out must match x in shape, dtype and device")
+    mode = 0 if out is None else (1 if out is x else 2)
+    return _RopeFn.apply(x, out if mode == 2 else None, x.shape[-1], H, cos, sin, bool(inverse), float(alpha),
+                         float(alpha), mode)
+
+
+def rope_packed(qv: Tensor, ncols: int, num_heads: int, rotary: Rotary, offset: int, alpha: float = 1.0,
+                bwd_alpha: Optional[float] = None) -> Tensor:
+    """A copy of ``qv`` with its first ``ncols`` features rotated (the ``q`` half of a packed
+    ``[q | v]``; all of a ``k``), as one autograd node: the per-op graph's form (a projection's
+    output may be a view, which autograd does not let a later node overwrite; the one-node module
+    of :mod:`xdot.models.fused` rotates in place).  ``bwd_alpha``: the factor of the backward
+    (default ``alpha``; 1 where ``alpha`` is the row side's pre-scale, whose gradient
+    :class:`xdot.parallel.attention.SeqParallelAttention` already returns w.r.t. the unscaled rows)."""
+    cos, sin = rotary.table(qv.shape[1], ncols // int(num_heads), offset, qv.device, _table_dtype(qv))
+    return _RopeFn.apply(qv, None, int(ncols), int(num_heads), cos, sin, False, float(alpha),
+                         float(alpha if bwd_alpha is None else bwd_alpha), 0)

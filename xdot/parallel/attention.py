@@ -755,11 +755,12 @@ def start_gather(qv: Tensor, comm: Optional[_comm.Communicator] = None,
 
 def seq_parallel_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
                                   comm: Optional[_comm.Communicator] = None,
-                                  pending: Optional["_PendingGather"] = None) -> Tensor:
+                                  pending: Optional["_PendingGather"] = None, k_prescaled: bool = False) -> Tensor:
     """Fused sequence-parallel attention with a packed gathered side ``qv = [q | v]`` (B, R, 2C).
 
     ``pending``: the handle of :func:`start_gather` on this ``qv`` (the gather is issued here
-    otherwise)."""
+    otherwise).  ``k_prescaled``: ``k`` already holds ``rows * scale * log2 e`` (only where
+    :func:`prescale_wanted`; the gradient returned for it is w.r.t. the unscaled rows)."""
     comm = comm or _comm.get_comm()
     if k.dim() != 3 or qv.dim() != 3 or qv.shape[-1] <= k.shape[-1]:
         raise ValueError("seq_parallel_attention_packed expects k (B, R, C) and qv (B, R, C + Cv)")
@@ -771,19 +772,27 @@ def seq_parallel_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor],
             raise ValueError(f"mask must be (B, R, T)=({k.shape[0]}, {k.shape[1]}, {T}), got {tuple(mask.shape)}")
         if isinstance(mask, torch.Tensor):
             mask = mask.to(torch.bool)
-    return SeqParallelAttention.apply(k, qv, mask, num_heads, float(scale), comm, pending, False,
+    return SeqParallelAttention.apply(k, qv, mask, num_heads, float(scale), comm, pending, bool(k_prescaled),
                                       torch.is_grad_enabled())
 
 
 def seq_parallel_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tensor], num_heads: int,
-                           scale: float, comm: Optional[_comm.Communicator] = None) -> Tensor:
+                           scale: float, comm: Optional[_comm.Communicator] = None, rope=None) -> Tensor:
     """Fused sequence-parallel attention on projected, head-interleaved (B, R, H*d) tensors.
 
     ``k``: row side (local rows), ``q``/``v``: gathered side (local shards), ``mask``: bool
     (B, R, T) with True = masked, a :class:`xdot.StructuredMask` (causal / window / lengths; its
     packed form is generated on the GPU, the torch path builds its dense tensor), or None.
+    ``rope``: an :class:`xdot.Rotary`; ``k`` and ``q`` are rotated at this rank's global positions
+    (``rank * R`` unless the object carries an offset) before the attention, ``v`` is not.
     Returns (B, R, H*dv) in ``k``'s dtype.
     """
     if k.dim() != 3 or q.dim() != 3 or v.dim() != 3:
         raise ValueError("seq_parallel_attention expects (B, R, H*d) tensors")
+    if rope is not None:
+        from ..ops.rope import rope as _rope
+
+        off = rope.resolve((comm or _comm.get_comm()).rank, k.shape[1])
+        k = _rope(k, num_heads, rope, offset=off)
+        q = _rope(q, num_heads, rope, offset=off)
     return seq_parallel_attention_packed(k, torch.cat([q, v], dim=-1), mask, num_heads, scale, comm)
