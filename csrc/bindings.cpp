@@ -426,11 +426,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> mask_pack(const at::Tensor& mask)
   return {bits, flags, bitsT};
 }
 
-// mask_pack's outputs for the mask `causal / window / lengths` describe (xdot.StructuredMask), the
-// packed columns being the runs of `segs` (nseg, 3) int32 (packed_start, length, global_start)
+// mask_pack's outputs for the mask `causal / window / lengths / doc_starts` describe
+// (xdot.StructuredMask), the packed columns being the runs of `segs` (nseg, 3) int32 (packed_start,
+// length, global_start); doc_starts: (n,) shared or (B, n) sorted int32 document starts
 std::tuple<at::Tensor, at::Tensor, at::Tensor> mask_gen(int64_t B, int64_t R, int64_t T, bool causal, int64_t window,
                                                         int64_t row_offset, const c10::optional<at::Tensor>& lengths,
-                                                        const at::Tensor& segs) {
+                                                        const at::Tensor& segs,
+                                                        const c10::optional<at::Tensor>& doc_starts) {
   Range rr_("xdot.mask_gen");
   TORCH_CHECK(B >= 0 && R >= 0 && T >= 0, "xdot.mask_gen: negative shape");
   TORCH_CHECK(segs.is_cuda() && segs.scalar_type() == at::kInt && segs.dim() == 2 && segs.size(1) == 3 &&
@@ -440,6 +442,17 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> mask_gen(int64_t B, int64_t R, in
     TORCH_CHECK(lengths->is_cuda() && lengths->device() == segs.device() && lengths->scalar_type() == at::kInt &&
                     lengths->dim() == 1 && lengths->size(0) == B && lengths->is_contiguous(),
                 "xdot.mask_gen: lengths must be a contiguous (B,) int32 tensor on the segment table's device");
+  const int* starts = nullptr;
+  int64_t nstarts = 0, starts_stride = 0;
+  if (doc_starts.has_value()) {
+    const at::Tensor& d = *doc_starts;
+    TORCH_CHECK(d.is_cuda() && d.device() == segs.device() && d.scalar_type() == at::kInt && d.is_contiguous() &&
+                    (d.dim() == 1 || (d.dim() == 2 && d.size(0) == B)) && d.size(-1) < (1LL << 31),
+                "xdot.mask_gen: doc_starts must be a contiguous (n,) or (B, n) int32 tensor on the segment table's device");
+    nstarts = d.size(-1);
+    starts_stride = d.dim() == 2 ? nstarts : 0;
+    if (d.numel() > 0) starts = d.data_ptr<int>();
+  }
   TORCH_CHECK(window >= 0 && window < (1LL << 40) && row_offset >= 0 && row_offset < (1LL << 40),
               "xdot.mask_gen: window / row_offset out of range");
   const int64_t NKT = (T + 63) / 64, NRT = (R + 63) / 64, Tpad = (T + 127) / 128 * 128;
@@ -451,7 +464,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> mask_gen(int64_t B, int64_t R, in
   xdot_mask_gen_launch(reinterpret_cast<uint64_t*>(bits.data_ptr()), reinterpret_cast<uint64_t*>(bitsT.data_ptr()),
                        flags.data_ptr<uint8_t>(), lengths.has_value() ? lengths->data_ptr<int>() : nullptr,
                        segs.data_ptr<int>(), (int)segs.size(0), causal ? 1 : 0, window, row_offset, (int)B, (int)R, (int)T,
-                       cur_stream(segs));
+                       starts, starts == nullptr ? 0 : (int)nstarts, starts_stride, cur_stream(segs));
   check_launch(hipGetLastError(), "mask_gen");
   return {bits, flags, bitsT};
 }
@@ -879,7 +892,7 @@ TORCH_LIBRARY(xdot, m) {
   m.def("softmax_fwd(Tensor x, Tensor? mask, float scale, int mdiv, int mmul, int mmod) -> Tensor");
   m.def("softmax_bwd(Tensor y, Tensor dy, float scale) -> Tensor");
   m.def("mask_pack(Tensor mask) -> (Tensor, Tensor, Tensor)");
-  m.def("mask_gen(int B, int R, int T, bool causal, int window, int row_offset, Tensor? lengths, Tensor segs) -> (Tensor, Tensor, Tensor)");
+  m.def("mask_gen(int B, int R, int T, bool causal, int window, int row_offset, Tensor? lengths, Tensor segs, Tensor? doc_starts=None) -> (Tensor, Tensor, Tensor)");
   m.def("flash_fwd(Tensor rows, Tensor kc, Tensor vc, Tensor? bits, Tensor? flags, int H, float scale, int nsplit=0, bool prescaled=False, int fp32_mode=0, Tensor(a!)? sbuf=None) -> (Tensor, Tensor)");
   m.def("flash_bwd_cols(Tensor dout, Tensor rows, Tensor kc, Tensor vc, Tensor out, Tensor lse, Tensor? bits, "
         "Tensor? flags, int H, float scale, Tensor? delta=None, bool fp32_out=True, bool prescaled=False, "

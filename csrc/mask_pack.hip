@@ -155,11 +155,53 @@ __global__ __launch_bounds__(256) void mask_pack_kernel(const uint8_t* __restric
 // of consecutive global columns (global_start < 0: a run that is masked whatever the row), so
 // within a run the interval is again an interval of packed columns: every word starts as "all
 // of its columns below T masked" and each overlapping run clears one shifted range of ones.
+//
+// Documents (DOCS; starts: n sorted int32 global positions per batch, row stride `dstride`, 0 for
+// one shared table): the row's own document is the interval [s[k-1], s[k] - 1] with k the number
+// of starts <= gr (s[-1] = 0, s[n] = infinity), cut into [lo, hi].  Every 128-column block of the
+// same 64 rows repeats the search, and a binary search is a chain of log2 n dependent loads, so
+// the wave searches together: k0, the count for its first row, by a 64-ary search (each lane
+// loads one sample, a ballot counts them: one load per factor 64 of n), then ONE load of the 64
+// starts that follow.  Unless all 64 are <= the wave's last row, they are every start that
+// separates two of its rows, and each lane counts those <= its own row in registers.  Otherwise
+// (64 or more documents begin inside the tile: one-row or empty documents) the last row's count k1
+// is searched the same way and a lane bisects [k0, k1] in memory.  Whatever the table holds,
+// every index read is in [0, n) and every search shrinks its range, so an unsorted (unvalidated
+// device) table gives an unspecified mask, not a fault.  Without DOCS the code is what it was.
+
+constexpr int64_t kNoBound = (int64_t)1 << 60;  // (the run arithmetic below stays in range)
+
+// first i in [a, e) with s[i] > x, else e: one lane's bisection
+__device__ __forceinline__ int doc_upper(const int* __restrict__ s, int a, int e, int64_t x) {
+  while (a < e) {
+    const int m = a + ((e - a) >> 1);
+    if ((int64_t)s[m] <= x) a = m + 1; else e = m;
+  }
+  return a;
+}
+
+// the same for wave-uniform a, e, x, by all 64 lanes of the wave together
+__device__ __forceinline__ int doc_upper_wave(const int* __restrict__ s, int a, int e, int64_t x, int lane) {
+  while (e - a > 64) {
+    // 64 chunks of `step`; lane j samples the last element of chunk j: chunks wholly <= x are passed
+    const int step = (e - a + 63) >> 6;
+    const int64_t p = (int64_t)a + (int64_t)(lane + 1) * step - 1;
+    const int c = __popcll(__ballot(p < e && (int64_t)s[p < e ? p : a] <= x));
+    const int64_t a2 = (int64_t)a + (int64_t)c * step;
+    e = (int)min(a2 + step - 1, (int64_t)e);  // that chunk's sample is > x (or past the end)
+    a = (int)min(a2, (int64_t)e);
+  }
+  const int i = a + lane;
+  return a + __popcll(__ballot(i < e && (int64_t)s[i < e ? i : 0] <= x));  // (n > 0: s[0] exists)
+}
+
+template <bool DOCS>
 __global__ __launch_bounds__(256) void mask_gen_kernel(uint64_t* __restrict__ bits, uint64_t* __restrict__ bt,
                                                         uint8_t* __restrict__ flags, const int* __restrict__ lengths,
                                                         const int* __restrict__ segs, int nseg, int causal,
                                                         int64_t window, int64_t row_off, int B, int R, int T, int NKT,
-                                                        int NKT4, int NRT, int Tpad, int KT_ALL) {
+                                                        int NKT4, int NRT, int Tpad, int KT_ALL,
+                                                        const int* __restrict__ starts, int n, int64_t dstride) {
   const int lane = threadIdx.x & 63;
   const int KT2 = (KT_ALL + 1) / 2;
   const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -170,23 +212,58 @@ __global__ __launch_bounds__(256) void mask_gen_kernel(uint64_t* __restrict__ bi
   const int r = rt * 64 + lane;
   uint64_t wv[2] = {0, 0};
   const int64_t c0 = (int64_t)kt0 * 64;
+  // the lane's own document [dlo, dhi], and the hull of the wave's documents [wlo, whi]: global
+  // columns outside the hull are masked in every row of the wave
+  int64_t dlo = 0, dhi = kNoBound, wlo = 0, whi = kNoBound;
+  if (DOCS && (int64_t)__builtin_amdgcn_readfirstlane(kt0) * 64 < T) {  // all 64 lanes enter (ballots, shuffles)
+    const int rtu = __builtin_amdgcn_readfirstlane(rt), bu = __builtin_amdgcn_readfirstlane(b);
+    const int* __restrict__ ds = starts + (int64_t)bu * dstride;
+    const int64_t g0 = row_off + (int64_t)rtu * 64, g1 = row_off + min(rtu * 64 + 63, R - 1);
+    const int64_t gr = row_off + r;  // rows past R: bounds nobody uses
+    const int k0 = doc_upper_wave(ds, 0, n, g0, lane);
+    if (k0 > 0) wlo = ds[k0 - 1];
+    const int i = k0 + lane;
+    const int v = ds[i < n ? i : 0];  // lane j: start k0 + j
+    const int cnt = __popcll(__ballot(i < n && (int64_t)v <= g1));
+    if (cnt < 64) {  // the starts in (g0, g1] are lanes 0 .. cnt - 1; k1 = k0 + cnt
+      if (k0 + cnt < n) whi = (int64_t)__builtin_amdgcn_readlane(v, cnt) - 1;
+      int k = 0;  // of them, those <= gr
+      for (int j = 0; j < cnt; ++j) k += (int64_t)__builtin_amdgcn_readlane(v, j) <= gr;
+      k = min(k, cnt);
+      const int below = __shfl(v, max(k - 1, 0), 64), above = __shfl(v, min(k, 63), 64);
+      dlo = k > 0 ? (int64_t)below : wlo;
+      dhi = k < cnt ? (int64_t)above - 1 : whi;
+    } else {
+      const int k1 = doc_upper_wave(ds, k0 + 64, n, g1, lane);
+      if (k1 < n) whi = (int64_t)ds[k1] - 1;
+      const int k = doc_upper(ds, k0, k1, gr);
+      dlo = k > 0 ? (int64_t)ds[k - 1] : 0;
+      dhi = k < n ? (int64_t)ds[k] - 1 : kNoBound;
+    }
+  }
   if (r < R && c0 < T) {
     const int64_t gr = row_off + r;
-    int64_t lo = 0, hi = (int64_t)1 << 60;  // no bound (the run arithmetic below stays in range)
+    int64_t lo = 0, hi = kNoBound;
     if (causal) hi = gr;
     if (window > 0) {
       lo = gr - (window - 1);
       if (!causal) hi = gr + (window - 1);
     }
     if (lengths != nullptr) hi = min(hi, (int64_t)lengths[b] - 1);
+    if (DOCS) {
+      lo = max(lo, dlo);
+      hi = min(hi, dhi);
+    }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int64_t n = min((int64_t)64, T - (c0 + 64 * h));
-      wv[h] = n >= 64 ? ~0ull : (n > 0 ? (1ull << n) - 1 : 0ull);
+      const int64_t nc = min((int64_t)64, T - (c0 + 64 * h));
+      wv[h] = nc >= 64 ? ~0ull : (nc > 0 ? (1ull << nc) - 1 : 0ull);
     }
     for (int s = 0; s < nseg; ++s) {  // wave-uniform
       const int64_t ps = segs[3 * s], len = segs[3 * s + 1], gs = segs[3 * s + 2];
       if (gs < 0 || ps + len <= c0 || ps >= c0 + 128) continue;
+      // the run's part of this block, in global columns, against the hull of the wave's documents
+      if (DOCS && (gs + (min(ps + len, c0 + 128) - 1 - ps) < wlo || gs + (max(ps, c0) - ps) > whi)) continue;
       // unmasked packed columns of this run: global [lo, hi] moved by (ps - gs), cut to the run
       const int64_t a = max(ps, lo - gs + ps), e = min(ps + len - 1, hi - gs + ps);
 #pragma unroll
@@ -222,16 +299,19 @@ extern "C" int xdot_mask_pack_launch(const uint8_t* mask, uint64_t* bits, uint64
 }
 
 // lengths: (B,) int32 or null; segs: (nseg, 3) int32 (packed_start, length, global_start) covering
-// [0, T); window <= 0: none
+// [0, T); window <= 0: none; starts: nstarts sorted int32 document starts per batch (batch b's at
+// starts + b * starts_stride, stride 0: one shared table) or null
 extern "C" int xdot_mask_gen_launch(uint64_t* bits, uint64_t* bt, uint8_t* flags, const int* lengths, const int* segs,
                                     int nseg, int causal, int64_t window, int64_t row_off, int B, int R, int T,
-                                    hipStream_t st) {
+                                    const int* starts, int nstarts, int64_t starts_stride, hipStream_t st) {
   using namespace xdot;
   const int NKT = (T + 63) / 64, NKT4 = (NKT + 3) & ~3, NRT = (R + 63) / 64, Tpad = (T + 127) / 128 * 128;
   const int KT_ALL = max(NKT4, Tpad / 64);
   const int64_t nblk = (int64_t)B * NRT * ((KT_ALL + 1) / 2);
   if (nblk == 0) return 0;
-  hipLaunchKernelGGL(mask_gen_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, st, bits, bt, flags, lengths, segs,
-                     nseg, causal, window, row_off, B, R, T, NKT, NKT4, NRT, Tpad, KT_ALL);
+  const bool docs = starts != nullptr && nstarts > 0;
+  hipLaunchKernelGGL(docs ? mask_gen_kernel<true> : mask_gen_kernel<false>, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0,
+                     st, bits, bt, flags, lengths, segs, nseg, causal, window, row_off, B, R, T, NKT, NKT4, NRT, Tpad,
+                     KT_ALL, starts, nstarts, starts_stride);
   return 0;
 }

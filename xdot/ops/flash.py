@@ -52,20 +52,22 @@ def generate_mask(spec: StructuredMask, B: int, R: int, T: int, row_offset: Opti
     ``segments``: the packed columns as runs ``(packed_start, length, global_start)`` of
     consecutive global columns (``global_start = -1``: a run that is always masked); None: the
     identity, packed column = global column.  ``row_offset`` is used where ``spec`` has none;
-    ``device``: default the device of ``spec.lengths`` when on a GPU, else the current one."""
+    ``device``: default the device of ``spec.lengths`` (else of ``spec.doc_starts``) when on a
+    GPU, else the current one."""
     spec.check(B)
     ro = spec.row_offset if spec.row_offset is not None else row_offset
     if ro is None:
         raise ValueError("generate_mask: row_offset is not set")
     if device is None:
-        ln = spec.lengths
-        device = ln.device if ln is not None and ln.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        on_gpu = [t for t in (spec.lengths, spec.doc_starts) if t is not None and t.is_cuda]
+        device = on_gpu[0].device if on_gpu else torch.device("cuda", torch.cuda.current_device())
     segs = [(0, T, 0)] if segments is None else [tuple(int(x) for x in sg) for sg in segments]
     if sorted((p, p + n) for p, n, _g in segs if n > 0) != _tiling(segs, T):
         raise ValueError(f"generate_mask: the segments must tile the {T} packed columns exactly, got {segs}")
     table = torch.tensor(segs or [(0, 0, 0)], dtype=torch.int32).reshape(-1, 3).to(device, non_blocking=True)
+    ds = spec.device_doc_starts(device)
     bits, flags, bits_t = _ext.ops().mask_gen(int(B), int(R), int(T), spec.causal, int(spec.window or 0), int(ro),
-                                              spec.device_lengths(device), table)
+                                              spec.device_lengths(device), table, *(() if ds is None else (ds,)))
     return PackedMask(bits, flags, bits_t, (B, R, T))
 
 

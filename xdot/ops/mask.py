@@ -17,7 +17,7 @@ Segment = Tuple[int, int, int]  # (packed_start, length, global_start); global_s
 
 
 class StructuredMask:
-    """``StructuredMask(causal=False, window=None, lengths=None, row_offset=None)``
+    """``StructuredMask(causal=False, window=None, lengths=None, row_offset=None, doc_starts=None)``
 
     True = masked, as everywhere in this package.  With ``gr = row_offset + r`` the global index
     of local row ``r`` and ``gc`` the global column in ``[0, T)``, an element is masked iff
@@ -25,7 +25,21 @@ class StructuredMask:
     * ``causal`` and ``gc > gr``, or
     * ``window = w`` (int >= 1) and ``gc < gr - (w - 1)`` -- without ``causal`` also
       ``gc > gr + (w - 1)`` --, or
-    * ``lengths`` is given and ``gc >= lengths[b]``.
+    * ``lengths`` is given and ``gc >= lengths[b]``, or
+    * ``doc_starts`` is given and ``doc(gc) != doc(gr)``, with ``doc(x)`` the number of entries
+      ``<= x``: several documents packed back to back into one sequence do not attend across
+      their boundaries.
+
+    ``doc_starts``: the global positions at which a new document begins, in non-decreasing order:
+    ``(n,)`` shared by the batch or ``(B, n)``, an integer tensor or a (nested) sequence of ints
+    (:meth:`from_doc_lengths` takes the documents' lengths instead).  Position 0 begins a
+    document whether listed or not; a repeated entry is an empty document (so rows of different
+    document counts are padded by repeating the last start, or with ``T``); entries ``>= T`` have
+    no effect; ``n = 0`` is one document.  A tensor is kept by reference like ``lengths``.  The
+    order and sign of a host sequence or CPU tensor are checked at construction; the CONTENT OF A
+    DEVICE TENSOR IS NOT VALIDATED (that would need a host synchronisation): the kernel stays in
+    bounds and terminates whatever it holds, but the mask of an unsorted table is unspecified.
+    Entries are read as int32, clamped to ``[0, 2^31 - 1]``.
 
     ``lengths``: a ``(B,)`` integer tensor (kept by reference: a device tensor is read by the
     kernel with no host synchronisation, and an in-place edit re-generates the cached packed
@@ -36,10 +50,11 @@ class StructuredMask:
     (``attn_mask`` of :class:`xdot.DistributedDotProductAttn`, ``mask`` of
     :func:`xdot.seq_parallel_attention` / the ring ops)."""
 
-    __slots__ = ("causal", "window", "lengths", "row_offset", "_T", "_bound", "__weakref__")
+    __slots__ = ("causal", "window", "lengths", "row_offset", "doc_starts", "_T", "_bound", "__weakref__")
 
     def __init__(self, causal: bool = False, window: Optional[int] = None,
-                 lengths: Union[None, torch.Tensor, Sequence[int]] = None, row_offset: Optional[int] = None):
+                 lengths: Union[None, torch.Tensor, Sequence[int]] = None, row_offset: Optional[int] = None,
+                 doc_starts: Union[None, torch.Tensor, Sequence[int], Sequence[Sequence[int]]] = None):
         if window is not None:
             if isinstance(window, bool) or not isinstance(window, int):
                 raise TypeError(f"StructuredMask: window must be an int or None, got {type(window).__name__}")
@@ -54,11 +69,14 @@ class StructuredMask:
             row_offset = int(row_offset)
             if row_offset < 0:
                 raise ValueError(f"StructuredMask: row_offset must be >= 0, got {row_offset}")
+        if doc_starts is not None:
+            doc_starts = _check_doc_starts(doc_starts)
         s = object.__setattr__
         s(self, "causal", bool(causal))
         s(self, "window", window)
         s(self, "lengths", lengths)
         s(self, "row_offset", row_offset)
+        s(self, "doc_starts", doc_starts)
         s(self, "_T", None)      # global column count, set on the copies bind() hands out
         s(self, "_bound", {})
 
@@ -67,17 +85,34 @@ class StructuredMask:
 
     def __repr__(self):
         ln = None if self.lengths is None else f"<{self.lengths.numel()} lengths on {self.lengths.device}>"
+        ds = "" if self.doc_starts is None else (f", doc_starts=<{tuple(self.doc_starts.shape)} starts on "
+                                                 f"{self.doc_starts.device}>")
         return (f"StructuredMask(causal={self.causal}, window={self.window}, lengths={ln}, "
-                f"row_offset={self.row_offset})")
+                f"row_offset={self.row_offset}{ds})")
+
+    @classmethod
+    def from_doc_lengths(cls, doc_lengths, **kw) -> "StructuredMask":
+        """The mask of documents of the given lengths packed back to back from position 0:
+        ``doc_lengths`` is ``(n,)`` or ``(B, n)`` (tensor or sequence), ``doc_starts`` its exclusive
+        cumulative sum along the last axis, computed with torch ops on the device the lengths
+        live on (no host synchronisation).  Other arguments pass through."""
+        if "doc_starts" in kw:
+            raise TypeError("StructuredMask.from_doc_lengths: doc_starts is computed from doc_lengths")
+        dl = _check_doc_starts(doc_lengths, what="doc_lengths", order=False)
+        return cls(doc_starts=torch.cumsum(dl, dim=-1) - dl, **kw)
 
     @property
-    def _version(self) -> int:
-        """What :class:`xdot.ops.flash.MaskCache` compares besides the object's identity."""
-        return 0 if self.lengths is None else self.lengths._version
+    def _version(self):
+        """What :class:`xdot.ops.flash.MaskCache` compares (``==``) besides the object's identity:
+        it changes with an in-place write to ``lengths`` or to ``doc_starts``."""
+        v = 0 if self.lengths is None else self.lengths._version
+        return v if self.doc_starts is None else (v, self.doc_starts._version)
 
     def check(self, B: int) -> None:
         if self.lengths is not None and self.lengths.numel() != B:
             raise ValueError(f"StructuredMask: lengths has {self.lengths.numel()} entries, the batch is {B}")
+        if self.doc_starts is not None and self.doc_starts.dim() == 2 and self.doc_starts.size(0) != B:
+            raise ValueError(f"StructuredMask: doc_starts has {self.doc_starts.size(0)} rows, the batch is {B}")
 
     def bind(self, row_offset: int, T: int) -> "StructuredMask":
         """The description with its row offset resolved (``row_offset`` is used only where the
@@ -89,7 +124,7 @@ class StructuredMask:
         if b is None:
             if len(self._bound) >= 8:
                 self._bound.pop(next(iter(self._bound)))
-            b = StructuredMask(self.causal, self.window, self.lengths, ro)
+            b = StructuredMask(self.causal, self.window, self.lengths, ro, self.doc_starts)
             object.__setattr__(b, "_T", int(T))
             self._bound[key] = b
         return b
@@ -101,6 +136,15 @@ class StructuredMask:
             return None
         ln = self.lengths.to(device=device, non_blocking=True)
         return ln.clamp(min=0, max=2**31 - 1).to(torch.int32).contiguous()
+
+    def device_doc_starts(self, device) -> Optional[torch.Tensor]:
+        """``doc_starts`` as the kernel reads them: contiguous int32 ``(n,)`` or ``(B, n)`` on
+        ``device``, clamped to ``[0, 2^31 - 1]`` (no host sync for a device tensor); None when
+        there are none (``n = 0`` included)."""
+        if self.doc_starts is None or self.doc_starts.numel() == 0:
+            return None
+        ds = self.doc_starts.to(device=device, non_blocking=True)
+        return ds.clamp(min=0, max=2**31 - 1).to(torch.int32).contiguous()
 
     def dense(self, B: int, R: int, T: int, row_offset: Optional[int] = None, device=None) -> torch.Tensor:
         """The equivalent ``(B, R, T)`` boolean tensor, built with plain torch ops (it allocates
@@ -121,7 +165,36 @@ class StructuredMask:
         m = m.unsqueeze(0).expand(B, R, T)
         if self.lengths is not None:
             m = m | (gc.view(1, 1, T) >= self.lengths.to(device=device, dtype=torch.int64).view(B, 1, 1))
+        if self.doc_starts is not None and self.doc_starts.numel() > 0:
+            ds = self.doc_starts.to(device=device, dtype=torch.int64).contiguous()
+            lead = ds.shape[:-1]  # () shared, (B,) per batch
+            doc_r = torch.searchsorted(ds, gr.view(R).expand(*lead, R).contiguous(), right=True)
+            doc_c = torch.searchsorted(ds, gc.view(T).expand(*lead, T).contiguous(), right=True)
+            m = m | (doc_r.unsqueeze(-1) != doc_c.unsqueeze(-2))
         return m.contiguous()
+
+
+def _check_doc_starts(x, what: str = "doc_starts", order: bool = True) -> torch.Tensor:
+    """``doc_starts`` (or the lengths they come from) as an integer tensor of rank 1 or 2; what a
+    host sequence or CPU tensor holds is checked (sign, ``order``: non-decreasing), what a device
+    tensor holds is not (no host synchronisation)."""
+    if not isinstance(x, torch.Tensor):
+        try:
+            x = torch.as_tensor(x)
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise ValueError(f"StructuredMask: {what} must be an integer tensor or a (nested) sequence of ints: {e}")
+        if x.numel() == 0:  # an empty list comes out as float32
+            x = x.to(torch.int64)
+    if x.is_floating_point() or x.is_complex() or x.dtype == torch.bool:
+        raise ValueError(f"StructuredMask: {what} must hold integers, got {x.dtype}")
+    if x.dim() not in (1, 2):
+        raise ValueError(f"StructuredMask: {what} must be (n,) or (B, n), got shape {tuple(x.shape)}")
+    if x.device.type == "cpu" and x.numel() > 0:
+        if bool((x < 0).any()):
+            raise ValueError(f"StructuredMask: {what} has a negative entry")
+        if order and x.size(-1) > 1 and bool((x[..., 1:] < x[..., :-1]).any()):
+            raise ValueError(f"StructuredMask: {what} must be in non-decreasing order")
+    return x
 
 
 def resolve(mask, B: int, R: int, T: int, rank: int, packed: bool, device):

@@ -781,7 +781,7 @@ def seq_parallel_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tenso
     """Fused sequence-parallel attention on projected, head-interleaved (B, R, H*d) tensors.
 
     ``k``: row side (local rows), ``q``/``v``: gathered side (local shards), ``mask``: bool
-    (B, R, T) with True = masked, a :class:`xdot.StructuredMask` (causal / window / lengths; its
+    (B, R, T) with True = masked, a :class:`xdot.StructuredMask` (causal / window / lengths / documents; its
     packed form is generated on the GPU, the torch path builds its dense tensor), or None.
     ``rope``: an :class:`xdot.Rotary`; ``k`` and ``q`` are rotated at this rank's global positions
     (``rank * R`` unless the object carries an offset) before the attention, ``v`` is not.
