@@ -430,3 +430,54 @@ def test_flash_cols_row_splits(gpu, monkeypatch, dt, mask_kind):
         assert r16 <= (8e-3 if dt == torch.bfloat16 else 1e-3), f"splits {s}: 16-bit out {r16:.2e}"
         _close(f"splits {s} d cols (q)", flash.btc_to_rank_major(g16[..., :C].contiguous(), N), refq, gfro)
         _close(f"splits {s} d cols (v)", flash.btc_to_rank_major(g16[..., C:].contiguous(), N), refv, gfro)
+
+
+def test_flash_partial_slot_ops(gpu):
+    """The launches into partial slots (flash.fwd_partial / fwd_combine / fwd_merge /
+    bwd_rows_partial / bwd_rows_sum, slots sized by flash.splits) over two column segments match
+    the whole-row kernels; the first segment masks rows 0-39 entirely (its lse is -inf there)."""
+    from xdot.ops import flash
+
+    B, H, D, R, T = 1, 2, 32, 130, 200  # two row blocks, the second ragged
+    C, scale = H * D, 1.0 / math.sqrt(D)
+    segs = [(0, 128), (128, 200)]
+    g = torch.Generator(device="cpu").manual_seed(3)
+    rows = torch.randn(B, R, C, generator=g).to(gpu, torch.bfloat16)
+    kc = torch.randn(B, T, C, generator=g).to(gpu, torch.bfloat16)
+    vc = torch.randn(B, T, C, generator=g).to(gpu, torch.bfloat16)
+    do = torch.randn(B, R, C, generator=g).to(gpu, torch.bfloat16)
+    mask = torch.rand(B, R, T, generator=g) < 0.4
+    mask[:, :40, :128] = True
+    mask[..., T - 1] = False
+    mask = mask.to(gpu)
+    mks = [flash.prepare_mask(mask[..., a:b], B, R, b - a) for a, b in segs]
+    out, lse = flash.fwd(rows, kc, vc, flash.prepare_mask(mask, B, R, T), H, scale)
+
+    ns = [flash.splits(B, R, b - a, H) for a, b in segs]
+    opart = torch.empty(sum(ns), B, R, C, dtype=torch.float32, device=gpu)
+    lpart = torch.empty(sum(ns), B, H, R, dtype=torch.float32, device=gpu)
+    for i, ((a, b), mk) in enumerate(zip(segs, mks)):
+        flash.fwd_partial(rows, kc[:, a:b], vc[:, a:b], mk, H, scale, opart, lpart, sum(ns[:i]), ns[i])
+    assert (lpart[:ns[0], :, :, :40] == -float("inf")).all()
+    o2, l2 = flash.fwd_combine(opart, lpart, H, rows)
+    assert o2.dtype == rows.dtype and l2.dtype == torch.float32
+    _close("combined out", o2, out, 1e-2)
+    assert (l2 - lse).abs().max().item() < 1e-2, "combined lse"
+
+    lrun = torch.empty(B, H, R, dtype=torch.float32, device=gpu)
+    flash.fwd_merge(opart, lpart, lrun, H)  # every slot into slot 0, its LSE into lrun
+    lpart[0].copy_(lrun)
+    o3, l3 = flash.fwd_combine(opart[:1], lpart[:1], H, rows)
+    _close("merged out", o3, out, 1e-2)
+    assert (l3 - lse).abs().max().item() < 1e-2, "merged lse"
+
+    delta = flash.bwd_delta(do, out, H)
+    mk = flash.prepare_mask(mask, B, R, T)
+    dk = flash.bwd_rows(do, rows, kc, vc, lse, delta, mk, H, scale)
+    nr = [flash.splits(B, R, b - a, H, True) for a, b in segs]
+    dpart = torch.empty(sum(nr), B, R, C, dtype=torch.float32, device=gpu)
+    for i, ((a, b), mki) in enumerate(zip(segs, mks)):
+        flash.bwd_rows_partial(do, rows, kc[:, a:b], vc[:, a:b], lse, delta, mki, H, scale, dpart, sum(nr[:i]), nr[i])
+    dk2 = flash.bwd_rows_sum(dpart, H, rows)
+    assert dk2.dtype == rows.dtype
+    _close("summed d rows", dk2, dk, 1.5e-2)

@@ -30,7 +30,8 @@ from .. import _ext
 from ..ops.linear import linear_backward, native_wgrad, proj, weight_grad_pair
 from ..ops.rope import _table_dtype, rope_apply
 from ..utils.env import FLAGS
-from ..parallel.attention import SeqParallelAttention, _on_stream, gather_plan, prescale_wanted, start_gather
+from ..utils.streams import _on_stream, _side_stream
+from ..parallel.attention import SeqParallelAttention, gather_plan, prescale_wanted, start_gather
 
 _LOG2E = 1.4426950408889634  # as the kernels' scale * log2 e (csrc/flash_common.h, csrc/reduce.hip)
 
@@ -64,8 +65,6 @@ def _wgrad_stream(t):
     are library GEMMs: ``xdot.ops.linear.native_wgrad``)."""
     if not (t.is_cuda and FLAGS.wgrad_side and native_wgrad(t, t)) or torch.cuda.is_current_stream_capturing():
         return None
-    from ..parallel.attention import _side_stream
-
     return _side_stream(t.device, 0)
 
 

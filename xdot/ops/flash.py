@@ -259,6 +259,14 @@ def score_buffer_numel(B: int, H: int, R: int, T: int) -> int:
     return (B * H * ((R + 31) // 32) * ((T + 31) // 32) + 1) * 1024
 
 
+def _score_room(device) -> float:
+    """Bytes the score buffers may take: ``XDOT_FP32_SCORES_FRAC`` of the memory free on the
+    device (free + cached by torch)."""
+    free, _ = torch.cuda.mem_get_info(device)
+    cached = torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+    return FLAGS.fp32_scores_frac * (free + cached)
+
+
 def score_buffer(B: int, H: int, R: int, T: int, device) -> Optional[torch.Tensor]:
     """The fp32 score buffer (``csrc/flash_f32.hip`` exact, ``csrc/flash_x3.hip`` split; score-buffer mode) or None.
 
@@ -272,9 +280,7 @@ def score_buffer(B: int, H: int, R: int, T: int, device) -> Optional[torch.Tenso
         return None
     n = score_buffer_numel(B, H, R, T)
     dev = torch.device(device)
-    free, _ = torch.cuda.mem_get_info(dev)
-    cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-    if 4 * n > FLAGS.fp32_scores_frac * (free + cached):
+    if 4 * n > _score_room(dev):
         return None
     return torch.empty(n, dtype=torch.float32, device=dev)
 
@@ -297,9 +303,7 @@ def score_buffers(B: int, H: int, R: int, T: int, device, dsbuf: bool = True):
         return None
     n = score_buffer_numel(B, H, R, T)
     dev = torch.device(device)
-    free, _ = torch.cuda.mem_get_info(dev)
-    cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-    room = FLAGS.fp32_scores_frac * (free + cached)
+    room = _score_room(dev)
     if 8 * n <= room and FLAGS.fp32_scores_dsbuf and dsbuf:
         both = torch.empty(2 * n, dtype=torch.float32, device=dev)
         return both[:n], both[n:]
@@ -318,12 +322,6 @@ def ds_only_wanted(fp32_mode: int, D: int) -> bool:
         return False
     m = FLAGS.fp32_ds_only
     return m == "all" or (m == "split" and fp32_mode == 1)
-
-
-def ds_buffer(B: int, H: int, R: int, T: int, device) -> Optional[torch.Tensor]:
-    """The dS buffer of the dS-only mode (:func:`ds_only_wanted`), same size rule as
-    :func:`score_buffer`, or None."""
-    return score_buffer(B, H, R, T, device)
 
 
 def fwd(rows: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, mk: Optional[PackedMask], H: int,
@@ -400,3 +398,46 @@ def bwd(dout: torch.Tensor, rows: torch.Tensor, kc: torch.Tensor, vc: torch.Tens
                      sbuf=sbuf)
     C = rows.shape[-1]
     return drows, dkv[..., :C], dkv[..., C:]
+
+
+# ---- launches into partial slots (gather chunks, ring blocks) ------------------------------------
+def splits(B: int, R: int, T: int, H: int, rows_kernel: bool = False) -> int:
+    """Partial slots one :func:`fwd_partial` (``rows_kernel``: :func:`bwd_rows_partial`) launch over
+    ``T`` columns fills: the column splits the launcher picks for it."""
+    return int(_ext.ops().flash_splits(int(B), int(R), int(T), int(H), bool(rows_kernel)))
+
+
+def fwd_partial(rows: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, mk: Optional[PackedMask], H: int,
+                scale: float, opart: torch.Tensor, lpart: torch.Tensor, slot: int, nsplit: int,
+                prescaled: bool = False, fp32_mode: int = 0) -> None:
+    """Forward over one column segment into slots ``[slot, slot + nsplit)`` of ``opart`` (S, B, R, C)
+    / ``lpart`` (S, B, H, R), fp32: per slot the output normalised over its columns and their LSE
+    (-inf where they are all masked: the merges leave such a slot's output out).  ``rows`` contiguous."""
+    bits, flags = _mask_args(mk)
+    _ext.ops().flash_fwd_partial(rows, _kv(kc), _kv(vc), bits, flags, int(H), float(scale), opart, lpart, int(slot),
+                                 int(nsplit), bool(prescaled), int(fp32_mode))
+
+
+def fwd_combine(opart: torch.Tensor, lpart: torch.Tensor, H: int, like: torch.Tensor):
+    """Merge ALL slots -> (out like ``like`` (B, R, C), lse (B, H, R) fp32)."""
+    return _ext.ops().flash_fwd_combine(opart, lpart, int(H), like)
+
+
+def fwd_merge(opart: torch.Tensor, lpart: torch.Tensor, lrun: torch.Tensor, H: int) -> None:
+    """Merge all slots into slot 0 of ``opart`` in fp32, in place; the merged LSE goes to ``lrun``
+    (B, H, R) (slot 0 of ``lpart`` is still being read): the caller copies it back."""
+    _ext.ops().flash_fwd_merge(opart, lpart, lrun, int(H))
+
+
+def bwd_rows_partial(dout, rows, kc, vc, lse, delta, mk: Optional[PackedMask], H: int, scale: float,
+                     dpart: torch.Tensor, slot: int, nsplit: int, prescaled: bool = False, fp32_mode: int = 0) -> None:
+    """Row-side grads of one column segment into slots ``[slot, slot + nsplit)`` of ``dpart``
+    (S, B, R, C) fp32.  ``dout`` / ``rows`` / ``lse`` / ``delta`` contiguous."""
+    bits, flags = _mask_args(mk)
+    _ext.ops().flash_bwd_rows_partial(dout, rows, _kv(kc), _kv(vc), lse, delta, bits, flags, int(H), float(scale),
+                                      dpart, int(slot), int(nsplit), bool(prescaled), int(fp32_mode))
+
+
+def bwd_rows_sum(dpart: torch.Tensor, H: int, like: torch.Tensor) -> torch.Tensor:
+    """Σ of all ``dpart`` slots -> (B, R, C) like ``like``."""
+    return _ext.ops().flash_bwd_rows_sum(dpart, int(H), like)

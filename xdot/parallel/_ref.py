@@ -1,0 +1,69 @@
+"""The attention maths in torch, written once: the oracle of the CPU tests and the path that CPU
+tensors (and GPU dtypes the kernels do not take) run.  Row side ``k`` (B, R, H*dh), one column
+segment of the gathered side ``kc`` (B, T, H*dh) / ``vc`` (B, T, H*dv), ``mask`` bool (B, R, T)
+with True = masked, or None.  fp64 stays fp64, everything else computes in fp32.  The flash and
+the ring path are layout adapters over these functions (:mod:`xdot.parallel.attention`,
+:mod:`xdot.parallel.ring`)."""
+from __future__ import annotations
+
+import torch
+
+
+def compute_dtype(x):
+    return torch.float64 if x.dtype == torch.float64 else torch.float32
+
+
+def heads(x, H: int, cdt):
+    """(B, L, H*d) -> (B, H, L, d) in the compute dtype."""
+    B, L, C = x.shape
+    return x.reshape(B, L, H, C // H).transpose(1, 2).to(cdt)
+
+
+def _merge(x):
+    """(B, H, L, d) -> (B, L, H*d)"""
+    return x.transpose(1, 2).reshape(x.shape[0], x.shape[2], -1)
+
+
+def _scores(kh, qh, mask, scale):
+    s = torch.matmul(kh, qh.transpose(-1, -2)) * scale
+    if mask is not None:
+        s = s.masked_fill(mask.unsqueeze(1), -float("inf"))
+    return s
+
+
+def delta(do, o, H: int, cdt):
+    """δ = rowsum(dO ⊙ O) per head: (B, H, R)."""
+    return (heads(do, H, cdt) * heads(o, H, cdt)).sum(-1)
+
+
+def block_fwd(k, kc, vc, mask, H: int, scale: float):
+    """One column segment of the forward -> (o (B, R, H*dv) normalised over the segment, lse
+    (B, H, R)), compute dtype; a row the segment masks entirely gets o = 0, lse = -inf."""
+    cdt = compute_dtype(k)
+    s = _scores(heads(k, H, cdt), heads(kc, H, cdt), mask, scale)
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - lse.clamp_min(torch.finfo(cdt).min).unsqueeze(-1))
+    return _merge(torch.matmul(p, heads(vc, H, cdt))), lse
+
+
+def combine(parts, dtype):
+    """Merge segment partials [(o, lse)] -> (o in ``dtype``, lse); NaN for fully masked rows.  One
+    part comes back bit for bit on its live rows (its weight is exactly 1)."""
+    L = torch.stack([l for _, l in parts])                      # (S, B, H, R)
+    lse = torch.logsumexp(L, dim=0)
+    w = torch.exp(L - lse.unsqueeze(0))                         # NaN only where every segment is -inf
+    H = lse.shape[1]
+    o = sum(wi.transpose(1, 2).repeat_interleave(oi.shape[-1] // H, dim=-1) * oi
+            for wi, (oi, _) in zip(w, parts))
+    return o.to(dtype), lse
+
+
+def block_bwd(do, k, kc, vc, lse, delta, mask, H: int, scale: float):
+    """Gradients of one column segment given the whole row's ``lse`` and ``delta`` (B, H, R) ->
+    (dk (B, R, H*dh), dq (B, T, H*dh), dv (B, T, H*dv)), compute dtype."""
+    cdt = compute_dtype(k)
+    kh, qh, vh, doh = heads(k, H, cdt), heads(kc, H, cdt), heads(vc, H, cdt), heads(do, H, cdt)
+    p = torch.exp(_scores(kh, qh, mask, scale) - lse.unsqueeze(-1))
+    ds = p * (torch.matmul(doh, vh.transpose(-1, -2)) - delta.unsqueeze(-1)) * scale
+    return (_merge(torch.matmul(ds, qh)), _merge(torch.matmul(ds.transpose(-1, -2), kh)),
+            _merge(torch.matmul(p.transpose(-1, -2), doh)))

@@ -32,10 +32,13 @@ import torch
 from torch import Tensor
 
 from .. import _ext
+from ..ops import flash
 from ..ops.mask import StructuredMask, resolve as resolve_mask
 from ..utils import comm as _comm
 from ..utils.checks import check_consistent
 from ..utils.env import FLAGS
+from ..utils.streams import _on_stream, _prep_event, _side_stream
+from . import _ref
 
 __all__ = ["seq_parallel_attention", "seq_parallel_attention_packed", "start_gather", "flash_supported",
            "SeqParallelAttention"]
@@ -78,20 +81,31 @@ def unpad_heads(x: Tensor, H: int, d: int, Dp: int) -> Tensor:
 def flash_supported(x: Tensor, head_dim: int, v_head_dim: int) -> bool:
     """The flash kernels take this (dtype, device, head dims), directly or zero-padded
     (:func:`flash_head_dim`)."""
-    if not x.is_cuda or x.dtype not in FLASH_DTYPES:
-        return False
-    if flash_head_dim(head_dim, v_head_dim) is None:
-        return False
-    return _ext.use_hip(x) and hasattr(_ext.ops(), "flash_fwd")
+    return _kernels_take(x) and flash_head_dim(head_dim, v_head_dim) is not None
+
+
+def _kernels_take(x: Tensor) -> bool:
+    """A GPU tensor of a flash dtype, and the extension with the flash kernels is loaded."""
+    return bool(x.is_cuda and x.dtype in FLASH_DTYPES and _ext.use_hip(x) and hasattr(_ext.ops(), "flash_fwd"))
 
 
 def _hip_ok(k: Tensor, qv: Tensor, H: int) -> bool:
-    """The HIP kernels take this call: a GPU bf16/fp16 row side, a supported head dim and a
+    """The HIP kernels take this call: a GPU bf16/fp16/fp32 row side, a supported head dim and a
     value width equal to the key width (otherwise the torch path runs, as documented)."""
     C = k.shape[-1]
-    return (k.is_cuda and k.dtype in FLASH_DTYPES and C % H == 0
-            and C // H in FLASH_HEAD_DIMS and qv.shape[-1] == 2 * C and _ext.use_hip(k)
-            and hasattr(_ext.ops(), "flash_fwd"))
+    return C % H == 0 and C // H in FLASH_HEAD_DIMS and qv.shape[-1] == 2 * C and _kernels_take(k)
+
+
+def _prescale_rows(k: Tensor) -> bool:
+    """The HIP path runs on a pre-scaled row side (``flash.prescale``; XDOT_PRESCALE, default on):
+    16-bit rows with a multiple of 8 elements."""
+    return bool(FLAGS.prescale and k.numel() % 8 == 0 and k.dtype != torch.float32)
+
+
+def prescale_wanted(k_like: Tensor, qv_like: Tensor, H: int) -> bool:
+    """The HIP path will run on pre-scaled rows for a row side shaped / typed like ``k_like``
+    (the condition :meth:`SeqParallelAttention.forward` applies)."""
+    return _hip_ok(k_like, qv_like, H) and _prescale_rows(k_like)
 
 
 # ----------------------------------------------------------------------------------------
@@ -192,94 +206,63 @@ def _as_global(g: Tensor) -> Tensor:
 
 
 # ----------------------------------------------------------------------------------------
-# torch reference implementation of the per-rank compute (CPU / fallback / testing)
+# torch path of the per-rank compute (CPU / fallback / testing): layout adapters over _ref
 # ----------------------------------------------------------------------------------------
-def _cdt(x):
-    return torch.float64 if x.dtype == torch.float64 else torch.float32
+def _forward_torch(k, qvg, mask, H, scale):
+    """Whole-row forward from the rank-major gathered (N, B, R, C + Cv): one block, combined
+    alone (a fully masked row comes out NaN)."""
+    C = k.shape[-1]
+    part = _ref.block_fwd(k, _as_global(qvg[..., :C]), _as_global(qvg[..., C:]), mask, H, scale)
+    return _ref.combine([part], k.dtype)
 
 
-def _ref_fwd(k, qg, vg, mask, H, scale):
-    cdt = _cdt(k)
+def _segmented_forward_torch(k, qv, mask, H, scale, pending, n, rank):
     B, R, C = k.shape
-    dh = C // H
-    dv = vg.shape[-1] // H
-    qa, va = _as_global(qg), _as_global(vg)
-    T = qa.shape[1]
-    kh = k.view(B, R, H, dh).transpose(1, 2).to(cdt)
-    qh = qa.view(B, T, H, dh).transpose(1, 2).to(cdt)
-    vh = va.view(B, T, H, dv).transpose(1, 2).to(cdt)
-    s = torch.matmul(kh, qh.transpose(-1, -2)) * scale
-    if mask is not None:
-        s = s.masked_fill(mask.unsqueeze(1), -float("inf"))
-    lse = torch.logsumexp(s, dim=-1)                      # (B, H, R)
-    p = torch.exp(s - lse.unsqueeze(-1))
-    o = torch.matmul(p, vh)                               # (B, H, R, dv)
-    return o.transpose(1, 2).reshape(B, R, H * dv).to(k.dtype), lse
+    plan = _segment_plan(n, rank, len(pending.chunks), FLAGS.local_first)
+    parts = []
+    if FLAGS.local_first:
+        own = None if mask is None else _mask_cols(B, R, n, rank, rank + 1, 0, R)(mask)
+        parts.append(_ref.block_fwd(k, qv[..., :C], qv[..., C:], own, H, scale))
+    gs = []
+    for c, (r0, rc) in enumerate(pending.chunks):
+        g = pending.wait(c)                                      # (N, B, rc, 2C)
+        gs.append(g)
+        for _, j0, j1 in (p for p in plan if p[0] == c):
+            seg = _as_global(g[j0:j1])
+            m = None if mask is None else _mask_cols(B, R, n, j0, j1, r0, rc)(mask)
+            parts.append(_ref.block_fwd(k, seg[..., :C], seg[..., C:], m, H, scale))
+    o, lse = _ref.combine(parts, k.dtype)
+    return o, lse, [torch.cat(gs, dim=2) if len(gs) > 1 else gs[0]]
 
 
-def _ref_fwd_partial(k, kc, vc, mask, H, scale):
-    """One column segment of the forward in torch: ``kc``/``vc`` (B, Tseg, ·) in the segment's
-    column order, ``mask`` (B, R, Tseg) or None -> (o (B, R, H*dv) normalised over the
-    segment, lse (B, H, R)); a row the segment masks entirely gets o = 0, lse = -inf."""
-    cdt = _cdt(k)
-    B, R, C = k.shape
-    dh = C // H
-    T = kc.shape[1]
-    dv = vc.shape[-1] // H
-    kh = k.view(B, R, H, dh).transpose(1, 2).to(cdt)
-    qh = kc.reshape(B, T, H, dh).transpose(1, 2).to(cdt)
-    vh = vc.reshape(B, T, H, dv).transpose(1, 2).to(cdt)
-    s = torch.matmul(kh, qh.transpose(-1, -2)) * scale
-    if mask is not None:
-        s = s.masked_fill(mask.unsqueeze(1), -float("inf"))
-    lse = torch.logsumexp(s, dim=-1)
-    p = torch.exp(s - lse.clamp_min(torch.finfo(cdt).min).unsqueeze(-1))
-    o = torch.matmul(p, vh)
-    return o.transpose(1, 2).reshape(B, R, H * dv), lse
+def _backward_torch(ctx, do, k, o, lse, qvg):
+    """-> (dk, d[q|v] of this rank's rows) from the rank-major gathered ``qvg`` (N, B, R, C + Cv)."""
+    C = k.shape[-1]
+    n, B, Rg = qvg.shape[:3]
+    delta = _ref.delta(do, o, ctx.H, lse.dtype)
+    dk, dq, dv = _ref.block_bwd(do, k, _as_global(qvg[..., :C]), _as_global(qvg[..., C:]), lse, delta, ctx.mask,
+                                ctx.H, ctx.scale)
+    parts = torch.cat([dq, dv], dim=-1).view(B, n, Rg, -1).permute(1, 0, 2, 3).contiguous()  # rank-major
+    if k.dtype in (torch.bfloat16, torch.float16) and not FLAGS.grad_fp32:
+        parts = parts.to(k.dtype)  # the HIP path's wire dtype (one rounding per partial)
+    h, dqv = _reduce_async(ctx.comm, parts)
+    if h is not None:
+        h.wait()
+    return dk, dqv
 
 
-def _ref_combine(parts, dtype):
-    """Merge segment partials [(o, lse)] -> (o in ``dtype``, lse); NaN for fully masked rows."""
-    L = torch.stack([l for _, l in parts])                      # (S, B, H, R)
-    lse = torch.logsumexp(L, dim=0)
-    w = torch.exp(L - lse.unsqueeze(0))                         # NaN only where every segment is -inf
-    B, H, R = lse.shape
-    o = sum(wi.transpose(1, 2).repeat_interleave(oi.shape[-1] // H, dim=-1) * oi
-            for wi, (oi, _) in zip(w, parts))
-    return o.to(dtype), lse
+def _reduce_async(comm, parts, out=None):
+    """(N, B, rc, 2C) rank-major partials -> (handle or None, (B, rc, 2C))"""
+    if comm.world_size == 1:
+        return None, parts[0]
+    if out is None:
+        out = torch.empty(parts.shape[1:], dtype=parts.dtype, device=parts.device)
+    return comm.reduce_scatter(out, parts, async_op=True), out
 
 
-def _ref_bwd(do, k, qg, vg, o, lse, mask, H, scale):
-    cdt = _cdt(k)
-    B, R, C = k.shape
-    dh = C // H
-    dv = vg.shape[-1] // H
-    n = qg.shape[0]
-    qa, va = _as_global(qg), _as_global(vg)
-    T = qa.shape[1]
-    kh = k.view(B, R, H, dh).transpose(1, 2).to(cdt)
-    qh = qa.view(B, T, H, dh).transpose(1, 2).to(cdt)
-    vh = va.view(B, T, H, dv).transpose(1, 2).to(cdt)
-    doh = do.view(B, R, H, dv).transpose(1, 2).to(cdt)
-    oh = o.view(B, R, H, dv).transpose(1, 2).to(cdt)
-    s = torch.matmul(kh, qh.transpose(-1, -2)) * scale
-    if mask is not None:
-        s = s.masked_fill(mask.unsqueeze(1), -float("inf"))
-    p = torch.exp(s - lse.unsqueeze(-1))
-    delta = (doh * oh).sum(-1, keepdim=True)
-    dp = torch.matmul(doh, vh.transpose(-1, -2))
-    ds = p * (dp - delta) * scale
-    dk = torch.matmul(ds, qh)                                          # (B, H, R, dh)
-    dq_all = torch.matmul(ds.transpose(-1, -2), kh)                    # (B, H, T, dh)
-    dv_all = torch.matmul(p.transpose(-1, -2), doh)                    # (B, H, T, dv)
-    dk = dk.transpose(1, 2).reshape(B, R, H * dh)
-
-    def rank_major(x, d):  # (B, H, T, d) -> (N, B, R, H*d)
-        return x.transpose(1, 2).reshape(B, n, R, H * d).permute(1, 0, 2, 3).contiguous()
-
-    return dk, rank_major(dq_all, dh), rank_major(dv_all, dv)
-
-
+# ----------------------------------------------------------------------------------------
+# the segmented forward
+# ----------------------------------------------------------------------------------------
 def _segment_plan(n: int, rank: int, nchunks: int, local_first: bool) -> List[Tuple[int, int, int]]:
     """Peer segments (chunk c, source ranks j0..j1-1) of the segmented forward, in launch order;
     the own rank is left out of every chunk when its block runs first."""
@@ -301,66 +284,44 @@ def _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescal
     all-gather is in flight), then each gathered chunk's peer blocks as soon as that chunk
     lands.  Every segment is a subset of a row's columns, so the partials (o normalised over
     the segment, its lse) merge exactly.  -> (o, lse, gathered buffers saved for backward)."""
+    if not use_hip:
+        return _segmented_forward_torch(k, qv, mask, H, scale, pending, n, rank)
     B, R, C = k.shape
     chunks = pending.chunks
     local_first = FLAGS.local_first
     plan = _segment_plan(n, rank, len(chunks), local_first)
-    own = _mask_cols(B, R, n, rank, rank + 1, 0, R)
-    if use_hip:
-        from ..ops import flash
+    if local_first and 0 < rank < n - 1 and SEGMENT_MERGE:
+        # a middle rank's peers sit on both sides of its own block in every chunk: ONE partial
+        # over the whole chunk with the own columns masked out (their tiles are skipped whole,
+        # two boundary tiles per row block take the masked path) instead of two launches
+        plan = [(c, 0, -1) for c in range(len(chunks))]
+    widths = ([R] if local_first else []) + [(n if j1 == -1 else j1 - j0) * chunks[c][1] for c, j0, j1 in plan]
+    ns = [flash.splits(B, R, w, H) for w in widths]
+    opart = torch.empty(sum(ns), B, R, C, dtype=torch.float32, device=k.device)
+    lpart = torch.empty(sum(ns), B, H, R, dtype=torch.float32, device=k.device)
+    slots = iter([(sum(ns[:i]), nsi) for i, nsi in enumerate(ns)])  # (first slot, slots) per launch
 
-        ops = _ext.ops()
-        if local_first and 0 < rank < n - 1 and SEGMENT_MERGE:
-            # a middle rank's peers sit on both sides of its own block in every chunk: ONE partial
-            # over the whole chunk with the own columns masked out (their tiles are skipped whole,
-            # two boundary tiles per row block take the masked path) instead of two launches
-            plan = [(c, 0, -1) for c in range(len(chunks))]
-        widths = ([R] if local_first else []) + [(n if j1 == -1 else j1 - j0) * chunks[c][1] for c, j0, j1 in plan]
-        ns = [int(ops.flash_splits(B, R, w, H, False)) for w in widths]
-        opart = torch.empty(sum(ns), B, R, C, dtype=torch.float32, device=k.device)
-        lpart = torch.empty(sum(ns), B, H, R, dtype=torch.float32, device=k.device)
-        slot = [0, 0]  # next partial slot, next entry of ns
+    def run(seg, mk):  # seg: (B, Tseg, 2C) = [q | v] of the segment's columns
+        slot, nsi = next(slots)
+        flash.fwd_partial(k, seg[..., :C], seg[..., C:], mk, H, scale, opart, lpart, slot, nsi, prescaled, fp32_mode)
 
-        def run(kc, vc, mk):
-            bits, flags = (mk.bits, mk.flags) if mk is not None else (None, None)
-            nsi = ns[slot[1]]
-            ops.flash_fwd_partial(k, flash._kv(kc), flash._kv(vc), bits, flags, int(H), float(scale), opart, lpart,
-                                  slot[0], nsi, prescaled, fp32_mode)
-            slot[0] += nsi
-            slot[1] += 1
-
-        if local_first:
-            mk = flash.prepare_mask_cached(mask, B, R, R, tag=("own", rank, n), view=own)
-            run(qv[..., :C], qv[..., C:], mk)
-        bufs = []
-        for c, (r0, rc) in enumerate(chunks):
-            g = flash.gathered_to_btc(pending.wait(c))          # (B, N*rc, 2C)
-            bufs.append(g)
-            for _, j0, j1 in (p for p in plan if p[0] == c):
-                if j1 == -1:  # merged: every rank of the chunk, the own columns masked out
-                    mk = _own_excluded_mask(mask, B, R, n, rank, r0, rc, k.device)
-                    run(g[..., :C], g[..., C:], mk)
-                    continue
-                mk = flash.prepare_mask_cached(mask, B, R, (j1 - j0) * rc, tag=("seg", r0, rc, n, j0, j1),
-                                               view=_mask_cols(B, R, n, j0, j1, r0, rc))
-                seg = g[:, j0 * rc:j1 * rc]
-                run(seg[..., :C], seg[..., C:], mk)
-        o, lse = ops.flash_fwd_combine(opart, lpart, int(H), k)
-        perm = pending.permuted()
-        return o, lse, ([perm] if perm is not None else bufs)
-    parts = []
     if local_first:
-        parts.append(_ref_fwd_partial(k, qv[..., :C], qv[..., C:], None if mask is None else own(mask), H, scale))
-    gs = []
+        own = _mask_cols(B, R, n, rank, rank + 1, 0, R)
+        run(qv, flash.prepare_mask_cached(mask, B, R, R, tag=("own", rank, n), view=own))
+    bufs = []
     for c, (r0, rc) in enumerate(chunks):
-        g = pending.wait(c)                                      # (N, B, rc, 2C)
-        gs.append(g)
+        g = flash.gathered_to_btc(pending.wait(c))          # (B, N*rc, 2C)
+        bufs.append(g)
         for _, j0, j1 in (p for p in plan if p[0] == c):
-            seg = _as_global(g[j0:j1])
-            m = None if mask is None else _mask_cols(B, R, n, j0, j1, r0, rc)(mask)
-            parts.append(_ref_fwd_partial(k, seg[..., :C], seg[..., C:], m, H, scale))
-    o, lse = _ref_combine(parts, k.dtype)
-    return o, lse, [torch.cat(gs, dim=2) if len(gs) > 1 else gs[0]]
+            if j1 == -1:  # merged: every rank of the chunk, the own columns masked out
+                run(g, _own_excluded_mask(mask, B, R, n, rank, r0, rc, k.device))
+                continue
+            mk = flash.prepare_mask_cached(mask, B, R, (j1 - j0) * rc, tag=("seg", r0, rc, n, j0, j1),
+                                           view=_mask_cols(B, R, n, j0, j1, r0, rc))
+            run(g[:, j0 * rc:j1 * rc], mk)
+    o, lse = flash.fwd_combine(opart, lpart, H, k)
+    perm = pending.permuted()
+    return o, lse, ([perm] if perm is not None else bufs)
 
 
 _OWN_EX = {}
@@ -373,8 +334,6 @@ def _own_excluded_mask(mask, B: int, R: int, n: int, rank: int, r0: int, rc: int
     """Packed (B, R, n*rc) mask of one gather chunk with this rank's own columns masked (they
     ran first, under the all-gather), OR-ed with the user mask's columns of the chunk.  Cached:
     on the user mask (MASK_CACHE) or, without one, per shape."""
-    from ..ops import flash
-
     def own_cols(m):  # (a row of column indices: -1 = always masked)
         m = m.clone()
         m[..., rank * rc:(rank + 1) * rc] = True if m.dtype == torch.bool else -1
@@ -395,7 +354,6 @@ def _own_excluded_mask(mask, B: int, R: int, n: int, rank: int, r0: int, rc: int
     return _OWN_EX[key]
 
 
-_SIDE = {}
 # The fused backward runs its gathered-side half on a high-priority side stream so the row-side
 # kernel fills the column kernel's last, mostly empty workgroup round.  Eager, on one MI355X
 # (benchmarks/graph_ab.py, profiles/r3_graph.md), two streams vs one: N=1 8.18 vs 8.60 ms, N=2
@@ -406,58 +364,220 @@ _SIDE = {}
 ONE_STREAM_BACKWARD = None
 
 
-def _two_stream_backward(R: int) -> bool:
+def _two_stream_backward() -> bool:
     if ONE_STREAM_BACKWARD is not None:
         return not ONE_STREAM_BACKWARD
     return not torch.cuda.is_current_stream_capturing()
 
 
-def _side_stream(dev: torch.device, priority: int = -1, tag: str = "") -> "torch.cuda.Stream":
-    """Per-device compute stream of the backward (created once per priority and tag; -1 = high)."""
-    i = dev.index if dev.index is not None else torch.cuda.current_device()
-    if (i, priority, tag) not in _SIDE:
-        _SIDE[(i, priority, tag)] = torch.cuda.Stream(device=i, priority=priority)
-    return _SIDE[(i, priority, tag)]
+# ----------------------------------------------------------------------------------------
+# HIP halves of the autograd function
+# ----------------------------------------------------------------------------------------
+def _score_buffers(k, H, T, fm, one_kernel, segmented):
+    """The fp32 score buffers of a forward that a backward will follow -> (sbuf, dsbuf, segmented).
+    When a buffer fits (``flash.score_buffer``) the backward reads S / dS instead of recomputing
+    them, and ONE kernel runs over the whole gathered side (in fp32 the own-block-first
+    segmentation hides < 5 % of a rank's forward): ``segmented`` comes back False.
+    ``one_kernel``: the gathered side is (or can be read as) one buffer."""
+    B, R, C = k.shape
+    D = C // H
+    sbuf = dsbuf = None
+    if one_kernel:
+        if flash.ds_only_wanted(fm, D):  # dS-only: nothing stored by the forward
+            dsbuf = flash.score_buffer(B, H, R, T, k.device)
+            if dsbuf is not None:
+                segmented = False
+        else:
+            # the fused exact column pass overwrites S with dS in place: no second buffer
+            sbs = flash.score_buffers(B, H, R, T, k.device, dsbuf=not flash.fused_cols_wanted(fm, D))
+            if sbs is not None:
+                sbuf, dsbuf = sbs
+                segmented = False
+    if D > WIDE_F32_NEEDS_SCORES and sbuf is None:
+        # no kernel recomputes an fp32 head this wide (three D-wide register sets) and the torch
+        # path would materialise a score matrix larger than the buffer that did not fit
+        raise RuntimeError(
+            f"xdot: training exact-fp32 attention at head dim {D} needs the flash score buffer "
+            f"({4 * flash.score_buffer_numel(B, H, R, T) / 2**30:.1f} GiB), which does not fit "
+            f"within XDOT_FP32_SCORES_FRAC={FLAGS.fp32_scores_frac} of the free device memory: shorten the "
+            "sequence, raise XDOT_FP32_SCORES_FRAC, or run the module in bf16")
+    return sbuf, dsbuf, segmented
 
 
-_EV = {}
+def _whole_forward_hip(k, mask, packed_full, pending, n, H, scale, prescaled, fm, sbuf):
+    """One kernel over the whole gathered side -> (o, lse, the (B, T, 2C) buffer, its packed mask)."""
+    B, R, C = k.shape
+    chunks = pending.chunks
+    if len(chunks) > 1:  # several gather chunks, one buffer in (chunk, rank, row) order
+        pending.wait_all()
+        qvg = pending.permuted()
+        mk = _whole_mask(mask, B, R, n, chunks)
+    else:
+        mk = packed_full if packed_full is not None else _whole_mask(mask, B, R, n, chunks)
+        qvg = flash.gathered_to_btc(pending.wait(0))     # (B, T, 2C), a view for B = 1
+    o, lse = flash.fwd(k, qvg[..., :C], qvg[..., C:], mk, H, scale, prescaled=prescaled, fp32_mode=fm, sbuf=sbuf)
+    return o, lse, qvg, mk
 
 
-def _prep_event(dev) -> "torch.cuda.Event":
-    """One reusable event per device for "δ is ready" (a stream wait captures the event's state at
-    the call, so re-recording it next step is safe): no event creation per backward."""
-    i = dev.index if dev.index is not None else torch.cuda.current_device()
-    if i not in _EV:
-        _EV[i] = torch.cuda.Event()
-    return _EV[i]
+def _whole_mask(mask, B, R, n, chunks):
+    """Packed (cached) mask of the one gathered buffer: rank-major columns, or with several gather
+    chunks their (chunk, rank, row) order."""
+    if len(chunks) == 1:
+        return flash.prepare_mask_cached(mask, B, R, n * R)
+    return flash.prepare_mask_cached(mask, B, R, n * R, tag=("perm", tuple(chunks), n), view=_perm_cols(B, R, n, chunks))
 
 
-class _on_stream:
-    """``with _on_stream(s, cur):`` makes ``s`` current and restores ``cur`` (the caller's
-    current stream, already looked up).  Same effect as ``torch.cuda.stream(s)`` on one device
-    without its device-index and current-stream lookups: 0.9 vs 5.8 µs of host per switch on
-    MI355X (``benchmarks/micro/stream_ctx.py``)."""
-    __slots__ = ("s", "cur")
-
-    def __init__(self, s, cur):
-        self.s, self.cur = s, cur
-
-    def __enter__(self):
-        if self.s is not self.cur:
-            torch.cuda.set_stream(self.s)
-        return self.s
-
-    def __exit__(self, *exc):
-        if self.s is not self.cur:
-            torch.cuda.set_stream(self.cur)
-        return False
+def _backward_masks(ctx, B, R, n, one):
+    """The packed masks of the backward's buffers: the forward's, or packed here (cached) after a
+    segmented forward."""
+    chunks = ctx.chunks
+    if ctx.mks is not None and not (one and len(chunks) > 1):
+        return ctx.mks
+    if one:
+        return [_whole_mask(ctx.mask, B, R, n, chunks)]
+    return [flash.prepare_mask_cached(ctx.mask, B, R, n * rc, tag=(r0, rc, n),
+                                      view=_mask_cols(B, R, n, 0, n, r0, rc)) for r0, rc in chunks]
 
 
-def prescale_wanted(k_like: Tensor, qv_like: Tensor, H: int) -> bool:
-    """The HIP path will run on pre-scaled rows for a row side shaped / typed like ``k_like``
-    (the condition :meth:`SeqParallelAttention.forward` applies)."""
-    return (_hip_ok(k_like, qv_like, H) and FLAGS.prescale and k_like.numel() % 8 == 0
-            and k_like.dtype != torch.float32)
+def _saved_scores(ctx, sbt, k, H):
+    """(S buffer, dS buffer) of this backward.  Score buffer: S -> dS in the column kernel, then dK
+    from dS.  With a separate dS buffer S stays intact, so a second backward through a retained
+    graph reads it again; in place (S overwritten with dS) the first backward consumes it and a
+    second one recomputes."""
+    has_s, has_ds = getattr(ctx, "sb_kind", (False, False))
+    sbuf = sbt[0] if has_s else None
+    dsbuf = sbt[-1] if has_ds else None
+    if has_s and not has_ds:
+        if getattr(ctx, "sb_used", False):
+            sbuf = None
+        ctx.sb_used = True
+    D = k.shape[-1] // H
+    if sbuf is None and k.dtype == torch.float32 and D > WIDE_F32_NEEDS_SCORES and ctx.fp32_mode == 0:
+        raise RuntimeError(
+            f"xdot: a second backward through a retained graph of exact-fp32 attention at head dim "
+            f"{D} needs the scores, which the first backward overwrote in place (no kernel "
+            "recomputes an fp32 head this wide); set XDOT_FP32_SCORES_DS=1 with room for the "
+            "separate dS buffer, or do not retain the graph")
+    return sbuf, dsbuf
+
+
+def _cols_one_buffer(cols, g, mk, sbuf, dsbuf, fused, hi):
+    """The column pass(es) over the one gathered buffer -> (d[q|v] (B, T, 2C), the event after
+    which the row kernel may read dS from a score buffer, or None)."""
+    if dsbuf is not None and sbuf is not None:
+        # dQ pass (S -> dS), then the row kernel (reads dS) on `cur` concurrently
+        # with the dV pass (reads S) here.  (The dV pass beside the dQ pass on a third
+        # stream instead measured 54.62 vs 54.71 ms, and one rep ran 171 ms:
+        # profiles/r6_fp32.md)
+        dkv, _ = cols(g, mk, sbuf=sbuf, dsbuf=dsbuf, passes=2)
+        ev_cols = torch.cuda.Event()
+        ev_cols.record(hi)
+        cols(g, mk, sbuf=sbuf, dsbuf=dsbuf, passes=1, out_dkv=dkv)
+        return dkv, ev_cols
+    # (fused exact pass: dP, dQ and dV in one kernel, S -> dS in place)
+    dkv, _ = cols(g, mk, sbuf=sbuf, dsbuf=dsbuf, passes=4 if fused else 3)
+    if sbuf is None and dsbuf is None:
+        return dkv, None
+    ev_cols = torch.cuda.Event()  # the row kernel reads the dS this kernel wrote
+    ev_cols.record(hi)
+    return dkv, ev_cols
+
+
+def _rows_hip(ctx, do, k, lse, delta, bufs, mks, sbuf, dsbuf, cur):
+    """Row-side dk on the current stream: one kernel over the one buffer, or one partial launch
+    per chunk buffer and their sum."""
+    H, scale = ctx.H, ctx.scale
+    B, R, C = k.shape
+    if len(bufs) == 1:
+        g = bufs[0]
+        dk = flash.bwd_rows(do, k, g[..., :C], g[..., C:], lse, delta, mks[0], H, scale,
+                            nsplit=FLAGS.rows_split, prescaled=ctx.prescaled, fp32_mode=ctx.fp32_mode,
+                            sbuf=sbuf, dsbuf=dsbuf)
+        if sbuf is not None:
+            sbuf.record_stream(cur)
+        if dsbuf is not None:
+            dsbuf.record_stream(cur)
+        return dk
+    ns = flash.splits(B, R, ctx.comm.world_size * ctx.chunks[0][1], H, True)
+    dpart = torch.empty(len(bufs) * ns, B, R, C, dtype=torch.float32, device=k.device)
+    for c, (g, mk) in enumerate(zip(bufs, mks)):
+        flash.bwd_rows_partial(do, k, g[..., :C], g[..., C:], lse, delta, mk, H, scale, dpart, c * ns, ns,
+                               ctx.prescaled, ctx.fp32_mode)
+    return flash.bwd_rows_sum(dpart, H, k)
+
+
+def _backward_hip(ctx, do, k, o, lse, bufs, sbt):
+    """δ, then two independent streams: 1) gathered-side grads on a HIGH-priority stream,
+    followed there by their reduce-scatter(s), and 2) the row-side dk on the current
+    stream.  2) fills the partly occupied last workgroup rounds of 1) and hides the
+    reduce-scatter, while the priority keeps 1) (and so the collective) nearly as
+    early as when it runs alone.  δ runs on the priority stream too, so 1) reaches
+    the GPU first.  Per-chunk kernels (chunk c's reduce-scatter under chunk c+1's
+    kernel) only when the chunks are separate buffers (B > 1)."""
+    comm, H, scale, chunks = ctx.comm, ctx.H, ctx.scale, ctx.chunks
+    n = comm.world_size
+    B, R, C = k.shape
+    one = len(bufs) == 1  # one gathered buffer: natural order, or chunks permuted (B = 1)
+    mks = _backward_masks(ctx, B, R, n, one)
+    cur = torch.cuda.current_stream(do.device)
+    # high priority so the gathered side (and its reduce-scatter) finishes early (an
+    # ordinary-priority side stream measured slower at N=1 and N=8: profiles/r2_bwd_overlap.md)
+    hi = _side_stream(do.device, -1) if _two_stream_backward() else cur
+    hi.wait_stream(cur)
+    handles, outs = [], []
+    gdt = k.dtype if not FLAGS.grad_fp32 else torch.float32
+    sbuf, dsbuf = _saved_scores(ctx, sbt, k, H)
+    ev_cols = None
+    with _on_stream(hi, cur):
+        delta, lse2 = flash.bwd_prep(do, o, lse, H)  # one prep pass for both kernels
+        ev = _prep_event(hi.device)
+        ev.record(hi)
+        dqv = None
+        if n > 1 and len(chunks) > 1 and B == 1:
+            dqv = torch.empty(B, R, 2 * C, dtype=gdt, device=k.device)
+        # partials rounded once to the compute dtype in the kernel (XDOT_GRAD_FP32=1
+        # keeps fp32): half the epilogue stores and half the reduce-scatter bytes
+        cargs = dict(fp32_out=FLAGS.grad_fp32, prescaled=ctx.prescaled, lse2=lse2, fp32_mode=ctx.fp32_mode)
+
+        def cols(g, mk, **kw):
+            return flash.bwd_cols(do, k, g[..., :C], g[..., C:], o, lse, mk, H, scale, delta, **cargs, **kw)
+
+        def scatter(part, r0, rc):  # (B, n*rc, 2C) of one chunk -> its reduce-scatter
+            h, oc = _reduce_async(comm, flash.btc_to_rank_major(part, n), None if dqv is None else dqv[:, r0:r0 + rc])
+            handles.append(h)
+            outs.append(oc)
+
+        if one:
+            fused = sbuf is not None and dsbuf is None and flash.fused_cols_wanted(ctx.fp32_mode, C // H)
+            dkv, ev_cols = _cols_one_buffer(cols, bufs[0], mks[0], sbuf, dsbuf, fused, hi)
+            off = 0
+            for r0, rc in chunks:  # (chunk, rank, row) order: chunk c's ranks are contiguous
+                scatter(dkv if len(chunks) == 1 else dkv[:, off:off + n * rc], r0, rc)
+                off += n * rc
+        else:
+            for c, (r0, rc) in enumerate(chunks):
+                scatter(cols(bufs[c], mks[c])[0], r0, rc)
+    # the row-side kernel starts as soon as δ exists: back to back measured slower at
+    # every rank shape (profiles/r2_bwd_overlap.md)
+    cur.wait_event(ev if ev_cols is None else ev_cols)
+    delta.record_stream(cur)
+    dk = _rows_hip(ctx, do, k, lse, delta, bufs, mks, sbuf, dsbuf, cur)
+    with _on_stream(hi, cur):  # the gathered-side grads complete on the priority stream
+        for h in handles:
+            if h is not None:
+                h.wait()
+        if dqv is None:
+            dqv = outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+    cur.wait_stream(hi)
+    for oc in outs:
+        oc.record_stream(cur)
+    dqv.record_stream(cur)
+    # consumers that can run on the priority stream (the packed [q|v] projection's
+    # weight gradient, xdot.ops.linear.LinearFn) start there as soon as the
+    # reduce-scatter lands, under the row-side kernel still running on `cur`
+    if FLAGS.wgrad_side and dqv.dtype == k.dtype:
+        dqv._xdot_ready_on = hi
+    return dk, dqv
 
 
 # ----------------------------------------------------------------------------------------
@@ -474,9 +594,9 @@ class SeqParallelAttention(torch.autograd.Function):
         the fused module folds it into the k projection's epilogue).  ``grad_on``: grad mode at the
         call (inside ``forward`` it is always off, and ``needs_input_grad`` ignores it)."""
         check_consistent(comm, "seq_parallel_attention", k, qv, H)
-        C = k.shape[-1]
-        B, R = k.shape[0], k.shape[1]
+        B, R, C = k.shape
         n, rank = comm.world_size, comm.rank
+        T = n * qv.shape[1]
         use_hip = _hip_ok(k, qv, H)
         if pending is None:
             pending = _PendingGather(comm, qv, _row_chunks(n, qv.shape[1], use_hip))
@@ -484,15 +604,12 @@ class SeqParallelAttention(torch.autograd.Function):
         prescaled = False
         fm = 0  # fp32 kernel family (XDOT_FP32_MODE), fixed at forward for the backward too
         packed_full = None  # the whole-row packed mask, when the caller packed it ahead
-        D = C // H
         if use_hip:
-            from ..ops import flash
-
-            fm = flash.fp32_code(k.dtype) if D <= 128 else 0  # wide fp32 heads are exact only
+            fm = flash.fp32_code(k.dtype) if C // H <= 128 else 0  # wide fp32 heads are exact only
             # the row side pre-multiplied by scale*log2 e once (XDOT_PRESCALE, default on): the
             # forward and both backward kernels read this same buffer and seed their score
             # accumulators instead of scaling every score (saved in place of k for backward)
-            prescaled = FLAGS.prescale and (k.numel() % 8 == 0) and k.dtype != torch.float32
+            prescaled = _prescale_rows(k)
             if prescaled and not k_prescaled:
                 k = flash.prescale(k, scale)
             if isinstance(mask, flash.PendingMask):
@@ -502,56 +619,25 @@ class SeqParallelAttention(torch.autograd.Function):
         mask = getattr(mask, "raw", mask)
         # a StructuredMask: bound to this rank's rows for the kernels' generated packed masks; the
         # torch path below gets its dense tensor, built once here
-        mask = resolve_mask(mask, B, R, n * qv.shape[1], rank, use_hip, k.device)
+        mask = resolve_mask(mask, B, R, T, rank, use_hip, k.device)
         segmented = n > 1 and (FLAGS.local_first or len(chunks) > 1)
         sbuf = dsbuf = None
         # a backward can run on this forward (grad mode is off inside Function.forward: autograd's
         # needs_input_grad, or the fused node's, says it); without one no score buffer is taken
         # (no 20 GB allocation and store pass for inference / no_grad forwards)
         need_bwd = bool(grad_on) and any(getattr(ctx, "needs_input_grad", (True,))[:2])
-        if use_hip and k.dtype == torch.float32 and need_bwd and (len(chunks) == 1 or B == 1):
-            # fp32 (exact or split): score buffer (flash.score_buffer) when it fits: the backward
-            # then reads S / dS instead of recomputing them.  One kernel over the whole gathered
-            # side (in fp32 the own-block-first segmentation hides < 5 % of a rank's forward)
-            if flash.ds_only_wanted(fm, D):  # dS-only: nothing stored by the forward
-                dsbuf = flash.ds_buffer(B, H, R, n * qv.shape[1], k.device)
-                if dsbuf is not None:
-                    segmented = False
-            else:
-                # the fused exact column pass overwrites S with dS in place: no second buffer
-                sbs = flash.score_buffers(B, H, R, n * qv.shape[1], k.device,
-                                          dsbuf=not flash.fused_cols_wanted(fm, D))
-                if sbs is not None:
-                    sbuf, dsbuf = sbs
-                    segmented = False
-        if use_hip and k.dtype == torch.float32 and D > WIDE_F32_NEEDS_SCORES and sbuf is None and need_bwd:
-            # no kernel recomputes an fp32 head this wide (three D-wide register sets) and the torch
-            # path would materialise a score matrix larger than the buffer that did not fit
-            raise RuntimeError(
-                f"xdot: training exact-fp32 attention at head dim {D} needs the flash score buffer "
-                f"({4 * flash.score_buffer_numel(B, H, R, n * qv.shape[1]) / 2**30:.1f} GiB), which does not fit "
-                f"within XDOT_FP32_SCORES_FRAC={FLAGS.fp32_scores_frac} of the free device memory: shorten the "
-                "sequence, raise XDOT_FP32_SCORES_FRAC, or run the module in bf16")
-        if not segmented:
-            if use_hip:
-                if len(chunks) > 1:  # several gather chunks, one buffer in (chunk, rank, row) order
-                    pending.wait_all()
-                    qvg = pending.permuted()
-                    mk = flash.prepare_mask_cached(mask, B, R, n * R, tag=("perm", tuple(chunks), n),
-                                                   view=_perm_cols(B, R, n, chunks))
-                else:
-                    mk = packed_full if packed_full is not None else flash.prepare_mask_cached(mask, B, R, n * R)
-                    qvg = flash.gathered_to_btc(pending.wait(0))     # (B, T, 2C), a view for B = 1
-                o, lse = flash.fwd(k, qvg[..., :C], qvg[..., C:], mk, H, scale, prescaled=prescaled, fp32_mode=fm,
-                                   sbuf=sbuf)
-                bufs, mks = [qvg], [mk]
-            else:
-                qvg = pending.wait(0)                            # (N, B, R, 2C)
-                o, lse = _ref_fwd(k, qvg[..., :C], qvg[..., C:], mask, H, scale)
-                bufs, mks = [qvg], [mask]
-        else:
+        if use_hip and k.dtype == torch.float32 and need_bwd:
+            sbuf, dsbuf, segmented = _score_buffers(k, H, T, fm, len(chunks) == 1 or B == 1, segmented)
+        if segmented:
             o, lse, bufs = _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescaled, fm)
             mks = [packed_full] if packed_full is not None else None  # backward packs its own (cached)
+        elif use_hip:
+            o, lse, qvg, mk = _whole_forward_hip(k, mask, packed_full, pending, n, H, scale, prescaled, fm, sbuf)
+            bufs, mks = [qvg], [mk]
+        else:
+            qvg = pending.wait(0)                            # (N, B, R, 2C)
+            o, lse = _forward_torch(k, qvg, mask, H, scale)
+            bufs, mks = [qvg], [mask]
         # the score buffers travel as saved tensors: autograd frees them after the backward unless
         # the graph is retained (a ctx attribute would keep 20-40 GB alive as long as the graph is
         # referenced, e.g. through the previous step's loss)
@@ -567,169 +653,13 @@ class SeqParallelAttention(torch.autograd.Function):
     @_ext.pinned
     def backward(ctx, do):
         k, o, lse, *bufs = ctx.saved_tensors
-        has_s, has_ds = getattr(ctx, "sb_kind", (False, False))
-        nsb = int(has_s) + int(has_ds)
-        sbt = bufs[len(bufs) - nsb:] if nsb else []
-        bufs = bufs[:len(bufs) - nsb]
-        comm, H, scale, chunks = ctx.comm, ctx.H, ctx.scale, ctx.chunks
-        n = comm.world_size
-        C = k.shape[-1]
-        B, R = k.shape[0], k.shape[1]
+        nsb = sum(getattr(ctx, "sb_kind", (False, False)))
+        bufs, sbt = bufs[:len(bufs) - nsb], bufs[len(bufs) - nsb:]
         do = do.contiguous()
-
-        def reduce_async(parts, out=None):  # (N, B, rc, 2C) rank-major partials -> (B, rc, 2C)
-            if n == 1:
-                return None, parts[0]
-            if out is None:
-                out = torch.empty(parts.shape[1:], dtype=parts.dtype, device=parts.device)
-            return comm.reduce_scatter(out, parts, async_op=True), out
-
         if ctx.use_hip:
-            from ..ops import flash
-
-            one = len(bufs) == 1  # one gathered buffer: natural order, or chunks permuted (B = 1)
-            mks = ctx.mks
-            if mks is None or (one and len(chunks) > 1):  # segmented forward: masks packed here (cached)
-                if one:
-                    mks = [flash.prepare_mask_cached(ctx.mask, B, R, n * R,
-                                                     tag=None if len(chunks) == 1 else ("perm", tuple(chunks), n),
-                                                     view=None if len(chunks) == 1 else _perm_cols(B, R, n, chunks))]
-                else:
-                    mks = [flash.prepare_mask_cached(ctx.mask, B, R, n * rc, tag=(r0, rc, n),
-                                                     view=_mask_cols(B, R, n, 0, n, r0, rc)) for r0, rc in chunks]
-            # δ, then two independent streams: 1) gathered-side grads on a HIGH-priority stream,
-            # followed there by their reduce-scatter(s), and 2) the row-side dk on the current
-            # stream.  2) fills the partly occupied last workgroup rounds of 1) and hides the
-            # reduce-scatter, while the priority keeps 1) (and so the collective) nearly as
-            # early as when it runs alone.  δ runs on the priority stream too, so 1) reaches
-            # the GPU first.  Per-chunk kernels (chunk c's reduce-scatter under chunk c+1's
-            # kernel) only when the chunks are separate buffers (B > 1).
-            cur = torch.cuda.current_stream(do.device)
-            # high priority so the gathered side (and its reduce-scatter) finishes early (an
-            # ordinary-priority side stream measured slower at N=1 and N=8: profiles/r2_bwd_overlap.md)
-            hi = _side_stream(do.device, -1) if _two_stream_backward(R) else cur
-            hi.wait_stream(cur)
-            handles, outs = [], []
-            gdt = k.dtype if not FLAGS.grad_fp32 else torch.float32
-            # score buffer: S -> dS in the column kernel, then dK from dS.  With a separate dS buffer
-            # S stays intact, so a second backward through a retained graph reads it again; in place
-            # (S overwritten with dS) the first backward consumes it and a second one recomputes
-            sbuf = sbt[0] if has_s else None
-            dsbuf = sbt[-1] if has_ds else None
-            if has_s and not has_ds:
-                if getattr(ctx, "sb_used", False):
-                    sbuf = None
-                ctx.sb_used = True
-            if (sbuf is None and k.dtype == torch.float32 and C // H > WIDE_F32_NEEDS_SCORES
-                    and ctx.fp32_mode == 0):
-                raise RuntimeError(
-                    f"xdot: a second backward through a retained graph of exact-fp32 attention at head dim "
-                    f"{C // H} needs the scores, which the first backward overwrote in place (no kernel "
-                    "recomputes an fp32 head this wide); set XDOT_FP32_SCORES_DS=1 with room for the "
-                    "separate dS buffer, or do not retain the graph")
-            ev_cols = None
-            with _on_stream(hi, cur):
-                delta, lse2 = flash.bwd_prep(do, o, lse, H)  # one prep pass for both kernels
-                ev = _prep_event(hi.device)
-                ev.record(hi)
-                dqv = None
-                if n > 1 and len(chunks) > 1 and B == 1:
-                    dqv = torch.empty(B, R, 2 * C, dtype=gdt, device=k.device)
-                # partials rounded once to the compute dtype in the kernel (XDOT_GRAD_FP32=1
-                # keeps fp32): half the epilogue stores and half the reduce-scatter bytes
-                if one:
-                    g = bufs[0]
-                    cargs = dict(fp32_out=FLAGS.grad_fp32, prescaled=ctx.prescaled, lse2=lse2,
-                                 fp32_mode=ctx.fp32_mode, sbuf=sbuf)
-                    if dsbuf is not None and sbuf is not None:
-                        # dQ pass (S -> dS), then the row kernel (reads dS) on `cur` concurrently
-                        # with the dV pass (reads S) here.  (The dV pass beside the dQ pass on a third
-                        # stream instead measured 54.62 vs 54.71 ms, and one rep ran 171 ms:
-                        # profiles/r6_fp32.md)
-                        dkv, _ = flash.bwd_cols(do, k, g[..., :C], g[..., C:], o, lse, mks[0], H, scale, delta,
-                                                dsbuf=dsbuf, passes=2, **cargs)
-                        ev_cols = torch.cuda.Event()
-                        ev_cols.record(hi)
-                        flash.bwd_cols(do, k, g[..., :C], g[..., C:], o, lse, mks[0], H, scale, delta,
-                                       dsbuf=dsbuf, passes=1, out_dkv=dkv, **cargs)
-                    else:
-                        # (fused exact pass: dP, dQ and dV in one kernel, S -> dS in place)
-                        fused = sbuf is not None and dsbuf is None and flash.fused_cols_wanted(ctx.fp32_mode, C // H)
-                        dkv, _ = flash.bwd_cols(do, k, g[..., :C], g[..., C:], o, lse, mks[0], H, scale, delta,
-                                                dsbuf=dsbuf, passes=4 if fused else 3, **cargs)
-                        if sbuf is not None or dsbuf is not None:  # the row kernel reads the dS this kernel wrote
-                            ev_cols = torch.cuda.Event()
-                            ev_cols.record(hi)
-                    off = 0
-                    for r0, rc in chunks:  # (chunk, rank, row) order: chunk c's ranks are contiguous
-                        part = dkv if len(chunks) == 1 else dkv[:, off:off + n * rc]
-                        off += n * rc
-                        h, oc = reduce_async(flash.btc_to_rank_major(part, n),
-                                             None if dqv is None else dqv[:, r0:r0 + rc])
-                        handles.append(h)
-                        outs.append(oc)
-                else:
-                    for c, (r0, rc) in enumerate(chunks):
-                        g = bufs[c]
-                        dkv, _ = flash.bwd_cols(do, k, g[..., :C], g[..., C:], o, lse, mks[c], H, scale, delta,
-                                                fp32_out=FLAGS.grad_fp32, prescaled=ctx.prescaled, lse2=lse2,
-                                            fp32_mode=ctx.fp32_mode)
-                        h, oc = reduce_async(flash.btc_to_rank_major(dkv, n),
-                                             None if dqv is None else dqv[:, r0:r0 + rc])
-                        handles.append(h)
-                        outs.append(oc)
-            # the row-side kernel starts as soon as δ exists: back to back measured slower at
-            # every rank shape (profiles/r2_bwd_overlap.md)
-            cur.wait_event(ev if ev_cols is None else ev_cols)
-            delta.record_stream(cur)
-            if one:
-                g = bufs[0]
-                dk = flash.bwd_rows(do, k, g[..., :C], g[..., C:], lse, delta, mks[0], H, scale,
-                                    nsplit=FLAGS.rows_split, prescaled=ctx.prescaled, fp32_mode=ctx.fp32_mode,
-                                    sbuf=sbuf, dsbuf=dsbuf)
-                if sbuf is not None:
-                    sbuf.record_stream(cur)
-                if dsbuf is not None:
-                    dsbuf.record_stream(cur)
-            else:
-                ops = _ext.ops()
-                ns = int(ops.flash_splits(B, R, n * chunks[0][1], H, True))
-                dpart = torch.empty(len(chunks) * ns, B, R, C, dtype=torch.float32, device=k.device)
-                for c in range(len(chunks)):
-                    g = bufs[c]
-                    mk = mks[c]
-                    bits, flags = (mk.bits, mk.flags) if mk is not None else (None, None)
-                    ops.flash_bwd_rows_partial(do, k, flash._kv(g[..., :C]), flash._kv(g[..., C:]), lse, delta, bits,
-                                               flags, int(H), float(scale), dpart, c * ns, ns, ctx.prescaled,
-                                               ctx.fp32_mode)
-                dk = ops.flash_bwd_rows_sum(dpart, int(H), k)
-            with _on_stream(hi, cur):  # the gathered-side grads complete on the priority stream
-                for h in handles:
-                    if h is not None:
-                        h.wait()
-                handles = []
-                if dqv is None:
-                    dqv = outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
-            cur.wait_stream(hi)
-            for oc in outs:
-                oc.record_stream(cur)
-            dqv.record_stream(cur)
-            # consumers that can run on the priority stream (the packed [q|v] projection's
-            # weight gradient, xdot.ops.linear.LinearFn) start there as soon as the
-            # reduce-scatter lands, under the row-side kernel still running on `cur`
-            if FLAGS.wgrad_side and dqv.dtype == k.dtype:
-                dqv._xdot_ready_on = hi
+            dk, dqv = _backward_hip(ctx, do, k, o, lse, bufs, sbt)
         else:
-            qvg = bufs[0]
-            dk, dq_parts, dv_parts = _ref_bwd(do, k, qvg[..., :C], qvg[..., C:], o, lse, ctx.mask, H, scale)
-            parts = torch.cat([dq_parts, dv_parts], dim=-1)
-            if k.dtype in (torch.bfloat16, torch.float16) and not FLAGS.grad_fp32:
-                parts = parts.to(k.dtype)  # the HIP path's wire dtype (one rounding per partial)
-            h, dqv = reduce_async(parts)
-            handles = [h]
-        for h in handles:
-            if h is not None:
-                h.wait()
+            dk, dqv = _backward_torch(ctx, do, k, o, lse, bufs[0])
         return dk.to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None, None
 
 
@@ -753,6 +683,19 @@ def start_gather(qv: Tensor, comm: Optional[_comm.Communicator] = None,
     return _PendingGather(comm, qv.detach(), plan, out=out)
 
 
+def _checked_mask(mask, k: Tensor, T: int):
+    """The mask argument of a ``*_packed`` entry point, validated: a :class:`StructuredMask`, a
+    (B, R, T) tensor (-> bool), a ``flash.PendingMask`` of that shape, or None."""
+    if isinstance(mask, StructuredMask):
+        mask.check(k.shape[0])
+    elif mask is not None:
+        if tuple(mask.shape) != (k.shape[0], k.shape[1], T):
+            raise ValueError(f"mask must be (B, R, T)=({k.shape[0]}, {k.shape[1]}, {T}), got {tuple(mask.shape)}")
+        if isinstance(mask, torch.Tensor):
+            mask = mask.to(torch.bool)
+    return mask
+
+
 def seq_parallel_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
                                   comm: Optional[_comm.Communicator] = None,
                                   pending: Optional["_PendingGather"] = None, k_prescaled: bool = False) -> Tensor:
@@ -764,14 +707,7 @@ def seq_parallel_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor],
     comm = comm or _comm.get_comm()
     if k.dim() != 3 or qv.dim() != 3 or qv.shape[-1] <= k.shape[-1]:
         raise ValueError("seq_parallel_attention_packed expects k (B, R, C) and qv (B, R, C + Cv)")
-    if isinstance(mask, StructuredMask):
-        mask.check(k.shape[0])
-    elif mask is not None:
-        T = qv.shape[1] * comm.world_size
-        if tuple(mask.shape) != (k.shape[0], k.shape[1], T):
-            raise ValueError(f"mask must be (B, R, T)=({k.shape[0]}, {k.shape[1]}, {T}), got {tuple(mask.shape)}")
-        if isinstance(mask, torch.Tensor):
-            mask = mask.to(torch.bool)
+    mask = _checked_mask(mask, k, qv.shape[1] * comm.world_size)
     return SeqParallelAttention.apply(k, qv, mask, num_heads, float(scale), comm, pending, bool(k_prescaled),
                                       torch.is_grad_enabled())
 

@@ -40,48 +40,16 @@ import torch
 from torch import Tensor
 
 from .. import _ext
-from ..ops.mask import StructuredMask, resolve as resolve_mask
+from ..ops import flash
+from ..ops.mask import resolve as resolve_mask
 from ..utils import comm as _comm
 from ..utils.checks import check_consistent
 from ..utils.env import FLAGS
+from ..utils.streams import _on_stream, _side_stream
+from . import _ref
+from .attention import WIDE_F32_NEEDS_SCORES, _checked_mask, _hip_ok, _prescale_rows
 
 __all__ = ["RingAttention", "ring_attention", "ring_attention_packed"]
-
-
-def _heads(x: Tensor, H: int, cdt) -> Tensor:
-    B, L, C = x.shape
-    return x.view(B, L, H, C // H).transpose(1, 2).to(cdt)
-
-
-def _ref_block_fwd(k, blk, mask, H, scale):
-    """Block partial: (o (B, H, R, dv) normalised within the block, lse (B, H, R)), compute dtype."""
-    cdt = torch.float64 if k.dtype == torch.float64 else torch.float32
-    C = k.shape[-1]
-    kh, qh, vh = _heads(k, H, cdt), _heads(blk[..., :C], H, cdt), _heads(blk[..., C:], H, cdt)
-    s = torch.matmul(kh, qh.transpose(-1, -2)) * scale
-    if mask is not None:
-        s = s.masked_fill(mask.unsqueeze(1), -float("inf"))
-    lse = torch.logsumexp(s, dim=-1)
-    p = torch.exp(s - lse.unsqueeze(-1))
-    return torch.matmul(p, vh), lse
-
-
-def _ref_block_bwd(do, k, blk, lse, delta, mask, H, scale):
-    """-> (dk (B, R, C), [dq | dv] of the block (B, R, 2C)), compute dtype."""
-    cdt = lse.dtype
-    B, R, C = k.shape
-    kh, qh, vh = _heads(k, H, cdt), _heads(blk[..., :C], H, cdt), _heads(blk[..., C:], H, cdt)
-    doh = _heads(do, H, cdt)
-    s = torch.matmul(kh, qh.transpose(-1, -2)) * scale
-    if mask is not None:
-        s = s.masked_fill(mask.unsqueeze(1), -float("inf"))
-    p = torch.exp(s - lse.unsqueeze(-1))
-    ds = p * (torch.matmul(doh, vh.transpose(-1, -2)) - delta.unsqueeze(-1)) * scale
-    merge = lambda x: x.transpose(1, 2).reshape(B, x.shape[2], -1)  # noqa: E731
-    dk = merge(torch.matmul(ds, qh))
-    dq = merge(torch.matmul(ds.transpose(-1, -2), kh))
-    dv = merge(torch.matmul(p.transpose(-1, -2), doh))
-    return dk, torch.cat([dq, dv], dim=-1)
 
 
 class _Ring:
@@ -138,6 +106,9 @@ class _Rings:
         else:
             self.rings = [_Ring(comm, blk[:, a:b].contiguous() if len(self.lanes) > 1 else blk, d)
                           for (d, a, b) in self.lanes]
+        # kernel launches per step, and the columns of the widest (what sizes the partial slots)
+        self.launches = 1 if self.merged else len(self.lanes)
+        self.width = R if self.merged else max(b - a for _, a, b in self.lanes)
         self.h = None
 
     def _views(self):
@@ -186,6 +157,128 @@ def _bidir() -> bool:
     return FLAGS.ring_bidir
 
 
+def _forward_hip(k, rings, mask, H, scale, n):
+    """-> (o, lse, the row side the kernels read (pre-scaled or not: saved for the backward), the
+    packed masks per step and launch, prescaled, fp32 kernel family)"""
+    B, R, C = k.shape
+    fm = flash.fp32_code(k.dtype)
+    prescaled = _prescale_rows(k)
+    kk = flash.prescale(k, scale) if prescaled else k.contiguous()
+    U, ns = rings.launches, flash.splits(B, R, rings.width, H)
+    # slot 0: the running (O, LSE) of the blocks seen so far (fp32), then ns slots per launch
+    # for the arriving pieces' split partials, merged into slot 0 after each step -- resident
+    # partials stay (1 + U ns) slots whatever the ring length
+    opart = torch.empty(1 + U * ns, B, R, C, dtype=torch.float32, device=k.device)
+    lpart = torch.empty(1 + U * ns, B, H, R, dtype=torch.float32, device=k.device)
+    lpart[0].fill_(-float("inf"))
+    lrun = torch.empty(B, H, R, dtype=torch.float32, device=k.device)
+    mks: List = []
+    for s in range(n):
+        rings.start(s)
+        step = []
+        for ui, (g, view, tag, _lanes) in enumerate(rings.units(s, mask, R)):
+            mk = flash.prepare_mask_cached(mask, B, R, g.shape[1], tag=tag, view=view)
+            step.append(mk)
+            flash.fwd_partial(kk, g[..., :C], g[..., C:], mk, H, scale, opart, lpart, 1 + ui * ns, ns, prescaled, fm)
+        mks.append(step)
+        if s < n - 1:
+            flash.fwd_merge(opart, lpart, lrun, H)
+            lpart[0].copy_(lrun)
+        rings.advance()
+    o, lse = flash.fwd_combine(opart, lpart, H, k)
+    return o, lse, kk, mks, prescaled, fm
+
+
+def _forward_torch(k, qv, rings, mask, H, scale, n):
+    """-> (o, lse, the mask slices per step and lane): a running log-sum-exp merge of the blocks'
+    partials, as the kernels' slot 0."""
+    B, R, C = k.shape
+    cdt = _ref.compute_dtype(k)
+    acc = torch.zeros(B, H, R, (qv.shape[-1] - C) // H, dtype=cdt, device=k.device)
+    lse = torch.full((B, H, R), -float("inf"), dtype=cdt, device=k.device)
+    mks: List = []
+    for s in range(n):
+        rings.start(s)
+        step = []
+        for (_d, a, b), ring in zip(rings.lanes, rings.rings):
+            m = _block_mask(mask, ring.src(s), R, a, b)
+            step.append(m)
+            ob, lb = _ref.block_fwd(k, ring.cur[..., :C], ring.cur[..., C:], m, H, scale)
+            new = torch.logaddexp(lse, lb)
+            live = torch.isfinite(new).unsqueeze(-1)
+            w_old = torch.where(live, torch.exp(lse - new).unsqueeze(-1), torch.zeros_like(acc[..., :1]))
+            w_new = torch.where(torch.isfinite(lb).unsqueeze(-1), torch.exp(lb - new).unsqueeze(-1),
+                                torch.zeros_like(acc[..., :1]))
+            acc = acc * w_old + _ref.heads(ob, H, cdt) * w_new
+            lse = new
+        mks.append(step)
+        rings.advance()
+    acc = torch.where(torch.isfinite(lse).unsqueeze(-1), acc, torch.full_like(acc, float("nan")))
+    return acc.transpose(1, 2).reshape(B, R, -1).to(k.dtype), lse, mks
+
+
+def _backward_hip(ctx, do, k, o, lse, rings):
+    """-> (step(s): the launches of ring step s -> the lanes' fp32 [dq | dv] contributions,
+    dk(): the row-side gradient after the last step)"""
+    H, scale, n = ctx.H, ctx.scale, ctx.comm.world_size
+    B, R, C = k.shape
+    lanes = rings.lanes
+    cur = torch.cuda.current_stream(do.device)
+    ov = FLAGS.ring_overlap
+    two = ov not in ("0", "false", "off", "no") and (ov != "auto" or -(-R // 128) * B * H >= 1024)
+    hi = _side_stream(do.device) if two else cur  # XDOT_RING_OVERLAP (utils/env.py)
+    delta = flash.bwd_delta(do, o, H)
+    nsr = flash.splits(B, R, rings.width, H, True)
+    # slot 0: running fp32 dk, then nsr column-split partial slots per launch
+    dpart = torch.empty(1 + rings.launches * nsr, B, R, C, dtype=torch.float32, device=k.device)
+    dpart[0].zero_()
+
+    def step(s):
+        # the gathered-side kernels run on the high-priority side stream, concurrently with
+        # the row-side partials here, when a block is big enough for that to pay
+        # (``hi is cur`` otherwise)
+        units = rings.units(s, None, R)
+        full, contribs = [], []
+        hi.wait_stream(cur)
+        with _on_stream(hi, cur):
+            for ui, (g, _v, _t, ls) in enumerate(units):
+                c_, _ = flash.bwd_cols(do, k, g[..., :C], g[..., C:], o, lse, ctx.mks[s][ui], H, scale, delta,
+                                       fp32_out=True, prescaled=ctx.prescaled, fp32_mode=ctx.fp32_mode)
+                full.append(c_)
+                # a merged launch covers both lanes: lane li's contribution is its row range
+                contribs.extend(c_ if len(ls) == 1 else c_[:, lanes[li][1]:lanes[li][2]] for li in ls)
+        for ui, (g, _v, _t, _ls) in enumerate(units):
+            flash.bwd_rows_partial(do, k, g[..., :C], g[..., C:], lse, delta, ctx.mks[s][ui], H, scale, dpart,
+                                   1 + ui * nsr, nsr, ctx.prescaled, ctx.fp32_mode)
+        if s < n - 1:
+            _ext.ops().sum_partials_into(dpart, dpart[0])
+        cur.wait_stream(hi)
+        for c_ in full:
+            c_.record_stream(cur)
+        return contribs
+
+    return step, lambda: flash.bwd_rows_sum(dpart, H, k)
+
+
+def _backward_torch(ctx, do, k, o, lse, rings):
+    """As :func:`_backward_hip`, in torch."""
+    C = k.shape[-1]
+    cdt = lse.dtype
+    delta = _ref.delta(do, o, ctx.H, cdt)
+    dk = torch.zeros(k.shape, dtype=cdt, device=k.device)
+
+    def step(s):
+        contribs = []
+        for li, ring in enumerate(rings.rings):
+            dkb, dq, dv = _ref.block_bwd(do, k, ring.cur[..., :C], ring.cur[..., C:], lse, delta, ctx.mks[s][li],
+                                         ctx.H, ctx.scale)
+            dk.add_(dkb)
+            contribs.append(torch.cat([dq, dv], dim=-1))
+        return contribs
+
+    return step, lambda: dk
+
+
 class RingAttention(torch.autograd.Function):
     """Ring attention on the packed gathered side ``qv = [q | v]`` (B, R, 2C) of this rank."""
 
@@ -195,87 +288,30 @@ class RingAttention(torch.autograd.Function):
         check_consistent(comm, "ring_attention", k, qv, H)
         B, R, C = k.shape
         n = comm.world_size
-        from .attention import FLASH_DTYPES, FLASH_HEAD_DIMS, WIDE_F32_NEEDS_SCORES
-
         # (the ring has no score buffer: exact fp32 heads past 256 run the torch path)
-        use_hip = (_ext.use_hip(k) and k.dtype in FLASH_DTYPES and qv.shape[-1] == 2 * C
-                   and C // H in FLASH_HEAD_DIMS
-                   and not (k.dtype == torch.float32 and C // H > WIDE_F32_NEEDS_SCORES))
+        use_hip = _hip_ok(k, qv, H) and not (k.dtype == torch.float32 and C // H > WIDE_F32_NEEDS_SCORES)
         # a StructuredMask: bound to this rank's rows (packed masks generated per block), or its
         # dense tensor, built once, for the torch path
         mask = resolve_mask(mask, B, R, n * R, comm.rank, use_hip, k.device)
         qv = qv.contiguous()
         rings = _Rings(comm, qv, _bidir())
-        L = len(rings.lanes)
-        mks: List = []  # per step, per lane
-        prescaled = False
-        fm = 0
+        prescaled, fm = False, 0
         if use_hip:
-            from ..ops import flash
-
-            ops = _ext.ops()
-            fm = flash.fp32_code(k.dtype)
-            prescaled = FLAGS.prescale and (k.numel() % 8 == 0) and k.dtype != torch.float32
-            kk = flash.prescale(k, scale) if prescaled else k.contiguous()
-            U = 1 if rings.merged else L  # kernel launches per step
-            ns = int(ops.flash_splits(B, R, R if rings.merged else max(b - a for _, a, b in rings.lanes), H, False))
-            # slot 0: the running (O, LSE) of the blocks seen so far (fp32), then ns slots per launch
-            # for the arriving pieces' split partials, merged into slot 0 after each step -- resident
-            # partials stay (1 + U ns) slots whatever the ring length
-            opart = torch.empty(1 + U * ns, B, R, C, dtype=torch.float32, device=k.device)
-            lpart = torch.empty(1 + U * ns, B, H, R, dtype=torch.float32, device=k.device)
-            lpart[0].fill_(-float("inf"))
-            lrun = torch.empty(B, H, R, dtype=torch.float32, device=k.device)
-            for s in range(n):
-                rings.start(s)
-                step = []
-                for ui, (g, view, tag, _lanes) in enumerate(rings.units(s, mask, R)):
-                    mk = flash.prepare_mask_cached(mask, B, R, g.shape[1], tag=tag, view=view)
-                    step.append(mk)
-                    bits, flags = (mk.bits, mk.flags) if mk is not None else (None, None)
-                    ops.flash_fwd_partial(kk, flash._kv(g[..., :C]), flash._kv(g[..., C:]), bits, flags, int(H),
-                                          float(scale), opart, lpart, 1 + ui * ns, ns, prescaled, fm)
-                mks.append(step)
-                if s < n - 1:
-                    ops.flash_fwd_merge(opart, lpart, lrun, int(H))
-                    lpart[0].copy_(lrun)
-                rings.advance()
-            o, lse = ops.flash_fwd_combine(opart, lpart, int(H), k)
-            ctx.save_for_backward(kk, qv, o, lse)
+            o, lse, k, mks, prescaled, fm = _forward_hip(k, rings, mask, H, scale, n)
         else:
-            cdt = torch.float64 if k.dtype == torch.float64 else torch.float32
-            acc = torch.zeros(B, H, R, (qv.shape[-1] - C) // H, dtype=cdt, device=k.device)
-            lse = torch.full((B, H, R), -float("inf"), dtype=cdt, device=k.device)
-            for s in range(n):
-                rings.start(s)
-                step = []
-                for (_d, a, b), ring in zip(rings.lanes, rings.rings):
-                    m = _block_mask(mask, ring.src(s), R, a, b)
-                    step.append(m)
-                    ob, lb = _ref_block_fwd(k, ring.cur, m, H, scale)
-                    new = torch.logaddexp(lse, lb)
-                    live = torch.isfinite(new).unsqueeze(-1)
-                    w_old = torch.where(live, torch.exp(lse - new).unsqueeze(-1), torch.zeros_like(acc[..., :1]))
-                    w_new = torch.where(torch.isfinite(lb).unsqueeze(-1), torch.exp(lb - new).unsqueeze(-1),
-                                        torch.zeros_like(acc[..., :1]))
-                    acc = acc * w_old + torch.nan_to_num(ob, nan=0.0) * w_new
-                    lse = new
-                mks.append(step)
-                rings.advance()
-            acc = torch.where(torch.isfinite(lse).unsqueeze(-1), acc, torch.full_like(acc, float("nan")))
-            o = acc.transpose(1, 2).reshape(B, R, -1).to(k.dtype)
-            ctx.save_for_backward(k, qv, o, lse)
+            o, lse, mks = _forward_torch(k, qv, rings, mask, H, scale, n)
+        ctx.save_for_backward(k, qv, o, lse)
         ctx.mks, ctx.H, ctx.scale, ctx.comm, ctx.use_hip, ctx.prescaled = mks, H, scale, comm, use_hip, prescaled
-        ctx.fp32_mode, ctx.bidir = fm, L > 1
+        ctx.fp32_mode, ctx.bidir = fm, len(rings.lanes) > 1
         return o
 
     @staticmethod
     @_ext.pinned
     def backward(ctx, do):
         k, qv, o, lse = ctx.saved_tensors
-        comm, H, scale = ctx.comm, ctx.H, ctx.scale
+        comm = ctx.comm
         n = comm.world_size
-        B, R, C = k.shape
+        B = k.shape[0]
         do = do.contiguous()
         rings = _Rings(comm, qv, ctx.bidir)
         lanes = rings.lanes
@@ -288,59 +324,10 @@ class RingAttention(torch.autograd.Function):
             if n > 1 else None
         acc_h = None
         accs = None
-        if ctx.use_hip:
-            from ..ops import flash
-
-            from .attention import _side_stream
-
-            ops = _ext.ops()
-            cur = torch.cuda.current_stream(do.device)
-            ov = FLAGS.ring_overlap
-            two = ov not in ("0", "false", "off", "no") and (ov != "auto" or -(-R // 128) * B * H >= 1024)
-            hi = _side_stream(do.device) if two else cur  # XDOT_RING_OVERLAP (utils/env.py)
-            delta = flash.bwd_delta(do, o, H)
-            U = 1 if rings.merged else len(lanes)  # kernel launches per step
-            nsr = int(ops.flash_splits(B, R, R if rings.merged else max(b - a for _, a, b in lanes), H, True))
-            # slot 0: running fp32 dk, then nsr column-split partial slots per launch
-            dpart = torch.empty(1 + U * nsr, B, R, C, dtype=torch.float32, device=k.device)
-            dpart[0].zero_()
-        else:
-            cdt = lse.dtype
-            delta = (_heads(do, H, cdt) * _heads(o, H, cdt)).sum(-1)
-            dk = torch.zeros(B, R, C, dtype=cdt, device=k.device)
+        step, dk = (_backward_hip if ctx.use_hip else _backward_torch)(ctx, do, k, o, lse, rings)
         for s in range(n):
             rings.start(s)
-            contribs = []
-            if ctx.use_hip:
-                # the gathered-side kernels run on the high-priority side stream, concurrently with
-                # the row-side partials here, when a block is big enough for that to pay
-                # (``hi is cur`` otherwise)
-                units = rings.units(s, None, R)
-                full = []
-                hi.wait_stream(cur)
-                with torch.cuda.stream(hi):
-                    for ui, (g, _v, _t, ls) in enumerate(units):
-                        c_, _ = flash.bwd_cols(do, k, g[..., :C], g[..., C:], o, lse, ctx.mks[s][ui], H, scale, delta,
-                                               fp32_out=True, prescaled=ctx.prescaled, fp32_mode=ctx.fp32_mode)
-                        full.append(c_)
-                        # a merged launch covers both lanes: lane li's contribution is its row range
-                        contribs.extend(c_ if len(ls) == 1 else c_[:, lanes[li][1]:lanes[li][2]] for li in ls)
-                for ui, (g, _v, _t, _ls) in enumerate(units):
-                    mk = ctx.mks[s][ui]
-                    bits, flags = (mk.bits, mk.flags) if mk is not None else (None, None)
-                    ops.flash_bwd_rows_partial(do, k, flash._kv(g[..., :C]), flash._kv(g[..., C:]), lse, delta, bits,
-                                               flags, int(H), float(scale), dpart, 1 + ui * nsr, nsr, ctx.prescaled,
-                                               ctx.fp32_mode)
-                if s < n - 1:
-                    ops.sum_partials_into(dpart, dpart[0])
-                cur.wait_stream(hi)
-                for c_ in full:
-                    c_.record_stream(cur)
-            else:
-                for li, ring in enumerate(rings.rings):
-                    dkb, c_ = _ref_block_bwd(do, k, ring.cur, lse, delta, ctx.mks[s][li], H, scale)
-                    dk += dkb
-                    contribs.append(c_)
+            contribs = step(s)
             # each accumulator arrives from the previous rank of its lane one hop behind its block
             if acc_h is not None:
                 acc_h.wait()
@@ -355,9 +342,7 @@ class RingAttention(torch.autograd.Function):
             acc_h.wait()
             accs = acc_in
         dqv = accs[0] if len(accs) == 1 else torch.cat(accs, dim=1)
-        if ctx.use_hip:
-            dk = ops.flash_bwd_rows_sum(dpart, int(H), k)
-        return dk.to(k.dtype), dqv.to(k.dtype), None, None, None, None
+        return dk().to(k.dtype), dqv.to(k.dtype), None, None, None, None
 
 
 def ring_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
@@ -367,13 +352,7 @@ def ring_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor], num_hea
     comm = comm or _comm.get_comm()
     if k.dim() != 3 or qv.dim() != 3 or qv.shape[-1] <= k.shape[-1] or qv.shape[:2] != k.shape[:2]:
         raise ValueError("ring_attention expects k (B, R, C) and qv (B, R, C + Cv) with equal R")
-    if isinstance(mask, StructuredMask):
-        mask.check(k.shape[0])
-    elif mask is not None:
-        T = qv.shape[1] * comm.world_size
-        if tuple(mask.shape) != (k.shape[0], k.shape[1], T):
-            raise ValueError(f"mask must be (B, R, T)=({k.shape[0]}, {k.shape[1]}, {T}), got {tuple(mask.shape)}")
-        mask = mask.to(torch.bool)
+    mask = _checked_mask(mask, k, qv.shape[1] * comm.world_size)
     return RingAttention.apply(k, qv, mask, num_heads, float(scale), comm)
 
 
