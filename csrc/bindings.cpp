@@ -893,23 +893,23 @@ TORCH_LIBRARY(xdot, m) {
   m.def("softmax_bwd(Tensor y, Tensor dy, float scale) -> Tensor");
   m.def("mask_pack(Tensor mask) -> (Tensor, Tensor, Tensor)");
   m.def("mask_gen(int B, int R, int T, bool causal, int window, int row_offset, Tensor? lengths, Tensor segs, Tensor? doc_starts=None) -> (Tensor, Tensor, Tensor)");
-  m.def("flash_fwd(Tensor rows, Tensor kc, Tensor vc, Tensor? bits, Tensor? flags, int H, float scale, int nsplit=0, bool prescaled=False, int fp32_mode=0, Tensor(a!)? sbuf=None) -> (Tensor, Tensor)");
+  m.def("flash_fwd(Tensor rows, Tensor kc, Tensor vc, Tensor? bits, Tensor? flags, int H, float scale, int nsplit=0, bool prescaled=False, int fp32_mode=0, Tensor(a!)? sbuf=None, int Hg=0) -> (Tensor, Tensor)");
   m.def("flash_bwd_cols(Tensor dout, Tensor rows, Tensor kc, Tensor vc, Tensor out, Tensor lse, Tensor? bits, "
         "Tensor? flags, int H, float scale, Tensor? delta=None, bool fp32_out=True, bool prescaled=False, "
         "Tensor? lse2=None, int fp32_mode=0, Tensor(a!)? sbuf=None, Tensor(b!)? dsbuf=None, int passes=3, "
-        "Tensor(c!)? dkv_out=None) -> (Tensor, Tensor)");
+        "Tensor(c!)? dkv_out=None, int Hg=0) -> (Tensor, Tensor)");
   m.def("flash_bwd_prep(Tensor dout, Tensor out, Tensor lse, int H) -> (Tensor, Tensor)");
   m.def("flash_bwd_delta(Tensor dout, Tensor out, int H) -> Tensor");
   m.def("sum_partials(Tensor part, ScalarType out_dtype) -> Tensor");
   m.def("flash_splits(int B, int R, int T, int H, bool rows_kernel) -> int");
   m.def("flash_fwd_plan(int B, int R, int T, int H, int D, ScalarType dtype, int fp32_mode, bool sbuf, int nsplit) -> int[]");
   m.def("flash_cols_plan(int B, int R, int T, int H, int D, ScalarType dtype, int fp32_mode, bool sbuf, bool dsbuf, "
-        "int passes, bool prescaled, bool fp32_out) -> int[]");
+        "int passes, bool prescaled, bool fp32_out, int Hg=0) -> int[]");
   m.def("flash_fwd_partial(Tensor rows, Tensor kc, Tensor vc, Tensor? bits, Tensor? flags, int H, float scale, "
-        "Tensor(a!) opart, Tensor(b!) lpart, int sp0, int nsplit, bool prescaled=False, int fp32_mode=0) -> ()");
+        "Tensor(a!) opart, Tensor(b!) lpart, int sp0, int nsplit, bool prescaled=False, int fp32_mode=0, int Hg=0) -> ()");
   m.def("flash_fwd_combine(Tensor opart, Tensor lpart, int H, Tensor like) -> (Tensor, Tensor)");
   m.def("flash_bwd_rows_partial(Tensor dout, Tensor rows, Tensor kc, Tensor vc, Tensor lse, Tensor delta, Tensor? bits, "
-        "Tensor? flags, int H, float scale, Tensor(a!) dpart, int sp0, int nsplit, bool prescaled=False, int fp32_mode=0) -> ()");
+        "Tensor? flags, int H, float scale, Tensor(a!) dpart, int sp0, int nsplit, bool prescaled=False, int fp32_mode=0, int Hg=0) -> ()");
   m.def("flash_bwd_rows_sum(Tensor dpart, int H, Tensor like) -> Tensor");
   m.def("flash_fwd_merge(Tensor(a!) opart, Tensor lpart, Tensor(b!) lrun, int H) -> ()");
   m.def("sum_partials_into(Tensor part, Tensor(a!) out) -> ()");
@@ -919,7 +919,7 @@ TORCH_LIBRARY(xdot, m) {
         "Tensor(d!)[] grad_out) -> ()");
   m.def("flash_bwd_rows(Tensor dout, Tensor rows, Tensor kc, Tensor vc, Tensor lse, Tensor delta, Tensor? bits, "
         "Tensor? flags, int H, float scale, int nsplit=0, bool prescaled=False, int fp32_mode=0, Tensor? sbuf=None, "
-        "Tensor? dsbuf=None) -> Tensor");
+        "Tensor? dsbuf=None, int Hg=0) -> Tensor");
   m.def("flash_prescale(Tensor x, float scale) -> Tensor");
   m.def("rope_table(int R, int D, int offset, Tensor inv_freq) -> (Tensor, Tensor)");
   m.def("rope_apply(Tensor x, Tensor cos, Tensor sin, int H, bool inverse, float alpha, Tensor(a!) out) -> ()");

@@ -14,31 +14,42 @@ using namespace xdot::bind;
 using namespace xdot::fa;
 using OptT = c10::optional<at::Tensor>;
 
-struct FlashGeom { int64_t B, R, C, T, D, ld; };
+// C: row-side columns H*D; Cg: gathered-side columns Hg*D (Hg = H / G gathered heads, G row heads each)
+struct FlashGeom { int64_t B, R, C, T, D, ld, Cg, G; };
 
 // rows: contiguous (B, R, C).  kc / vc: (B, T, C) views with unit inner stride and a common
 // row stride `ld` (C for separate tensors, 2C for the two halves of a packed [q | v]).
 // `bits`: the kt-major (B, NKT, R) words, or with colmajor the (B, NRT, Tpad) words of the
-// backward column kernel (mask_pack's third output)
+// backward column kernel (mask_pack's third output).  Hg: gathered heads (0: H); Hg < H is grouped-query
+// attention, row head h reads gathered head h / (H / Hg)
 FlashGeom flash_check(const at::Tensor& rows, const at::Tensor& kc, const at::Tensor& vc, int64_t H, const OptT& bits,
-                      const OptT& flags, bool colmajor = false) {
+                      const OptT& flags, bool colmajor = false, int64_t Hg = 0) {
   TORCH_CHECK(rows.is_cuda() && kc.is_cuda() && vc.is_cuda(), "xdot.flash: GPU tensors required");
   TORCH_CHECK(rows.is_contiguous(), "xdot.flash: rows must be contiguous");
   TORCH_CHECK(rows.scalar_type() == kc.scalar_type() && rows.scalar_type() == vc.scalar_type(), "xdot.flash: dtype mismatch");
   TORCH_CHECK(rows.scalar_type() == at::kBFloat16 || rows.scalar_type() == at::kHalf || rows.scalar_type() == at::kFloat,
               "xdot.flash: bf16/fp16/fp32 only");
   TORCH_CHECK(rows.dim() == 3 && kc.dim() == 3 && vc.sizes() == kc.sizes(), "xdot.flash: rows (B,R,C), cols (B,T,C)");
-  FlashGeom g{rows.size(0), rows.size(1), rows.size(2), kc.size(1), 0, kc.stride(1)};
-  TORCH_CHECK(kc.size(0) == g.B && kc.size(2) == g.C, "xdot.flash: batch / feature mismatch");
+  FlashGeom g{rows.size(0), rows.size(1), rows.size(2), kc.size(1), 0, kc.stride(1), 0, 1};
+  TORCH_CHECK(H > 0 && g.C % H == 0, "xdot.flash: C not divisible by heads");
+  const int64_t hg = Hg > 0 ? Hg : H;
+  TORCH_CHECK(hg <= H && H % hg == 0, "xdot.flash: the heads H = ", H, " must be a multiple of the gathered heads Hg = ", hg);
+  g.D = g.C / H;
+  g.Cg = hg * g.D;
+  g.G = H / hg;
+  TORCH_CHECK(kc.size(0) == g.B, "xdot.flash: batch mismatch");
+  TORCH_CHECK(kc.size(2) == g.Cg, "xdot.flash: the gathered side must have Hg * D = ", g.Cg, " columns (Hg = ", hg,
+              ", D = ", g.D, "), got ", kc.size(2));
+  TORCH_CHECK(g.G == 1 || H <= 1024, "xdot.flash: grouped gathered heads take at most 1024 heads");
+  TORCH_CHECK(g.G == 1 || (rows.scalar_type() != at::kFloat && g.D <= 128),
+              "xdot.flash: grouped gathered heads (Hg < H) run in the 16-bit kernels with head dim <= 128 only");
   TORCH_CHECK(g.T > 0, "xdot.flash: empty key side");
   for (const at::Tensor* t : {&kc, &vc}) {
     TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == g.ld && (g.B == 1 || t->stride(0) == g.T * g.ld),
                 "xdot.flash: key/value side must be (B, T, C) rows with a common row stride");
-    TORCH_CHECK((g.B - 1) * g.T * g.ld + (g.T - 1) * g.ld + g.C <= avail_elems(*t), "xdot.flash: key/value out of bounds");
+    TORCH_CHECK((g.B - 1) * g.T * g.ld + (g.T - 1) * g.ld + g.Cg <= avail_elems(*t), "xdot.flash: key/value out of bounds");
   }
-  TORCH_CHECK(g.ld % 8 == 0 && g.ld >= g.C, "xdot.flash: row stride must be a multiple of 8 elements");
-  TORCH_CHECK(H > 0 && g.C % H == 0, "xdot.flash: C not divisible by heads");
-  g.D = g.C / H;
+  TORCH_CHECK(g.ld % 8 == 0 && g.ld >= g.Cg, "xdot.flash: row stride must be a multiple of 8 elements");
   TORCH_CHECK(g.D == 32 || g.D == 64 || g.D == 96 || g.D == 128 || g.D == 160 || g.D == 192 || g.D == 256 ||
                   g.D == 384,
               "xdot.flash: head dim must be 32/64/96/128 or (flash_wide.hip) 160/192/256/384");
@@ -62,7 +73,7 @@ FlashGeom flash_check(const at::Tensor& rows, const at::Tensor& kc, const at::Te
 // the geometry of a plan query: no tensors
 FlashGeom query_geom(int64_t B, int64_t R, int64_t T, int64_t H, int64_t D) {
   TORCH_CHECK(B > 0 && R > 0 && T > 0 && H > 0 && D > 0 && T < (1LL << 31) && R < (1LL << 31), "xdot.flash: plan query shape");
-  return FlashGeom{B, R, H * D, T, D, H * D};
+  return FlashGeom{B, R, H * D, T, D, H * D, H * D, 1};
 }
 
 // fp32 score buffer (flash_f32.hip exact, flash_x3.hip split): (B*H, ceil(R/32), ceil(T/32)) blocks
@@ -168,6 +179,8 @@ A flash_args(const FlashGeom& g, const at::Tensor& rows, const at::Tensor& kc, c
   a.mflags = hb ? flags->data_ptr<uint8_t>() : nullptr;
   a.B = (int)g.B; a.H = (int)H; a.R = (int)g.R; a.T = (int)g.T; a.scale = (float)scale;
   a.ldkv = g.ld;
+  a.G = g.G > 1 ? (int)g.G : 0;
+  a.gmul = g.G > 1 ? (int)(((1 << 20) + g.G - 1) / g.G) : 0;
   a.prescaled = prescaled ? 1 : 0; a.fp32_mode = (int)fp32_mode;
   return a;
 }
@@ -230,9 +243,9 @@ std::tuple<at::Tensor, at::Tensor> bwd_prep(const at::Tensor& dout, const at::Te
 // ---- ops ------------------------------------------------------------------------------------
 std::tuple<at::Tensor, at::Tensor> flash_fwd(const at::Tensor& rows, const at::Tensor& kc, const at::Tensor& vc,
                                              const OptT& bits, const OptT& flags, int64_t H, double scale, int64_t nsplit,
-                                             bool prescaled, int64_t fp32_mode, const OptT& sbuf) {
+                                             bool prescaled, int64_t fp32_mode, const OptT& sbuf, int64_t Hg) {
   Range rr_("xdot.flash_fwd");
-  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags);
+  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags, false, Hg);
   float* sb = sbuf_ptr(sbuf, g, H, rows, fp32_mode, "xdot.flash_fwd");
   auto out = at::empty_like(rows);
   const auto f32 = rows.options().dtype(at::kFloat);
@@ -271,9 +284,9 @@ std::tuple<at::Tensor, at::Tensor> flash_bwd_cols(const at::Tensor& dout, const 
                                                   const OptT& bits, const OptT& flags, int64_t H, double scale,
                                                   const OptT& delta_in, bool fp32_out, bool prescaled, const OptT& lse2_in,
                                                   int64_t fp32_mode, const OptT& sbuf, const OptT& dsbuf, int64_t passes,
-                                                  const OptT& dkv_out) {
+                                                  const OptT& dkv_out, int64_t Hg) {
   Range rr_("xdot.flash_bwd_cols");
-  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags, /*colmajor=*/true);
+  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags, /*colmajor=*/true, Hg);
   float* sb = sbuf_ptr(sbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_cols");
   float* dsb = sbuf_ptr(dsbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_cols (dS buffer)");
   // a dS buffer alone: dS-only mode (the recomputing column kernel stores dS, D <= 128)
@@ -285,14 +298,15 @@ std::tuple<at::Tensor, at::Tensor> flash_bwd_cols(const at::Tensor& dout, const 
   const auto f32 = rows.options().dtype(at::kFloat);
   // dkv_out: the other pass's output, completed in place
   at::Tensor dkv = dkv_out.has_value() && dkv_out->defined() ? *dkv_out
-                       : at::empty({g.B, g.T, 2 * g.C}, fp32_out ? kc.options().dtype(at::kFloat) : kc.options());
-  TORCH_CHECK(dkv.is_contiguous() && dkv.sizes() == at::IntArrayRef({g.B, g.T, 2 * g.C}) &&
+                       : at::empty({g.B, g.T, 2 * g.Cg}, fp32_out ? kc.options().dtype(at::kFloat) : kc.options());
+  TORCH_CHECK(dkv.is_contiguous() && dkv.sizes() == at::IntArrayRef({g.B, g.T, 2 * g.Cg}) &&
                   dkv.scalar_type() == (fp32_out ? at::kFloat : kc.scalar_type()) && dkv.device() == rows.device(),
-              "xdot.flash_bwd_cols: dkv_out");
+              "xdot.flash_bwd_cols: dkv_out must be (B, T, 2 * Hg * D) = (", g.B, ", ", g.T, ", ", 2 * g.Cg,
+              ") in the output dtype");
   const bool have_delta = delta_in.has_value() && delta_in->defined();
   if (have_delta) check_bhr(*delta_in, g.B, H, g.R, rows.device(), "xdot.flash_bwd_cols: delta");
   at::Tensor delta = have_delta ? *delta_in : at::empty({g.B, H, g.R}, f32);
-  a.dkc = dkv.data_ptr(); a.dvc = static_cast<char*>(dkv.data_ptr()) + g.C * dkv.element_size(); a.ldg = 2 * g.C;
+  a.dkc = dkv.data_ptr(); a.dvc = static_cast<char*>(dkv.data_ptr()) + g.Cg * dkv.element_size(); a.ldg = 2 * g.Cg;
   a.delta = delta.data_ptr<float>();
   // lse2 = lse * log2 e: given (from flash_bwd_prep, together with δ), or one prep pass here
   const bool have_lse2 = have_delta && lse2_in.has_value() && lse2_in->defined();
@@ -319,8 +333,8 @@ std::tuple<at::Tensor, at::Tensor> flash_bwd_cols(const at::Tensor& dout, const 
   } else {
     a.csq = run_q && p.sq > 1 ? p.sq : 0;
     a.csv = run_v && p.sv > 1 ? p.sv : 0;
-    if (a.csq) cpq = at::empty({a.csq, g.B, g.T, g.C}, f32);
-    if (a.csv) cpv = at::empty({a.csv, g.B, g.T, g.C}, f32);
+    if (a.csq) cpq = at::empty({a.csq, g.B, g.T, g.Cg}, f32);
+    if (a.csv) cpv = at::empty({a.csv, g.B, g.T, g.Cg}, f32);
   }
   a.cpq = cpq.defined() ? cpq.data_ptr<float>() : nullptr;
   a.cpv = cpv.defined() ? cpv.data_ptr<float>() : nullptr;
@@ -331,12 +345,14 @@ std::tuple<at::Tensor, at::Tensor> flash_bwd_cols(const at::Tensor& dout, const 
 // [sq, sv, heavy, whole, rem, split]: what flash_bwd_cols would choose for this shape on the current device
 std::vector<int64_t> flash_cols_plan(int64_t B, int64_t R, int64_t T, int64_t H, int64_t D, at::ScalarType dtype,
                                      int64_t fp32_mode, bool sbuf, bool dsbuf, int64_t passes, bool prescaled,
-                                     bool fp32_out) {
+                                     bool fp32_out, int64_t Hg) {
   const FlashGeom g = query_geom(B, R, T, H, D);
+  TORCH_CHECK(Hg >= 0 && (Hg == 0 || H % Hg == 0), "xdot.flash_cols_plan: H must be a multiple of Hg");
   static float present;  // the planner only asks whether the buffers exist
   xdot::fa::BwdArgs a{};
   a.B = (int)B; a.H = (int)H; a.R = (int)R; a.T = (int)T;
   a.prescaled = prescaled ? 1 : 0; a.fp32_mode = (int)fp32_mode;
+  a.G = Hg > 0 && Hg < H ? (int)(H / Hg) : 0;
   set_cols_mode(a, dtype, D, sbuf ? &present : nullptr, dsbuf ? &present : nullptr, passes, fp32_out);
   const ColsPlan p = plan_cols(a, dt_code(dtype), (int)g.D);
   return {p.sq, p.sv, p.heavy, p.whole, p.rem, p.split};
@@ -478,9 +494,9 @@ std::tuple<at::Tensor, at::Tensor> flash_bwd_prep(const at::Tensor& dout, const 
 at::Tensor flash_bwd_rows(const at::Tensor& dout, const at::Tensor& rows, const at::Tensor& kc, const at::Tensor& vc,
                           const at::Tensor& lse, const at::Tensor& delta, const OptT& bits, const OptT& flags, int64_t H,
                           double scale, int64_t nsplit, bool prescaled, int64_t fp32_mode, const OptT& sbuf,
-                          const OptT& dsbuf) {
+                          const OptT& dsbuf, int64_t Hg) {
   Range rr_("xdot.flash_bwd_rows");
-  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags);
+  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags, false, Hg);
   float* sb = sbuf_ptr(sbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_rows");
   float* dsb = sbuf_ptr(dsbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_rows (dS buffer)");
   TORCH_CHECK(!dsb || sb || g.D <= 128, "xdot.flash_bwd_rows: a dS buffer without the score buffer needs D <= 128");
@@ -509,9 +525,9 @@ int64_t flash_splits(int64_t B, int64_t R, int64_t T, int64_t H, bool rows_kerne
 // forward over this column chunk into partial slots [sp0, sp0 + nsplit) of opart / lpart
 void flash_fwd_partial(const at::Tensor& rows, const at::Tensor& kc, const at::Tensor& vc, const OptT& bits,
                        const OptT& flags, int64_t H, double scale, at::Tensor& opart, at::Tensor& lpart, int64_t sp0,
-                       int64_t nsplit, bool prescaled, int64_t fp32_mode) {
+                       int64_t nsplit, bool prescaled, int64_t fp32_mode, int64_t Hg) {
   Range rr_("xdot.flash_fwd_partial");
-  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags);
+  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags, false, Hg);
   TORCH_CHECK(sp0 >= 0 && nsplit >= 1, "xdot.flash_fwd_partial: slots");
   const int ns = pick_split(1, g.T, 1, nsplit);  // clamps nsplit to the column tiles
   check_part(opart, sp0 + ns, g.B * g.R * g.C, "opart");
@@ -569,9 +585,9 @@ void flash_fwd_merge(at::Tensor& opart, const at::Tensor& lpart, at::Tensor& lru
 void flash_bwd_rows_partial(const at::Tensor& dout, const at::Tensor& rows, const at::Tensor& kc, const at::Tensor& vc,
                             const at::Tensor& lse, const at::Tensor& delta, const OptT& bits, const OptT& flags, int64_t H,
                             double scale, at::Tensor& dpart, int64_t sp0, int64_t nsplit, bool prescaled,
-                            int64_t fp32_mode) {
+                            int64_t fp32_mode, int64_t Hg) {
   Range rr_("xdot.flash_bwd_rows_partial");
-  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags);
+  const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags, false, Hg);
   check_bhr(delta, g.B, H, g.R, rows.device(), "xdot.flash_bwd_rows_partial: delta");
   TORCH_CHECK(sp0 >= 0 && nsplit >= 1, "xdot.flash_bwd_rows_partial: slots");
   const int ns = pick_split(1, g.T, 1, nsplit);

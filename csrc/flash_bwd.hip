@@ -136,8 +136,9 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_rows_kernel(BwdArgs a) {
   const int ldb = a.ldkv * 2;
   ImgDma<D> dma;
   dma.init(wave, lane, ldb);
-  const char* kcb = reinterpret_cast<const char*>(reinterpret_cast<const T16*>(a.kc) + h * D + (int64_t)b * a.T * a.ldkv);
-  const char* vcb = reinterpret_cast<const char*>(reinterpret_cast<const T16*>(a.vc) + h * D + (int64_t)b * a.T * a.ldkv);
+  const int hg = a.G > 1 ? (h * a.gmul) >> 20 : h;  // gathered head h / G of this row head (grouped-query attention)
+  const char* kcb = reinterpret_cast<const char*>(reinterpret_cast<const T16*>(a.kc) + hg * D + (int64_t)b * a.T * a.ldkv);
+  const char* vcb = reinterpret_cast<const char*>(reinterpret_cast<const T16*>(a.vc) + hg * D + (int64_t)b * a.T * a.ldkv);
   const uint64_t* mwg = a.mbits ? a.mbits + (int64_t)b * NKT * a.R + rb * 128 : nullptr;  // + kt * R per tile
   const uint32_t moff = (uint32_t)(min((wave & 1) * 64 + lane, a.R - 1 - rb * 128) * 8 + (wave >> 1) * 4);
   const int NKT4 = (NKT + 3) & ~3;
@@ -316,7 +317,13 @@ template <int D, int NB = 0> struct ColsCfg {
   static constexpr int NG = 2 * IPW + 2;  // DMAs per wave per tile
 };
 
-template <int DT, int D, int WPS = 2, int NB = 0, bool PS = false>
+//
+// GQ (grouped-query attention, BwdArgs::G > 1): one workgroup per (b, GATHERED head, column block).  Its
+// q / v fragments are loaded once and it sweeps the row tiles of the group's G row heads back to
+// back into the same dq / dv accumulators: tile p of the G * NRT long sequence is row tile p % NRT
+// of row head hg * G + p / NRT.  The ring stage follows p (NRT may be odd); the mask tile follows
+// the row tile (all heads share the mask).
+template <int DT, int D, int WPS = 2, int NB = 0, bool PS = false, bool GQ = false>
 __global__ __launch_bounds__(256, WPS) void flash_bwd_cols_kernel(BwdArgs a) {
   using T16 = typename dt_traits<DT>::T;
   using CF = ColsCfg<D, NB>;
@@ -329,7 +336,9 @@ __global__ __launch_bounds__(256, WPS) void flash_bwd_cols_kernel(BwdArgs a) {
   const int ncb = (a.T + 127) / 128;
   const int lin = xcd_remap(blockIdx.x, gridDim.x);
   const int cb = lin % ncb, bh = lin / ncb;
-  const int b = bh / a.H, h = bh % a.H;
+  // hg: gathered head; h: its (first) row head
+  const int G = GQ ? a.G : 1, Hg = GQ ? a.H / a.G : a.H;
+  const int b = bh / Hg, hg = bh % Hg, h = hg * G;
   const int C = a.H * D;
   const int NKT = (a.T + 63) / 64;
   const int NRB32 = (a.R + 31) / 32;
@@ -341,7 +350,7 @@ __global__ __launch_bounds__(256, WPS) void flash_bwd_cols_kernel(BwdArgs a) {
 
   u32x4 qf[KS], vf[KS];
   {
-    const int64_t off = col_off(col_ok ? col : 0, b, a.T, a.ldkv) + h * D + 8 * hf;
+    const int64_t off = col_off(col_ok ? col : 0, b, a.T, a.ldkv) + hg * D + 8 * hf;
     const T16* pq = reinterpret_cast<const T16*>(a.kc) + off;
     const T16* pv = reinterpret_cast<const T16*>(a.vc) + off;
 #pragma unroll
@@ -375,20 +384,34 @@ __global__ __launch_bounds__(256, WPS) void flash_bwd_cols_kernel(BwdArgs a) {
   const int NRT64 = (a.R + 63) / 64, TPAD = (a.T + 127) / 128 * 128;
   const uint64_t* mb = a.mbits ? a.mbits + (int64_t)b * NRT64 * TPAD + cb * 128 : nullptr;
 
-  auto issue = [&](int rt) {
-    char* st = smem + (rt % NBUF) * CF::STAGE;
+  // tiles of the sweep: NRT row tiles of each of the G row heads
+  const int NT = GQ ? G * NRT : NRT;
+  int i_rt = 0, i_j = 0;  // GQ: (row tile, head of the group) of the next tile issued (in order)
+  auto issue = [&](int p) {
+    char* st = smem + (p % NBUF) * CF::STAGE;
+    int rt = p;
+    const char *rows_h = rows_b, *dout_h = dout_b;
+    const float *lse_h = lse, *dlt_h = dlt;
+    if constexpr (GQ) {
+      rt = i_rt;
+      rows_h += i_j * (D * 2);
+      dout_h += i_j * (D * 2);
+      lse_h += (int64_t)i_j * a.R;
+      dlt_h += (int64_t)i_j * a.R;
+      if (++i_rt == NRT) { i_rt = 0; ++i_j; }
+    }
     const int r0 = rt * 64;
     const int rmax = a.R - 1 - r0;  // rows past R re-read row R-1; the compute masks them
-    dma.issue(rows_b + (int64_t)r0 * C * 2, C * 2, rmax, st, wave);
-    dma.issue(dout_b + (int64_t)r0 * C * 2, C * 2, rmax, st + IMG, wave);
+    dma.issue(rows_h + (int64_t)r0 * C * 2, C * 2, rmax, st, wave);
+    dma.issue(dout_h + (int64_t)r0 * C * 2, C * 2, rmax, st + IMG, wave);
     const uint32_t ro = (uint32_t)min(lane, rmax);  // offsets stay tile-relative (32-bit)
-    if (wave == 0) glds4(lse + r0, ro * 4, st + CF::OFF_L);
-    else if (wave == 1) glds4(dlt + r0, ro * 4, st + CF::OFF_D);
+    if (wave == 0) glds4(lse_h + r0, ro * 4, st + CF::OFF_L);
+    else if (wave == 1) glds4(dlt_h + r0, ro * 4, st + CF::OFF_D);
     else if (wave == 2 && mb) glds16(mb + (int64_t)rt * TPAD, (uint32_t)lane * 16, st + CF::OFF_W);
-    else glds4(lse + r0, ro * 4, st + CF::OFF_X);  // keeps NG DMAs per wave per tile
+    else glds4(lse_h + r0, ro * 4, st + CF::OFF_X);  // keeps NG DMAs per wave per tile
     if (a.mflags) glds_flags(a.mflags + ((int64_t)b * NRB32 + 2 * rt) * NKT4, NKT4, min(2, NRB32 - 2 * rt), cb >> 1,
                              st + CF::OFF_F);
-    else glds4(lse + r0, ro * 4, st + CF::OFF_X);
+    else glds4(lse_h + r0, ro * 4, st + CF::OFF_X);
   };
 
   f32x16 dq[DB], dv[DB];
@@ -399,8 +422,8 @@ __global__ __launch_bounds__(256, WPS) void flash_bwd_cols_kernel(BwdArgs a) {
 
 #pragma unroll
   for (int t = 0; t < PF; ++t)
-    if (t < NRT) issue(t);
-  if (PF > 1 && NRT > 1) wait_vm<NG * (PF - 1)>();
+    if (t < NT) issue(t);
+  if (PF > 1 && NT > 1) wait_vm<NG * (PF - 1)>();
   else wait_vm<0>();
   raw_barrier();
   // P and dS of one 32-row half tile in place (s <- P, dp <- dS); rows of register r:
@@ -452,15 +475,21 @@ __global__ __launch_bounds__(256, WPS) void flash_bwd_cols_kernel(BwdArgs a) {
 
   // one row tile from ring stage BUF (a compile-time constant: every LDS address is a lane
   // base + immediate, no per-read address arithmetic)
-  auto tile = [&](auto bufc, int rt) {
+  int c_rt = 0;  // GQ: row tile of the tile being computed
+  auto tile = [&](auto bufc, int p) {
     constexpr int BUF = decltype(bufc)::value;
-    if (rt + PF < NRT) issue(rt + PF);
+    if (p + PF < NT) issue(p + PF);
+    int rt = p;
+    if constexpr (GQ) {
+      rt = c_rt;
+      if (++c_rt == NRT) c_rt = 0;
+    }
     char* ks = smem + BUF * CF::STAGE;
     const char* ds = ks + IMG;
     float* ls = reinterpret_cast<float*>(ks + CF::OFF_L);
     const float* dls = reinterpret_cast<const float*>(ks + CF::OFF_D);
     const uint64_t* ws = reinterpret_cast<const uint64_t*>(ks + CF::OFF_W);
-    if (rt * 64 + 64 > a.R) {  // last tile, partial: rows past R get lse = +inf -> P = dS = 0
+    if (rt * 64 + 64 > a.R) {  // a head's last tile, partial: rows past R get lse = +inf -> P = dS = 0
       if (wave == 0 && rt * 64 + lane >= a.R) ls[lane] = __builtin_inff();
       __syncthreads();
     }
@@ -496,20 +525,20 @@ __global__ __launch_bounds__(256, WPS) void flash_bwd_cols_kernel(BwdArgs a) {
       }
     }
     // tile rt+1 complete (this wave's DMAs), everyone done with tile rt, then rotate
-    if (rt + PF < NRT) wait_vm<NG * (PF - 1)>();
+    if (p + PF < NT) wait_vm<NG * (PF - 1)>();
     else wait_vm<0>();
     raw_barrier();
   };
-  for (int rt = 0; rt < NRT; rt += NBUF) {
-    tile(std::integral_constant<int, 0>{}, rt);
-    if (rt + 1 < NRT) tile(std::integral_constant<int, 1>{}, rt + 1);
+  for (int p = 0; p < NT; p += NBUF) {
+    tile(std::integral_constant<int, 0>{}, p);
+    if (p + 1 < NT) tile(std::integral_constant<int, 1>{}, p + 1);
     if constexpr (NBUF > 2) {
-      if (rt + 2 < NRT) tile(std::integral_constant<int, 2>{}, rt + 2);
+      if (p + 2 < NT) tile(std::integral_constant<int, 2>{}, p + 2);
     }
   }
   const float nscale = PS ? -LN2 : -a.scale;  // dq was accumulated from -dS (and K' = K * scale * log2 e)
   if (col_ok && a.dkv16) {  // input dtype: half the store (and reduce-scatter) bytes
-    const int64_t off = col_off(col, b, a.T, a.ldg) + h * D;
+    const int64_t off = col_off(col, b, a.T, a.ldg) + hg * D;
     T16* pq = reinterpret_cast<T16*>(a.dkc) + off;
     T16* pv = reinterpret_cast<T16*>(a.dvc) + off;
 #pragma unroll
@@ -525,7 +554,7 @@ __global__ __launch_bounds__(256, WPS) void flash_bwd_cols_kernel(BwdArgs a) {
         *reinterpret_cast<u32x2*>(pv + db * 32 + 8 * g + 4 * hf) = v2;
       }
   } else if (col_ok) {
-    const int64_t off = col_off(col, b, a.T, a.ldg) + h * D;
+    const int64_t off = col_off(col, b, a.T, a.ldg) + hg * D;
     float* pq = reinterpret_cast<float*>(a.dkc) + off;
     float* pv = reinterpret_cast<float*>(a.dvc) + off;
 #pragma unroll
@@ -661,6 +690,12 @@ static void launch_bwd_cols(const BwdArgs& a, hipStream_t st) {
   if (D <= 96 && a.prescaled && xdot_flash_bwd_cols2_launch(&a, DT, D, st) == 0) return;
   const int ncb = (a.T + 127) / 128;
   constexpr int LDS2 = 2 * ColsCfg<D, 2>::STAGE;
+  if (a.G > 1) {  // grouped-query attention: one workgroup per gathered head, its own instantiation
+    const dim3 ggrid(ncb * a.B * (a.H / a.G));
+    if (a.prescaled) hipLaunchKernelGGL((flash_bwd_cols_kernel<DT, D, 2, 2, true, true>), ggrid, dim3(256), LDS2, st, a);
+    else hipLaunchKernelGGL((flash_bwd_cols_kernel<DT, D, 2, 2, false, true>), ggrid, dim3(256), LDS2, st, a);
+    return;
+  }
   const dim3 grid(ncb * a.B * a.H);
   if (a.prescaled) hipLaunchKernelGGL((flash_bwd_cols_kernel<DT, D, 2, 2, true>), grid, dim3(256), LDS2, st, a);
   else hipLaunchKernelGGL((flash_bwd_cols_kernel<DT, D, 2, 2>), grid, dim3(256), LDS2, st, a);

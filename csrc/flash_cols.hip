@@ -45,7 +45,11 @@ template <int D> struct Cols2Cfg {
   static constexpr int LDS = OFF_V + 128 * Img<D>::ROW;
 };
 
-template <int DT, int D>
+//
+// GQ (grouped-query attention, BwdArgs::G > 1): one workgroup per (b, GATHERED head, column block), as
+// in flash_bwd_cols_kernel: tile p of the G * NRT long sequence is row tile p % NRT of row head
+// hg * G + p / NRT; row splits cut that sequence.
+template <int DT, int D, bool GQ = false>
 __global__ __launch_bounds__(256, 2) void flash_bwd_cols2_kernel(BwdArgs a) {
   using T16 = typename dt_traits<DT>::T;
   using CB = ColsStage<D>;
@@ -60,8 +64,10 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_cols2_kernel(BwdArgs a) {
   const int ncb = (a.T + 127) / 128;
   const int lin = xcd_remap(blockIdx.x, gridDim.x);
   const int cb = lin % ncb, bhs = lin / ncb;
-  const int bh = bhs % (a.B * a.H), sp = bhs / (a.B * a.H), ns = a.csq > 1 ? a.csq : 1;
-  const int b = bh / a.H, h = bh % a.H;
+  // hg: gathered head; h: its (first) row head
+  const int G = GQ ? a.G : 1, Hg = GQ ? a.H / a.G : a.H;
+  const int bh = bhs % (a.B * Hg), sp = bhs / (a.B * Hg), ns = a.csq > 1 ? a.csq : 1;
+  const int b = bh / Hg, hg = bh % Hg, h = hg * G;
   const int C = a.H * D;
   const int NKT = (a.T + 63) / 64;
   const int NRB32 = (a.R + 31) / 32;
@@ -76,7 +82,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_cols2_kernel(BwdArgs a) {
   char* vimg = smem + CF::OFF_V;
   u32x4 qf[KS];
   {
-    const int64_t off = col_off(col_ok ? col : 0, b, a.T, a.ldkv) + h * D + 8 * hf;
+    const int64_t off = col_off(col_ok ? col : 0, b, a.T, a.ldkv) + hg * D + 8 * hf;
     const T16* pq = reinterpret_cast<const T16*>(a.kc) + off;
     const T16* pv = reinterpret_cast<const T16*>(a.vc) + off;
     const int vr = wave * 32 + (lane & 31), f = (vr >> 2) & 3;
@@ -91,10 +97,11 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_cols2_kernel(BwdArgs a) {
   }
   const char* vw = vimg + wave * 32 * ROW;  // this wave's 32 V rows (row_frag base, r0 = 0)
 
-  // row split sp of ns (BwdArgs::csq, against the last-round tail): 64-row tiles [rt_beg, rt_end),
-  // rt_beg even (ring stage = tile parity)
-  const int NRT = (a.R + 63) / 64, NRT2 = (NRT + 1) / 2;
-  const int rt_beg = 2 * (int)((int64_t)sp * NRT2 / ns), rt_end = min(NRT, 2 * (int)((int64_t)(sp + 1) * NRT2 / ns));
+  // row split sp of ns (BwdArgs::csq, against the last-round tail): tiles [rt_beg, rt_end) of the
+  // sweep's NT (64-row tiles of one head, GQ: of the group's G heads back to back), rt_beg even
+  // (ring stage = parity of the position in the sweep)
+  const int NRT = (a.R + 63) / 64, NT = GQ ? G * NRT : NRT, NRT2 = (NT + 1) / 2;
+  const int rt_beg = 2 * (int)((int64_t)sp * NRT2 / ns), rt_end = min(NT, 2 * (int)((int64_t)(sp + 1) * NRT2 / ns));
   ImgDma<D> dma;
   dma.init(wave, lane, C * 2);
   const char* rows_b = reinterpret_cast<const char*>(reinterpret_cast<const T16*>(a.rows) + (int64_t)b * a.R * C + h * D);
@@ -104,20 +111,37 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_cols2_kernel(BwdArgs a) {
   const int NRT64 = (a.R + 63) / 64, TPAD = (a.T + 127) / 128 * 128;
   const uint64_t* mb = a.mbits ? a.mbits + (int64_t)b * NRT64 * TPAD + cb * 128 : nullptr;
 
-  auto issue = [&](int rt) {
-    char* st = smem + (rt & 1) * CF::STAGE;
+  // GQ: (row tile, head of the group) of the next tile issued / row tile of the one computed (in order)
+  int i_rt = 0, i_j = 0, c_rt = 0;
+  if constexpr (GQ) {
+    i_j = rt_beg / NRT;
+    i_rt = c_rt = rt_beg - i_j * NRT;
+  }
+  auto issue = [&](int p) {
+    char* st = smem + (p & 1) * CF::STAGE;
+    int rt = p;
+    const char *rows_h = rows_b, *dout_h = dout_b;
+    const float *lse_h = lse, *dlt_h = dlt;
+    if constexpr (GQ) {
+      rt = i_rt;
+      rows_h += i_j * (D * 2);
+      dout_h += i_j * (D * 2);
+      lse_h += (int64_t)i_j * a.R;
+      dlt_h += (int64_t)i_j * a.R;
+      if (++i_rt == NRT) { i_rt = 0; ++i_j; }
+    }
     const int r0 = rt * 64;
     const int rmax = a.R - 1 - r0;
-    dma.issue(rows_b + (int64_t)r0 * C * 2, C * 2, rmax, st, wave);
-    dma.issue(dout_b + (int64_t)r0 * C * 2, C * 2, rmax, st + IMG, wave);
+    dma.issue(rows_h + (int64_t)r0 * C * 2, C * 2, rmax, st, wave);
+    dma.issue(dout_h + (int64_t)r0 * C * 2, C * 2, rmax, st + IMG, wave);
     const uint32_t ro = (uint32_t)min(lane, rmax);
-    if (wave == 0) glds4(lse + r0, ro * 4, st + CB::OFF_L);
-    else if (wave == 1) glds4(dlt + r0, ro * 4, st + CB::OFF_D);
+    if (wave == 0) glds4(lse_h + r0, ro * 4, st + CB::OFF_L);
+    else if (wave == 1) glds4(dlt_h + r0, ro * 4, st + CB::OFF_D);
     else if (wave == 2 && mb) glds16(mb + (int64_t)rt * TPAD, (uint32_t)lane * 16, st + CB::OFF_W);
-    else glds4(lse + r0, ro * 4, st + CB::OFF_X);
+    else glds4(lse_h + r0, ro * 4, st + CB::OFF_X);
     if (a.mflags) glds_flags(a.mflags + ((int64_t)b * NRB32 + 2 * rt) * NKT4, NKT4, min(2, NRB32 - 2 * rt), cb >> 1,
                              st + CB::OFF_F);
-    else glds4(lse + r0, ro * 4, st + CB::OFF_X);
+    else glds4(lse_h + r0, ro * 4, st + CB::OFF_X);
   };
 
   f32x16 dq[DB], dv[DB];
@@ -238,15 +262,20 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_cols2_kernel(BwdArgs a) {
   if (rt_beg < rt_end) issue(rt_beg);
   wait_vm<0>();
   __syncthreads();  // also publishes the V image (drains its LDS stores)
-  auto tile = [&](auto bufc, int rt) {
+  auto tile = [&](auto bufc, int p) {
     constexpr int BUF = decltype(bufc)::value;
-    if (rt + 1 < rt_end) issue(rt + 1);
+    if (p + 1 < rt_end) issue(p + 1);
+    int rt = p;
+    if constexpr (GQ) {
+      rt = c_rt;
+      if (++c_rt == NRT) c_rt = 0;
+    }
     char* ks = smem + BUF * CF::STAGE;
     const char* ds = ks + IMG;
     float* ls = reinterpret_cast<float*>(ks + CB::OFF_L);
     const float* dls = reinterpret_cast<const float*>(ks + CB::OFF_D);
     const uint64_t* ws = reinterpret_cast<const uint64_t*>(ks + CB::OFF_W);
-    if (rt * 64 + 64 > a.R) {  // last tile, partial: rows past R get lse2 = +inf -> P = dS = 0
+    if (rt * 64 + 64 > a.R) {  // a head's last tile, partial: rows past R get lse2 = +inf -> P = dS = 0
       if (wave == 0 && rt * 64 + lane >= a.R) ls[lane] = __builtin_inff();
       __syncthreads();
     }
@@ -265,8 +294,8 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_cols2_kernel(BwdArgs a) {
     if (rt + 1 < rt_end) tile(std::integral_constant<int, 1>{}, rt + 1);
   }
   const float nscale = -LN2;  // dq was accumulated from -dS and K' = K * scale * log2 e
-  if (col_ok && ns > 1) {  // fp32 partials of split sp, (ns, B*T, C) per half
-    const int64_t off = (((int64_t)sp * a.B + b) * a.T + col) * C + h * D;
+  if (col_ok && ns > 1) {  // fp32 partials of split sp, (ns, B*T, Hg*D) per half
+    const int64_t off = (((int64_t)sp * a.B + b) * a.T + col) * (Hg * D) + hg * D;
     float* pq = a.cpq + off;
     float* pv = a.cpv + off;
 #pragma unroll
@@ -279,7 +308,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_cols2_kernel(BwdArgs a) {
         *reinterpret_cast<f32x4*>(pv + db * 32 + 8 * g + 4 * hf) = v4;
       }
   } else if (col_ok && a.dkv16) {
-    const int64_t off = col_off(col, b, a.T, a.ldg) + h * D;
+    const int64_t off = col_off(col, b, a.T, a.ldg) + hg * D;
     T16* pq = reinterpret_cast<T16*>(a.dkc) + off;
     T16* pv = reinterpret_cast<T16*>(a.dvc) + off;
 #pragma unroll
@@ -295,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_cols2_kernel(BwdArgs a) {
         *reinterpret_cast<u32x2*>(pv + db * 32 + 8 * g + 4 * hf) = v2;
       }
   } else if (col_ok) {
-    const int64_t off = col_off(col, b, a.T, a.ldg) + h * D;
+    const int64_t off = col_off(col, b, a.T, a.ldg) + hg * D;
     float* pq = reinterpret_cast<float*>(a.dkc) + off;
     float* pv = reinterpret_cast<float*>(a.dvc) + off;
 #pragma unroll
@@ -319,15 +348,19 @@ extern "C" int xdot_flash_bwd_cols2_launch(const xdot::fa::BwdArgs* a, int dt, i
   using namespace xdot::fa;
   const int ns = a->csq > 1 ? a->csq : 1;
   if (ns > 1 && (!a->cpq || !a->cpv || (D & 3))) return -1;
-  const dim3 grid(((a->T + 127) / 128) * a->B * a->H * ns);
+  const int Hg = a->G > 1 ? a->H / a->G : a->H;  // gathered heads: the grid and the output columns
+  const dim3 grid(((a->T + 127) / 128) * a->B * Hg * ns);
   const int odt = a->dkv16 ? dt : (int)DT_F32;
   const int64_t rows = (int64_t)a->B * a->T;
 #define XC2(DTV, DV)                                                                                   \
   if (dt == DTV && D == DV) {                                                                          \
-    hipLaunchKernelGGL((flash_bwd_cols2_kernel<DTV, DV>), grid, dim3(256), Cols2Cfg<DV>::LDS, st, *a); \
+    if (a->G > 1)                                                                                      \
+      hipLaunchKernelGGL((flash_bwd_cols2_kernel<DTV, DV, true>), grid, dim3(256), Cols2Cfg<DV>::LDS, st, *a); \
+    else                                                                                               \
+      hipLaunchKernelGGL((flash_bwd_cols2_kernel<DTV, DV>), grid, dim3(256), Cols2Cfg<DV>::LDS, st, *a); \
     if (ns > 1) {                                                                                      \
-      xdot_flash_cols_sum_launch(a->cpq, a->dkc, ns, rows, a->H * D, a->ldg, odt, st);                 \
-      xdot_flash_cols_sum_launch(a->cpv, a->dvc, ns, rows, a->H * D, a->ldg, odt, st);                 \
+      xdot_flash_cols_sum_launch(a->cpq, a->dkc, ns, rows, Hg * D, a->ldg, odt, st);                   \
+      xdot_flash_cols_sum_launch(a->cpv, a->dvc, ns, rows, Hg * D, a->ldg, odt, st);                   \
     }                                                                                                  \
     return 0;                                                                                          \
   }
@@ -336,12 +369,14 @@ extern "C" int xdot_flash_bwd_cols2_launch(const xdot::fa::BwdArgs* a, int dt, i
   return -1;
 }
 
-// row splits of the pipelined column kernel: XDOT_CSPLIT=n only (opt-in)
+// row splits of the pipelined column kernel: XDOT_CSPLIT=n (opt-in); automatic only for grouped heads
+// whose grid underfills the GPU
 extern "C" int xdot_flash_cols_splits_cols2(const xdot::fa::BwdArgs* a, int dt, int D, int* sq) {
   using namespace xdot;
   using namespace xdot::fa;
   *sq = 1;
-  const int NRT = (a->R + 63) / 64;
+  // tiles of one workgroup's sweep: the 64-row tiles of all G row heads of its gathered head
+  const int NRT = ((a->R + 63) / 64) * (a->G > 1 ? a->G : 1);
   const int e = env_int("XDOT_CSPLIT", 1, 4);  // as in flash_f32.hip, <= 4
   if (e >= 0) {
     *sq = (NRT + 1) / 2 / e >= 1 ? e : 1;
@@ -351,6 +386,24 @@ extern "C" int xdot_flash_cols_splits_cols2(const xdot::fa::BwdArgs* a, int dt, 
   // 3.68 -> 3.49 ms for the kernel, but the fp32 partials (3 x 154 MB written and read back)
   // cost more than that in the step (7.84 -> 8.08 ms); at the N=8 rank shape 0.51 -> 0.71 ms.
   // The tail workgroups of this short kernel run faster alone than the round model assumes.
+  //
+  // Grouped-query attention: the grid is G x smaller and every sweep G x longer.  Where the whole
+  // grid leaves at least half of the 2-per-CU workgroup slots empty (H = 8, Hg = 1, T = 25000: 196
+  // workgroups on 512 slots), the sweeps are cut so that it still runs in one round; the partials
+  // are Hg * D wide (G x smaller than the ones that did not pay above)
+  if (a->G > 1) {
+    const int cus = xdot_num_cus();
+    const int64_t slots = 2 * (int64_t)(cus > 0 ? cus : 256);
+    const int64_t W = (int64_t)((a->T + 127) / 128) * a->B * (a->H / a->G);
+    int s = (int)std::min<int64_t>(4, slots / std::max<int64_t>(W, 1));
+    // With a mask the sweeps are uneven (causal: the first column block sweeps every row, the last
+    // almost none) and a grid of about one round cannot even that out: T = R = 25000, H = 8, causal,
+    // Hg = 2 3.44 ms unsplit vs 2.31 ms in 4 pieces (Hg = 8: 2.25 ms), Hg = 1 3.45 (2 pieces) vs 2.98
+    // (profiles/gqa.md).  The sweep is cut back to about one head's length
+    if (a->mflags) s = std::max(s, std::min(4, a->G));
+    while (s >= 2 && (NRT + 1) / 2 / s < 1) --s;
+    if (s >= 2) *sq = s;
+  }
   (void)dt;
   (void)D;
   return 0;

@@ -96,8 +96,9 @@ __global__ __launch_bounds__(256, 2) void flash_fwd_kernel(FwdArgs a) {
   const int ldb = a.ldkv * 2;  // gathered row stride, bytes
   ImgDma<D> dma;
   dma.init(wave, lane, ldb);
-  const char* kcb = reinterpret_cast<const char*>(reinterpret_cast<const T16*>(a.kc) + h * D + (int64_t)b * a.T * a.ldkv);
-  const char* vcb = reinterpret_cast<const char*>(reinterpret_cast<const T16*>(a.vc) + h * D + (int64_t)b * a.T * a.ldkv);
+  const int hg = a.G > 1 ? (h * a.gmul) >> 20 : h;  // gathered head h / G of this row head (grouped-query attention)
+  const char* kcb = reinterpret_cast<const char*>(reinterpret_cast<const T16*>(a.kc) + hg * D + (int64_t)b * a.T * a.ldkv);
+  const char* vcb = reinterpret_cast<const char*>(reinterpret_cast<const T16*>(a.vc) + hg * D + (int64_t)b * a.T * a.ldkv);
   const uint64_t* mwg = a.mbits ? a.mbits + (int64_t)b * NKT * a.R + rb * 128 : nullptr;  // + kt * R per tile
   const uint32_t moff = (uint32_t)(min((wave & 1) * 64 + lane, a.R - 1 - rb * 128) * 8 + (wave >> 1) * 4);
   // two rings over the same 3 stages: Q(t) + mask words(t) and V(t) go to stage (t - kt_beg) % 3,

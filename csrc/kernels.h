@@ -64,6 +64,10 @@ struct FwdArgs {
   // exact fp32 only: non-null -> the raw scores S of every computed 32x32 tile are stored here
   // ((B*H, ceil(R/32), ceil(T/32)) blocks of 1024 floats, flash_f32.hip "score buffer")
   float* sbuf;
+  // grouped-query attention: G = H / Hg row heads share gathered head h / G (0 / 1: none).  kc / vc
+  // then hold Hg * D columns (16-bit kernels, D <= 128).  gmul = ceil(2^20 / G): h / G == (h * gmul) >> 20
+  // for h, G <= 1024 (no integer division in the kernels' prologue)
+  int G, gmul;
 };
 
 struct BwdArgs {
@@ -112,6 +116,11 @@ struct BwdArgs {
   // the gradients directly, the last xrem run in csq row pieces whose partials are compact:
   // cpq/cpv[((piece * 8*xrem + tail) * 128 + column-in-block) * D]
   int xcb, xwhole, xrem;
+  // grouped-query attention: G = H / Hg row heads share gathered head h / G (0 / 1: none).  kc / vc /
+  // dkc / dvc (and cpq / cpv) then have Hg * D columns; the column kernels run one workgroup per
+  // (b, gathered head, 128-column block) and sweep the row tiles of its G row heads (16-bit, D <= 128).
+  // gmul: as FwdArgs::gmul (row-side kernel)
+  int G, gmul;
 };
 
 }  // namespace fa

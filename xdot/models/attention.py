@@ -42,6 +42,11 @@ Keyword-only knobs (each mirrors an environment flag, the argument
 ``chunk_plan``  row chunks of the fused path's all-gather / reduce-scatter pipeline
                 (``XDOT_GATHER_CHUNKS``); the materialised path's chunking is ``offset``;
 ``comm``        communicator (default: the process group of :func:`xdot.init`);
+``num_gathered_heads``  heads of ``queries`` / ``values`` (the gathered side; grouped-query
+                attention's ``num_kv_heads``): gathered head ``h // G`` serves row head ``h``,
+                ``G = num_heads // num_gathered_heads``.  ``queries`` / ``values`` project to that
+                many heads, so the all-gather, the reduce-scatter, the ring hops and the buffer kept
+                for the backward are ``G`` times smaller.  ``None`` (default): ``num_heads``;
 ``rope``        an :class:`xdot.Rotary`: ``k`` and ``q`` are rotated (rotary position embedding,
                 :mod:`xdot.ops.rope`) after their projections, at this rank's global positions
                 (``rank * R`` unless the object carries an offset; 0 with ``distributed=False``),
@@ -118,7 +123,8 @@ class DistributedDotProductAttn(nn.Module):
                  num_heads: int = 1, add_bias: bool = False, offset: Optional[int] = 32,
                  distributed: bool = True, *, impl: str = "auto", fused: Optional[bool] = None,
                  backend: str = "auto", dtype: Optional[torch.dtype] = None, chunk_plan: Optional[int] = None,
-                 comm: Optional[_comm.Communicator] = None, rope: Optional[Rotary] = None):
+                 comm: Optional[_comm.Communicator] = None, rope: Optional[Rotary] = None,
+                 num_gathered_heads: Optional[int] = None):
         super().__init__()
         if fused is not None:
             if impl not in ("auto", "flash" if fused else "materialized"):
@@ -138,12 +144,17 @@ class DistributedDotProductAttn(nn.Module):
             raise ValueError(f"value_dim {value_dim} not divisible by num_heads {num_heads}")
         if impl not in ("auto", "flash", "materialized", "ring"):
             raise ValueError(f"impl must be auto|flash|materialized|ring, got {impl!r}")
+        if num_gathered_heads is None:
+            num_gathered_heads = num_heads
+        if int(num_gathered_heads) < 1 or num_heads % int(num_gathered_heads) != 0:
+            raise ValueError(f"num_heads {num_heads} not divisible by num_gathered_heads {num_gathered_heads}")
         if rope is not None:
             if not isinstance(rope, Rotary):
                 raise TypeError(f"rope must be an xdot.Rotary or None, got {type(rope).__name__}")
             if (key_dim // num_heads) % 2:
                 raise ValueError(f"rope needs an even head dim, got {key_dim // num_heads}")
         self.num_heads = num_heads
+        self.num_gathered_heads = int(num_gathered_heads)
         self.value_dim = value_dim
         self.offset = offset
         self.distributed = distributed
@@ -155,8 +166,9 @@ class DistributedDotProductAttn(nn.Module):
         self.comm = comm
         self.rope = rope
         self.keys = nn.Linear(key_dim, key_dim, bias=add_bias)
-        self.queries = nn.Linear(query_dim, key_dim, bias=add_bias)
-        self.values = nn.Linear(value_dim, value_dim, bias=add_bias)
+        # the gathered side: num_gathered_heads heads (key_dim / value_dim wide by default)
+        self.queries = nn.Linear(query_dim, self.num_gathered_heads * self.dim, bias=add_bias)
+        self.values = nn.Linear(value_dim, self.num_gathered_heads * (value_dim // num_heads), bias=add_bias)
         self.composition = nn.Linear(value_dim, value_dim, bias=add_bias)
         # weakref to an attached xdot.parallel.GradSync (set by it): the fused node hands it the
         # parameter gradients as they are computed (early all-reduce)
@@ -199,18 +211,21 @@ class DistributedDotProductAttn(nn.Module):
 
             comm = (self.comm or _comm.get_comm()) if self.distributed else _comm.LocalComm()
             H, dk, dv = self.num_heads, self.dim, self.value_dim // self.num_heads
+            Hg = self.num_gathered_heads  # (gh: None for the default, what the attention functions take)
+            gh = None if Hg == H else Hg
             Dp = pa.flash_head_dim(dk, dv) if keys.is_cuda else dk
             if keys.is_cuda and Dp is not None and (Dp != dk or Dp != dv):
                 # head dims the kernels do not take (or value width != key width): every head
                 # zero-padded to the next kernel dim, same scale 1/sqrt(dk)
                 qv = self._project_qv(queries, values)
-                q, k = qv[..., :H * dk], self._proj(self.keys, keys)
+                q, k = qv[..., :Hg * dk], self._proj(self.keys, keys)
                 if self.rope is not None:  # at width dk, before the zero padding
                     off = self.rope.resolve(comm.rank, k.shape[1])
-                    q, k = _rope(q, H, self.rope, offset=off), _rope(k, H, self.rope, offset=off)
-                qv = torch.cat([pa.pad_heads(q, H, dk, Dp), pa.pad_heads(qv[..., H * dk:], H, dv, Dp)], dim=-1)
+                    q, k = _rope(q, Hg, self.rope, offset=off), _rope(k, H, self.rope, offset=off)
+                # (the Hg gathered heads and the H row heads are padded separately)
+                qv = torch.cat([pa.pad_heads(q, Hg, dk, Dp), pa.pad_heads(qv[..., Hg * dk:], Hg, dv, Dp)], dim=-1)
                 k = pa.pad_heads(k, H, dk, Dp)
-                o = seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm)
+                o = seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm, gathered_heads=gh)
                 return self._proj(self.composition, pa.unpad_heads(o, H, dv, Dp))
             if isinstance(attn_mask, Tensor) and attn_mask.is_cuda and attn_mask.dim() == 3 and FLAGS.mask_async:
                 # pack the mask on a side stream while the projection GEMMs run
@@ -237,22 +252,22 @@ class DistributedDotProductAttn(nn.Module):
                     sync = (gs, id(self))
                 return AttnBlockFn.apply(keys, queries, attn_mask, self.keys.weight, self.keys.bias, wq, bq, wv, bv,
                                          self.composition.weight, self.composition.bias, self.num_heads, scale, comm,
-                                         self.chunk_plan, sync, torch.is_grad_enabled(), self.rope)
+                                         self.chunk_plan, sync, torch.is_grad_enabled(), self.rope, gh)
             # gathered side first: its all-gather runs while the row-side GEMM computes
             qv = self._project_qv(queries, values)
             pre = False
             if self.rope is not None:  # q rotated before the gather is issued
                 off = self.rope.resolve(comm.rank, qv.shape[1])
-                qv = rope_packed(qv, H * dk, H, self.rope, off)
+                qv = rope_packed(qv, Hg * dk, Hg, self.rope, off)
             pending = start_gather(qv, comm, chunks=self.chunk_plan)
             k = self._proj(self.keys, keys)
             if self.rope is not None:
                 # the row side's pre-scale rides in the rotation pass (its gradient comes back
                 # w.r.t. the unscaled rows: no factor in the backward)
-                pre = pa.prescale_wanted(k, qv, H)
+                pre = pa.prescale_wanted(k, qv, H, gh)
                 k = rope_packed(k, H * dk, H, self.rope, off, alpha=scale * _LOG2E if pre else 1.0, bwd_alpha=1.0)
             o = seq_parallel_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm, pending=pending,
-                                              k_prescaled=pre)
+                                              k_prescaled=pre, gathered_heads=gh)
             return self._proj(self.composition, o)
         if self._pick_impl(keys) == "ring":
             from ..parallel.ring import ring_attention_packed
@@ -262,9 +277,11 @@ class DistributedDotProductAttn(nn.Module):
             k = self._proj(self.keys, keys)
             if self.rope is not None:
                 off = self.rope.resolve(comm.rank, k.shape[1])
-                qv = rope_packed(qv, self.num_heads * self.dim, self.num_heads, self.rope, off)
+                qv = rope_packed(qv, self.num_gathered_heads * self.dim, self.num_gathered_heads, self.rope, off)
                 k = rope_packed(k, k.shape[-1], self.num_heads, self.rope, off)
-            o = ring_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm)
+            o = ring_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm,
+                                      gathered_heads=None if self.num_gathered_heads == self.num_heads
+                                      else self.num_gathered_heads)
             return self._proj(self.composition, o)
         k = self._proj(self.keys, keys)
         q = self._proj(self.queries, queries)
@@ -272,7 +289,8 @@ class DistributedDotProductAttn(nn.Module):
         if self.rope is not None:
             rank = (self.comm or _comm.get_comm()).rank if self.distributed else 0
             off = self.rope.resolve(rank, k.shape[1])
-            k, q = _rope(k, self.num_heads, self.rope, offset=off), _rope(q, self.num_heads, self.rope, offset=off)
+            k = _rope(k, self.num_heads, self.rope, offset=off)
+            q = _rope(q, self.num_gathered_heads, self.rope, offset=off)
         return self._proj(self.composition, self._materialized(k, q, v, attn_mask, scale))
 
     def _proj(self, layer: nn.Linear, x: Tensor) -> Tensor:
@@ -297,8 +315,11 @@ class DistributedDotProductAttn(nn.Module):
         B, R = k.shape[0], k.shape[1]
         if H > 1:
             k = k.view(B, R, H, self.dim).transpose(1, 2)
-            q = q.view(B, q.shape[1], H, self.dim).transpose(1, 2)
-            v = v.view(B, v.shape[1], H, self.value_dim // H).transpose(1, 2)
+            Hg = self.num_gathered_heads
+            q = q.view(B, q.shape[1], Hg, self.dim).transpose(1, 2)
+            v = v.view(B, v.shape[1], Hg, self.value_dim // H).transpose(1, 2)
+            if Hg != H:  # grouped heads: every gathered head repeated for its group's products
+                q, v = q.repeat_interleave(H // Hg, dim=1), v.repeat_interleave(H // Hg, dim=1)
         if self.distributed:
             comm = self.comm or _comm.get_comm()
             s = RightTransposeMultiplication.apply(k, q, self.offset, comm)
@@ -321,4 +342,5 @@ class DistributedDotProductAttn(nn.Module):
         return (f"heads={self.num_heads}, head_dim={self.dim}, value_dim={self.value_dim}, "
                 f"offset={self.offset}, distributed={self.distributed}, impl={self.impl}, backend={self.backend}, "
                 f"dtype={self.compute_dtype}, chunk_plan={self.chunk_plan}"
-                + (f", rope={self.rope!r}" if self.rope is not None else ""))
+                + (f", rope={self.rope!r}" if self.rope is not None else "")
+                + (f", num_gathered_heads={self.num_gathered_heads}" if self.num_gathered_heads != self.num_heads else ""))

@@ -78,7 +78,8 @@ class AttnBlockFn(torch.autograd.Function):
     @staticmethod
     @_ext.pinned
     def forward(ctx, xk, xqv, mask, wk, bk, wq, bq, wv, bv, wc, bc, H, scale, comm, chunk_plan, sync=None,
-                grad_on=True, rope=None):
+                grad_on=True, rope=None, Hg=None):
+        # Hg: gathered heads when fewer than H (grouped-query attention): wq / wv hold Hg heads
         wqv = _rows(wq, wv)
         bqv = _rows(bq, bv) if bq is not None else None
         n = comm.world_size
@@ -99,24 +100,26 @@ class AttnBlockFn(torch.autograd.Function):
         if rope is not None:
             # q rotated at this rank's global positions, in place and BEFORE the gather is issued
             # (with the in-place gather this block is what the peers pull); v is untouched
-            tab = rope.table(R, nq // H, rope.resolve(comm.rank, R), qv.device, _table_dtype(qv))
-            rope_apply(qv[..., :nq], H, *tab, out=qv[..., :nq])
+            tab = rope.table(R, nq // (Hg or H), rope.resolve(comm.rank, R), qv.device, _table_dtype(qv))
+            rope_apply(qv[..., :nq], Hg or H, *tab, out=qv[..., :nq])
         pending = start_gather(qv, comm, chunks=chunk_plan, out=gbuf)  # in flight under the row-side GEMM
         # the row side's pre-scale (scale * log2 e) folded into the k projection: one rounding, no
         # separate pass (the attention backward's dk is w.r.t. the unscaled k either way)
-        pre = xk.shape[-1] == wk.shape[1] and prescale_wanted(qv[..., :wk.shape[0]], qv, H)
+        # (the probe reads shape, dtype and device only: a stride-0 view shaped like k)
+        k_like = qv[..., :wk.shape[0]] if Hg is None else qv[..., :1].expand(B, R, wk.shape[0])
+        pre = xk.shape[-1] == wk.shape[1] and prescale_wanted(k_like, qv, H, Hg)
         k = proj(xk, wk, bk, alpha=scale * _LOG2E if pre else 1.0)
         if tab is not None:  # the pre-scale sits in the projection: a rotation commutes with a scalar
             rope_apply(k, H, *tab, out=k)
         actx = _Ctx()
         actx.needs_input_grad = (any(ctx.needs_input_grad),) * 2  # a backward can run (score buffers)
-        o = SeqParallelAttention.forward(actx, k, qv, mask, H, scale, comm, pending, pre, grad_on)  # k_prescaled
+        o = SeqParallelAttention.forward(actx, k, qv, mask, H, scale, comm, pending, pre, grad_on, Hg)  # k_prescaled
         out = proj(o, wc, bc)
         ctx.actx = actx
         ctx.sync = sync  # (GradSync, module key) or None
         ctx.params = (wk, bk, wq, bq, wv, bv, wc, bc)
         ctx.nq = nq
-        ctx.rope_tab, ctx.H = tab, H
+        ctx.rope_tab, ctx.H, ctx.Hg = tab, H, Hg or H
         ctx.has_b = (bk is not None, bq is not None, bc is not None)
         # the attention's tensors go through save_for_backward too (version checks, and a graph
         # retained for a second backward keeps them)
@@ -167,11 +170,11 @@ class AttnBlockFn(torch.autograd.Function):
             rope_apply(dk, ctx.H, *ctx.rope_tab, inverse=True, out=dk)
             dq, on = dqv[..., :ctx.nq], getattr(dqv, "_xdot_ready_on", None)
             if on is None:
-                rope_apply(dq, ctx.H, *ctx.rope_tab, inverse=True, out=dq)
+                rope_apply(dq, ctx.Hg, *ctx.rope_tab, inverse=True, out=dq)
             else:
                 here = torch.cuda.current_stream(dqv.device)
                 with _on_stream(on, here):
-                    rope_apply(dq, ctx.H, *ctx.rope_tab, inverse=True, out=dq)
+                    rope_apply(dq, ctx.Hg, *ctx.rope_tab, inverse=True, out=dq)
                 here.wait_stream(on)
         # the row-side weight gradient also runs beside the input-gradient GEMMs that follow
         # d[q|v] may be ready on the backward's priority stream (``_xdot_ready_on``): its weight
@@ -216,4 +219,4 @@ class AttnBlockFn(torch.autograd.Function):
         # the attention's tensors were only borrowed from ctx.saved_tensors (rebuilt from there by
         # every backward): do not keep them alive through the node after this backward
         ctx.actx._saved = None
-        return (dxk, dxqv, None, dwk, dbk, dwq, dbq, dwv, dbv, dwc, dbc, None, None, None, None, None, None, None)
+        return (dxk, dxqv, None, dwk, dbk, dwq, dbq, dwv, dbv, dwc, dbc, None, None, None, None, None, None, None, None)

@@ -2,7 +2,9 @@
 ``csrc/mask_pack.hip``).
 
 Tensors are head-interleaved: ``rows`` (B, R, H*D) local query-side rows, ``kc``/``vc``
-(B, T, H*D) the gathered key/value side.  The RCCL all-gather produces rank-major
+(B, T, Hg*D) the gathered key/value side.  ``Hg`` (None: ``H``) is the number of gathered heads:
+with ``Hg < H`` (grouped-query attention) row head ``h`` reads gathered head ``h // (H // Hg)`` and
+the gathered-side gradients are summed over each group in the column kernel (16-bit, D <= 128).  The RCCL all-gather produces rank-major
 (N, B, Rc, H*D); :func:`gathered_to_btc` turns that into (B, T, H*D) (a free view for B = 1)
 and :func:`btc_to_rank_major` maps the fp32 key/value-side gradients back for the
 reduce-scatter.
@@ -226,6 +228,12 @@ def _kv(x: torch.Tensor) -> torch.Tensor:
     return x.contiguous()
 
 
+def _hg(Hg: Optional[int]):
+    """The ops' trailing ``Hg`` argument: passed only when set (an extension built before it existed
+    -- an A/B build loaded through ``XDOT_EXT_PATH`` -- still takes every other call)."""
+    return (int(Hg),) if Hg else ()
+
+
 def _mask_args(mk: Optional[PackedMask]):
     return (mk.bits, mk.flags) if mk is not None else (None, None)
 
@@ -326,7 +334,8 @@ def ds_only_wanted(fp32_mode: int, D: int) -> bool:
 
 def fwd(rows: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, mk: Optional[PackedMask], H: int,
         scale: float, nsplit: int = 0, prescaled: bool = False,
-        fp32_mode: Optional[int] = None, sbuf: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        fp32_mode: Optional[int] = None, sbuf: Optional[torch.Tensor] = None,
+        Hg: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """-> (out (B, R, H*D) in rows.dtype, lse (B, H, R) fp32 natural log).
 
     ``nsplit``: column splits (0 = auto: split only when R is too small to fill the GPU).
@@ -336,7 +345,7 @@ def fwd(rows: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, mk: Optional[Pac
     bits, flags = _mask_args(mk)
     fm = fp32_code(rows.dtype) if fp32_mode is None else int(fp32_mode)
     return _ext.ops().flash_fwd(rows.contiguous(), _kv(kc), _kv(vc), bits, flags, int(H), float(scale), int(nsplit),
-                                bool(prescaled), fm, sbuf)
+                                bool(prescaled), fm, sbuf, *_hg(Hg))
 
 
 def bwd_delta(dout: torch.Tensor, out: torch.Tensor, H: int) -> torch.Tensor:
@@ -353,8 +362,8 @@ def bwd_cols(dout, rows, kc, vc, out, lse, mk: Optional[PackedMask], H: int, sca
              delta: Optional[torch.Tensor] = None, fp32_out: bool = True, prescaled: bool = False,
              lse2: Optional[torch.Tensor] = None, fp32_mode: Optional[int] = None,
              sbuf: Optional[torch.Tensor] = None, dsbuf: Optional[torch.Tensor] = None, passes: int = 3,
-             out_dkv: Optional[torch.Tensor] = None):
-    """Gathered-side grads -> (packed [d_kc | d_vc] (B, T, 2*H*D), delta (B, H, R)).
+             out_dkv: Optional[torch.Tensor] = None, Hg: Optional[int] = None):
+    """Gathered-side grads -> (packed [d_kc | d_vc] (B, T, 2*Hg*D), delta (B, H, R)).
 
     ``delta`` (from :func:`bwd_delta`) is computed here when not given; with ``lse2`` too (both
     from :func:`bwd_prep`) no prep pass is launched here.  The grads are fp32
@@ -368,12 +377,12 @@ def bwd_cols(dout, rows, kc, vc, out, lse, mk: Optional[PackedMask], H: int, sca
                                      out.contiguous(), lse.contiguous(), bits, flags, int(H), float(scale), delta,
                                      bool(fp32_out), bool(prescaled), lse2,
                                      fp32_code(rows.dtype) if fp32_mode is None else int(fp32_mode), sbuf, dsbuf,
-                                     int(passes), out_dkv)
+                                     int(passes), out_dkv, *_hg(Hg))
 
 
 def bwd_rows(dout, rows, kc, vc, lse, delta, mk: Optional[PackedMask], H: int, scale: float, nsplit: int = 0,
              prescaled: bool = False, fp32_mode: Optional[int] = None, sbuf: Optional[torch.Tensor] = None,
-             dsbuf: Optional[torch.Tensor] = None):
+             dsbuf: Optional[torch.Tensor] = None, Hg: Optional[int] = None):
     """Row-side grad (B, R, H*D) in rows.dtype.  ``nsplit`` 0: the launcher's occupancy model
     (column splits so the row kernel fills the GPU; 1 measured 7 % / 32 % slower at N = 1 / 8).
     ``sbuf``: the score buffer after :func:`bwd_cols` wrote dS into it (dK is then its only product);
@@ -382,22 +391,23 @@ def bwd_rows(dout, rows, kc, vc, lse, delta, mk: Optional[PackedMask], H: int, s
     return _ext.ops().flash_bwd_rows(dout.contiguous(), rows.contiguous(), _kv(kc), _kv(vc),
                                      lse.contiguous(), delta.contiguous(), bits, flags, int(H), float(scale),
                                      int(nsplit), bool(prescaled),
-                                     fp32_code(rows.dtype) if fp32_mode is None else int(fp32_mode), sbuf, dsbuf)
+                                     fp32_code(rows.dtype) if fp32_mode is None else int(fp32_mode), sbuf, dsbuf,
+                                     *_hg(Hg))
 
 
 def bwd(dout: torch.Tensor, rows: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, out: torch.Tensor,
         lse: torch.Tensor, mk: Optional[PackedMask], H: int, scale: float, prescaled: bool = False,
-        fp32_mode: Optional[int] = None, sbuf: Optional[torch.Tensor] = None):
-    """-> (d_rows (B, R, H*D) rows.dtype, d_kc, d_vc (B, T, H*D) fp32 partial grads).
+        fp32_mode: Optional[int] = None, sbuf: Optional[torch.Tensor] = None, Hg: Optional[int] = None):
+    """-> (d_rows (B, R, H*D) rows.dtype, d_kc, d_vc (B, T, Hg*D) fp32 partial grads).
 
     ``prescaled``: ``rows`` is :func:`prescale` output (the buffer the forward read); d_rows is
     still the gradient of the unscaled rows.  ``sbuf``: the forward's score buffer (consumed)."""
     dkv, delta = bwd_cols(dout, rows, kc, vc, out, lse, mk, H, scale, prescaled=prescaled, fp32_mode=fp32_mode,
-                          sbuf=sbuf)
+                          sbuf=sbuf, Hg=Hg)
     drows = bwd_rows(dout, rows, kc, vc, lse, delta, mk, H, scale, prescaled=prescaled, fp32_mode=fp32_mode,
-                     sbuf=sbuf)
-    C = rows.shape[-1]
-    return drows, dkv[..., :C], dkv[..., C:]
+                     sbuf=sbuf, Hg=Hg)
+    Cg = (Hg or H) * (rows.shape[-1] // H)
+    return drows, dkv[..., :Cg], dkv[..., Cg:]
 
 
 # ---- launches into partial slots (gather chunks, ring blocks) ------------------------------------
@@ -409,13 +419,13 @@ def splits(B: int, R: int, T: int, H: int, rows_kernel: bool = False) -> int:
 
 def fwd_partial(rows: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, mk: Optional[PackedMask], H: int,
                 scale: float, opart: torch.Tensor, lpart: torch.Tensor, slot: int, nsplit: int,
-                prescaled: bool = False, fp32_mode: int = 0) -> None:
+                prescaled: bool = False, fp32_mode: int = 0, Hg: Optional[int] = None) -> None:
     """Forward over one column segment into slots ``[slot, slot + nsplit)`` of ``opart`` (S, B, R, C)
     / ``lpart`` (S, B, H, R), fp32: per slot the output normalised over its columns and their LSE
     (-inf where they are all masked: the merges leave such a slot's output out).  ``rows`` contiguous."""
     bits, flags = _mask_args(mk)
     _ext.ops().flash_fwd_partial(rows, _kv(kc), _kv(vc), bits, flags, int(H), float(scale), opart, lpart, int(slot),
-                                 int(nsplit), bool(prescaled), int(fp32_mode))
+                                 int(nsplit), bool(prescaled), int(fp32_mode), *_hg(Hg))
 
 
 def fwd_combine(opart: torch.Tensor, lpart: torch.Tensor, H: int, like: torch.Tensor):
@@ -430,12 +440,13 @@ def fwd_merge(opart: torch.Tensor, lpart: torch.Tensor, lrun: torch.Tensor, H: i
 
 
 def bwd_rows_partial(dout, rows, kc, vc, lse, delta, mk: Optional[PackedMask], H: int, scale: float,
-                     dpart: torch.Tensor, slot: int, nsplit: int, prescaled: bool = False, fp32_mode: int = 0) -> None:
+                     dpart: torch.Tensor, slot: int, nsplit: int, prescaled: bool = False, fp32_mode: int = 0,
+                     Hg: Optional[int] = None) -> None:
     """Row-side grads of one column segment into slots ``[slot, slot + nsplit)`` of ``dpart``
     (S, B, R, C) fp32.  ``dout`` / ``rows`` / ``lse`` / ``delta`` contiguous."""
     bits, flags = _mask_args(mk)
     _ext.ops().flash_bwd_rows_partial(dout, rows, _kv(kc), _kv(vc), lse, delta, bits, flags, int(H), float(scale),
-                                      dpart, int(slot), int(nsplit), bool(prescaled), int(fp32_mode))
+                                      dpart, int(slot), int(nsplit), bool(prescaled), int(fp32_mode), *_hg(Hg))
 
 
 def bwd_rows_sum(dpart: torch.Tensor, H: int, like: torch.Tensor) -> torch.Tensor:

@@ -1,7 +1,8 @@
 """The attention maths in torch, written once: the oracle of the CPU tests and the path that CPU
 tensors (and GPU dtypes the kernels do not take) run.  Row side ``k`` (B, R, H*dh), one column
-segment of the gathered side ``kc`` (B, T, H*dh) / ``vc`` (B, T, H*dv), ``mask`` bool (B, R, T)
-with True = masked, or None.  fp64 stays fp64, everything else computes in fp32.  The flash and
+segment of the gathered side ``kc`` (B, T, Hg*dh) / ``vc`` (B, T, Hg*dv), ``mask`` bool (B, R, T)
+with True = masked, or None.  ``Hg`` (None: ``H``) gathered heads: row head ``h`` reads gathered
+head ``h // (H // Hg)`` (grouped-query attention, the ``repeat_interleave`` convention).  fp64 stays fp64, everything else computes in fp32.  The flash and
 the ring path are layout adapters over these functions (:mod:`xdot.parallel.attention`,
 :mod:`xdot.parallel.ring`)."""
 from __future__ import annotations
@@ -17,6 +18,20 @@ def heads(x, H: int, cdt):
     """(B, L, H*d) -> (B, H, L, d) in the compute dtype."""
     B, L, C = x.shape
     return x.reshape(B, L, H, C // H).transpose(1, 2).to(cdt)
+
+
+def gathered_heads(x, H: int, Hg, cdt):
+    """(B, T, Hg*d) -> (B, H, T, d) in the compute dtype: every gathered head repeated for its group."""
+    xh = heads(x, Hg or H, cdt)
+    return xh if not Hg or Hg == H else xh.repeat_interleave(H // Hg, dim=1)
+
+
+def _fold(x, H: int, Hg):
+    """(B, H, T, d) per-row-head gathered-side gradients -> (B, Hg, T, d): summed over each group."""
+    if not Hg or Hg == H:
+        return x
+    B, _, T, d = x.shape
+    return x.reshape(B, Hg, H // Hg, T, d).sum(2)
 
 
 def _merge(x):
@@ -36,14 +51,14 @@ def delta(do, o, H: int, cdt):
     return (heads(do, H, cdt) * heads(o, H, cdt)).sum(-1)
 
 
-def block_fwd(k, kc, vc, mask, H: int, scale: float):
+def block_fwd(k, kc, vc, mask, H: int, scale: float, Hg=None):
     """One column segment of the forward -> (o (B, R, H*dv) normalised over the segment, lse
     (B, H, R)), compute dtype; a row the segment masks entirely gets o = 0, lse = -inf."""
     cdt = compute_dtype(k)
-    s = _scores(heads(k, H, cdt), heads(kc, H, cdt), mask, scale)
+    s = _scores(heads(k, H, cdt), gathered_heads(kc, H, Hg, cdt), mask, scale)
     lse = torch.logsumexp(s, dim=-1)
     p = torch.exp(s - lse.clamp_min(torch.finfo(cdt).min).unsqueeze(-1))
-    return _merge(torch.matmul(p, heads(vc, H, cdt))), lse
+    return _merge(torch.matmul(p, gathered_heads(vc, H, Hg, cdt))), lse
 
 
 def combine(parts, dtype):
@@ -58,12 +73,13 @@ def combine(parts, dtype):
     return o.to(dtype), lse
 
 
-def block_bwd(do, k, kc, vc, lse, delta, mask, H: int, scale: float):
+def block_bwd(do, k, kc, vc, lse, delta, mask, H: int, scale: float, Hg=None):
     """Gradients of one column segment given the whole row's ``lse`` and ``delta`` (B, H, R) ->
-    (dk (B, R, H*dh), dq (B, T, H*dh), dv (B, T, H*dv)), compute dtype."""
+    (dk (B, R, H*dh), dq (B, T, Hg*dh), dv (B, T, Hg*dv)), compute dtype; dq / dv summed over each
+    group of row heads."""
     cdt = compute_dtype(k)
-    kh, qh, vh, doh = heads(k, H, cdt), heads(kc, H, cdt), heads(vc, H, cdt), heads(do, H, cdt)
+    kh, qh, vh, doh = heads(k, H, cdt), gathered_heads(kc, H, Hg, cdt), gathered_heads(vc, H, Hg, cdt), heads(do, H, cdt)
     p = torch.exp(_scores(kh, qh, mask, scale) - lse.unsqueeze(-1))
     ds = p * (torch.matmul(doh, vh.transpose(-1, -2)) - delta.unsqueeze(-1)) * scale
-    return (_merge(torch.matmul(ds, qh)), _merge(torch.matmul(ds.transpose(-1, -2), kh)),
-            _merge(torch.matmul(p.transpose(-1, -2), doh)))
+    return (_merge(torch.matmul(ds, qh)), _merge(_fold(torch.matmul(ds.transpose(-1, -2), kh), H, Hg)),
+            _merge(_fold(torch.matmul(p.transpose(-1, -2), doh), H, Hg)))

@@ -89,11 +89,52 @@ def _kernels_take(x: Tensor) -> bool:
     return bool(x.is_cuda and x.dtype in FLASH_DTYPES and _ext.use_hip(x) and hasattr(_ext.ops(), "flash_fwd"))
 
 
-def _hip_ok(k: Tensor, qv: Tensor, H: int) -> bool:
+def _hip_ok(k: Tensor, qv: Tensor, H: int, Hg: Optional[int] = None) -> bool:
     """The HIP kernels take this call: a GPU bf16/fp16/fp32 row side, a supported head dim and a
-    value width equal to the key width (otherwise the torch path runs, as documented)."""
+    value width equal to the key width (otherwise the torch path runs, as documented).  ``Hg``:
+    gathered heads (None: ``H``); ``qv`` is then ``2 * Hg * D`` wide."""
     C = k.shape[-1]
-    return C % H == 0 and C // H in FLASH_HEAD_DIMS and qv.shape[-1] == 2 * C and _kernels_take(k)
+    return (C % H == 0 and C // H in FLASH_HEAD_DIMS and qv.shape[-1] == 2 * (Hg or H) * (C // H)
+            and _kernels_take(k))
+
+
+def gathered_heads_arg(H: int, gathered_heads: Optional[int]) -> Optional[int]:
+    """``gathered_heads`` validated against ``H`` -> None when every row head has its own gathered
+    head (the default), else ``Hg`` with ``H % Hg == 0`` (grouped-query attention: gathered head
+    ``h // (H // Hg)`` serves row head ``h``)."""
+    if gathered_heads is None or int(gathered_heads) == H:
+        return None
+    Hg = int(gathered_heads)
+    if Hg < 1 or H % Hg:
+        raise ValueError(f"num_heads {H} must be a multiple of gathered_heads {gathered_heads}")
+    return Hg
+
+
+def _native_gqa(k: Tensor, H: int) -> bool:
+    """The kernels index a narrower gathered side themselves: the 16-bit families up to head dim
+    128.  Exact fp32, split-bf16 and the wide heads get the gathered heads expanded after the
+    gather and their gradients folded before the reduce-scatter (:func:`_expand_heads`)."""
+    return k.dtype != torch.float32 and k.shape[-1] // H <= 128
+
+
+def _expand_heads(g: Tensor, H: int, Hg: int) -> Tensor:
+    """Packed ``[q | v]`` (..., 2 * Hg * D) -> (..., 2 * H * D): every gathered head repeated for
+    the row heads of its group (one copy)."""
+    D = g.shape[-1] // (2 * Hg)
+    lead = tuple(g.shape[:-1])
+    return g.reshape(*lead, 2, Hg, 1, D).expand(*lead, 2, Hg, H // Hg, D).reshape(*lead, 2 * H * D)
+
+
+def _fold_heads(d: Tensor, H: int, Hg: int, dtype) -> Tensor:
+    """Packed ``[dq | dv]`` (..., 2 * H * D) per row head -> (..., 2 * Hg * D) in ``dtype``: the sum
+    over each group, in fp32 and in head order (deterministic)."""
+    D = d.shape[-1] // (2 * H)
+    lead = tuple(d.shape[:-1])
+    x = d.reshape(*lead, 2, Hg, H // Hg, D)
+    acc = x[..., 0, :].float()
+    for j in range(1, H // Hg):
+        acc = acc + x[..., j, :]
+    return acc.reshape(*lead, 2 * Hg * D).to(dtype)
 
 
 def _prescale_rows(k: Tensor) -> bool:
@@ -102,10 +143,10 @@ def _prescale_rows(k: Tensor) -> bool:
     return bool(FLAGS.prescale and k.numel() % 8 == 0 and k.dtype != torch.float32)
 
 
-def prescale_wanted(k_like: Tensor, qv_like: Tensor, H: int) -> bool:
+def prescale_wanted(k_like: Tensor, qv_like: Tensor, H: int, Hg: Optional[int] = None) -> bool:
     """The HIP path will run on pre-scaled rows for a row side shaped / typed like ``k_like``
     (the condition :meth:`SeqParallelAttention.forward` applies)."""
-    return _hip_ok(k_like, qv_like, H) and _prescale_rows(k_like)
+    return _hip_ok(k_like, qv_like, H, Hg) and _prescale_rows(k_like)
 
 
 # ----------------------------------------------------------------------------------------
@@ -208,21 +249,27 @@ def _as_global(g: Tensor) -> Tensor:
 # ----------------------------------------------------------------------------------------
 # torch path of the per-rank compute (CPU / fallback / testing): layout adapters over _ref
 # ----------------------------------------------------------------------------------------
-def _forward_torch(k, qvg, mask, H, scale):
-    """Whole-row forward from the rank-major gathered (N, B, R, C + Cv): one block, combined
+def _forward_torch(k, qvg, mask, H, scale, Hg=None):
+    """Whole-row forward from the rank-major gathered (N, B, R, Cq + Cv): one block, combined
     alone (a fully masked row comes out NaN)."""
-    C = k.shape[-1]
-    part = _ref.block_fwd(k, _as_global(qvg[..., :C]), _as_global(qvg[..., C:]), mask, H, scale)
+    C = _q_width(k, H, Hg)
+    part = _ref.block_fwd(k, _as_global(qvg[..., :C]), _as_global(qvg[..., C:]), mask, H, scale, Hg)
     return _ref.combine([part], k.dtype)
 
 
-def _segmented_forward_torch(k, qv, mask, H, scale, pending, n, rank):
-    B, R, C = k.shape
+def _q_width(k, H, Hg):
+    """Columns of the ``q`` half of a packed ``[q | v]``: ``Hg`` heads of the row side's head dim."""
+    return k.shape[-1] if not Hg else Hg * (k.shape[-1] // H)
+
+
+def _segmented_forward_torch(k, qv, mask, H, scale, pending, n, rank, Hg=None):
+    B, R = k.shape[:2]
+    C = _q_width(k, H, Hg)
     plan = _segment_plan(n, rank, len(pending.chunks), FLAGS.local_first)
     parts = []
     if FLAGS.local_first:
         own = None if mask is None else _mask_cols(B, R, n, rank, rank + 1, 0, R)(mask)
-        parts.append(_ref.block_fwd(k, qv[..., :C], qv[..., C:], own, H, scale))
+        parts.append(_ref.block_fwd(k, qv[..., :C], qv[..., C:], own, H, scale, Hg))
     gs = []
     for c, (r0, rc) in enumerate(pending.chunks):
         g = pending.wait(c)                                      # (N, B, rc, 2C)
@@ -230,18 +277,18 @@ def _segmented_forward_torch(k, qv, mask, H, scale, pending, n, rank):
         for _, j0, j1 in (p for p in plan if p[0] == c):
             seg = _as_global(g[j0:j1])
             m = None if mask is None else _mask_cols(B, R, n, j0, j1, r0, rc)(mask)
-            parts.append(_ref.block_fwd(k, seg[..., :C], seg[..., C:], m, H, scale))
+            parts.append(_ref.block_fwd(k, seg[..., :C], seg[..., C:], m, H, scale, Hg))
     o, lse = _ref.combine(parts, k.dtype)
     return o, lse, [torch.cat(gs, dim=2) if len(gs) > 1 else gs[0]]
 
 
 def _backward_torch(ctx, do, k, o, lse, qvg):
-    """-> (dk, d[q|v] of this rank's rows) from the rank-major gathered ``qvg`` (N, B, R, C + Cv)."""
-    C = k.shape[-1]
+    """-> (dk, d[q|v] of this rank's rows) from the rank-major gathered ``qvg`` (N, B, R, Cq + Cv)."""
+    C = _q_width(k, ctx.H, ctx.Hg)
     n, B, Rg = qvg.shape[:3]
     delta = _ref.delta(do, o, ctx.H, lse.dtype)
     dk, dq, dv = _ref.block_bwd(do, k, _as_global(qvg[..., :C]), _as_global(qvg[..., C:]), lse, delta, ctx.mask,
-                                ctx.H, ctx.scale)
+                                ctx.H, ctx.scale, ctx.Hg)
     parts = torch.cat([dq, dv], dim=-1).view(B, n, Rg, -1).permute(1, 0, 2, 3).contiguous()  # rank-major
     if k.dtype in (torch.bfloat16, torch.float16) and not FLAGS.grad_fp32:
         parts = parts.to(k.dtype)  # the HIP path's wire dtype (one rounding per partial)
@@ -278,15 +325,18 @@ def _mask_cols(B: int, R: int, n: int, j0: int, j1: int, r0: int, rc: int):
     return lambda m: m.reshape(*m.shape[:-1], n, R)[..., j0:j1, r0:r0 + rc].reshape(*m.shape[:-1], (j1 - j0) * rc)
 
 
-def _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescaled, fp32_mode=0):
+def _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescaled, fp32_mode=0, Hg=None,
+                       expand=False):
     """Forward of a multi-rank step as column segments merged by one log-sum-exp combine:
     the rank's OWN [q|v] block first (it needs no communication, so its partial runs while the
     all-gather is in flight), then each gathered chunk's peer blocks as soon as that chunk
     lands.  Every segment is a subset of a row's columns, so the partials (o normalised over
     the segment, its lse) merge exactly.  -> (o, lse, gathered buffers saved for backward)."""
     if not use_hip:
-        return _segmented_forward_torch(k, qv, mask, H, scale, pending, n, rank)
+        return _segmented_forward_torch(k, qv, mask, H, scale, pending, n, rank, Hg)
     B, R, C = k.shape
+    Cq = _q_width(k, H, Hg)
+    kHg = None if expand else Hg  # gathered heads the kernels see
     chunks = pending.chunks
     local_first = FLAGS.local_first
     plan = _segment_plan(n, rank, len(chunks), local_first)
@@ -301,9 +351,14 @@ def _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescal
     lpart = torch.empty(sum(ns), B, H, R, dtype=torch.float32, device=k.device)
     slots = iter([(sum(ns[:i]), nsi) for i, nsi in enumerate(ns)])  # (first slot, slots) per launch
 
-    def run(seg, mk):  # seg: (B, Tseg, 2C) = [q | v] of the segment's columns
+    def run(seg, mk):  # seg: (B, Tseg, 2 Cq) = [q | v] of the segment's columns
         slot, nsi = next(slots)
-        flash.fwd_partial(k, seg[..., :C], seg[..., C:], mk, H, scale, opart, lpart, slot, nsi, prescaled, fp32_mode)
+        if expand:  # a family without a grouped kernel: the segment's heads repeated (one copy)
+            seg = _expand_heads(seg, H, Hg)
+            flash.fwd_partial(k, seg[..., :C], seg[..., C:], mk, H, scale, opart, lpart, slot, nsi, prescaled, fp32_mode)
+            return
+        flash.fwd_partial(k, seg[..., :Cq], seg[..., Cq:], mk, H, scale, opart, lpart, slot, nsi, prescaled, fp32_mode,
+                          kHg)
 
     if local_first:
         own = _mask_cols(B, R, n, rank, rank + 1, 0, R)
@@ -404,8 +459,8 @@ def _score_buffers(k, H, T, fm, one_kernel, segmented):
     return sbuf, dsbuf, segmented
 
 
-def _whole_forward_hip(k, mask, packed_full, pending, n, H, scale, prescaled, fm, sbuf):
-    """One kernel over the whole gathered side -> (o, lse, the (B, T, 2C) buffer, its packed mask)."""
+def _whole_forward_hip(k, mask, packed_full, pending, n, H, scale, prescaled, fm, sbuf, Hg=None, expand=False):
+    """One kernel over the whole gathered side -> (o, lse, the (B, T, 2 Cq) buffer, its packed mask)."""
     B, R, C = k.shape
     chunks = pending.chunks
     if len(chunks) > 1:  # several gather chunks, one buffer in (chunk, rank, row) order
@@ -415,7 +470,13 @@ def _whole_forward_hip(k, mask, packed_full, pending, n, H, scale, prescaled, fm
     else:
         mk = packed_full if packed_full is not None else _whole_mask(mask, B, R, n, chunks)
         qvg = flash.gathered_to_btc(pending.wait(0))     # (B, T, 2C), a view for B = 1
-    o, lse = flash.fwd(k, qvg[..., :C], qvg[..., C:], mk, H, scale, prescaled=prescaled, fp32_mode=fm, sbuf=sbuf)
+    if expand:  # a family without a grouped kernel: H heads for the kernel, the Hg-wide buffer is kept
+        x = _expand_heads(qvg, H, Hg)
+        o, lse = flash.fwd(k, x[..., :C], x[..., C:], mk, H, scale, prescaled=prescaled, fp32_mode=fm, sbuf=sbuf)
+        return o, lse, qvg, mk
+    Cq = _q_width(k, H, Hg)
+    o, lse = flash.fwd(k, qvg[..., :Cq], qvg[..., Cq:], mk, H, scale, prescaled=prescaled, fp32_mode=fm, sbuf=sbuf,
+                       Hg=Hg)
     return o, lse, qvg, mk
 
 
@@ -488,11 +549,14 @@ def _rows_hip(ctx, do, k, lse, delta, bufs, mks, sbuf, dsbuf, cur):
     per chunk buffer and their sum."""
     H, scale = ctx.H, ctx.scale
     B, R, C = k.shape
+    # (bufs: expanded to H heads by the caller for a family without a grouped kernel)
+    Hg = None if ctx.expand else ctx.Hg
+    Cq = _q_width(k, H, Hg)
     if len(bufs) == 1:
         g = bufs[0]
-        dk = flash.bwd_rows(do, k, g[..., :C], g[..., C:], lse, delta, mks[0], H, scale,
+        dk = flash.bwd_rows(do, k, g[..., :Cq], g[..., Cq:], lse, delta, mks[0], H, scale,
                             nsplit=FLAGS.rows_split, prescaled=ctx.prescaled, fp32_mode=ctx.fp32_mode,
-                            sbuf=sbuf, dsbuf=dsbuf)
+                            sbuf=sbuf, dsbuf=dsbuf, Hg=Hg)
         if sbuf is not None:
             sbuf.record_stream(cur)
         if dsbuf is not None:
@@ -501,8 +565,8 @@ def _rows_hip(ctx, do, k, lse, delta, bufs, mks, sbuf, dsbuf, cur):
     ns = flash.splits(B, R, ctx.comm.world_size * ctx.chunks[0][1], H, True)
     dpart = torch.empty(len(bufs) * ns, B, R, C, dtype=torch.float32, device=k.device)
     for c, (g, mk) in enumerate(zip(bufs, mks)):
-        flash.bwd_rows_partial(do, k, g[..., :C], g[..., C:], lse, delta, mk, H, scale, dpart, c * ns, ns,
-                               ctx.prescaled, ctx.fp32_mode)
+        flash.bwd_rows_partial(do, k, g[..., :Cq], g[..., Cq:], lse, delta, mk, H, scale, dpart, c * ns, ns,
+                               ctx.prescaled, ctx.fp32_mode, Hg)
     return flash.bwd_rows_sum(dpart, H, k)
 
 
@@ -517,6 +581,11 @@ def _backward_hip(ctx, do, k, o, lse, bufs, sbt):
     comm, H, scale, chunks = ctx.comm, ctx.H, ctx.scale, ctx.chunks
     n = comm.world_size
     B, R, C = k.shape
+    Hg, expand = ctx.Hg, ctx.expand
+    Cq = _q_width(k, H, Hg)  # the saved buffers, the wire and d[q|v] are 2 Cq wide
+    if expand:  # a family without a grouped kernel: H heads for the kernels, gradients folded below
+        bufs = [_expand_heads(g, H, Hg) for g in bufs]
+    kHg, kC = (None, C) if expand else (Hg, Cq)  # what the kernels see
     one = len(bufs) == 1  # one gathered buffer: natural order, or chunks permuted (B = 1)
     mks = _backward_masks(ctx, B, R, n, one)
     cur = torch.cuda.current_stream(do.device)
@@ -534,15 +603,18 @@ def _backward_hip(ctx, do, k, o, lse, bufs, sbt):
         ev.record(hi)
         dqv = None
         if n > 1 and len(chunks) > 1 and B == 1:
-            dqv = torch.empty(B, R, 2 * C, dtype=gdt, device=k.device)
+            dqv = torch.empty(B, R, 2 * Cq, dtype=gdt, device=k.device)
         # partials rounded once to the compute dtype in the kernel (XDOT_GRAD_FP32=1
         # keeps fp32): half the epilogue stores and half the reduce-scatter bytes
-        cargs = dict(fp32_out=FLAGS.grad_fp32, prescaled=ctx.prescaled, lse2=lse2, fp32_mode=ctx.fp32_mode)
+        cargs = dict(fp32_out=FLAGS.grad_fp32 or expand, prescaled=ctx.prescaled, lse2=lse2, fp32_mode=ctx.fp32_mode,
+                     Hg=kHg)
 
         def cols(g, mk, **kw):
-            return flash.bwd_cols(do, k, g[..., :C], g[..., C:], o, lse, mk, H, scale, delta, **cargs, **kw)
+            return flash.bwd_cols(do, k, g[..., :kC], g[..., kC:], o, lse, mk, H, scale, delta, **cargs, **kw)
 
-        def scatter(part, r0, rc):  # (B, n*rc, 2C) of one chunk -> its reduce-scatter
+        def scatter(part, r0, rc):  # (B, n*rc, 2 Cq) of one chunk -> its reduce-scatter
+            if expand:  # per-row-head fp32 partials -> the group sums in the wire dtype
+                part = _fold_heads(part, H, Hg, gdt)
             h, oc = _reduce_async(comm, flash.btc_to_rank_major(part, n), None if dqv is None else dqv[:, r0:r0 + rc])
             handles.append(h)
             outs.append(oc)
@@ -589,15 +661,19 @@ class SeqParallelAttention(torch.autograd.Function):
 
     @staticmethod
     @_ext.pinned
-    def forward(ctx, k, qv, mask, H, scale, comm, pending=None, k_prescaled=False, grad_on=True):
+    def forward(ctx, k, qv, mask, H, scale, comm, pending=None, k_prescaled=False, grad_on=True, Hg=None):
         """``k_prescaled``: ``k`` already holds ``rows * scale * log2 e`` (:func:`prescale_wanted`;
         the fused module folds it into the k projection's epilogue).  ``grad_on``: grad mode at the
-        call (inside ``forward`` it is always off, and ``needs_input_grad`` ignores it)."""
-        check_consistent(comm, "seq_parallel_attention", k, qv, H)
+        call (inside ``forward`` it is always off, and ``needs_input_grad`` ignores it).  ``Hg``:
+        gathered heads when fewer than ``H`` (:func:`gathered_heads_arg`); ``qv`` is ``[q | v]`` with
+        ``Hg`` heads each."""
+        check_consistent(comm, "seq_parallel_attention", k, qv, H, Hg or H)
         B, R, C = k.shape
         n, rank = comm.world_size, comm.rank
         T = n * qv.shape[1]
-        use_hip = _hip_ok(k, qv, H)
+        use_hip = _hip_ok(k, qv, H, Hg)
+        # grouped heads in a family without a grouped kernel: expanded after the gather
+        expand = bool(Hg) and use_hip and not _native_gqa(k, H)
         if pending is None:
             pending = _PendingGather(comm, qv, _row_chunks(n, qv.shape[1], use_hip))
         chunks = pending.chunks
@@ -629,14 +705,15 @@ class SeqParallelAttention(torch.autograd.Function):
         if use_hip and k.dtype == torch.float32 and need_bwd:
             sbuf, dsbuf, segmented = _score_buffers(k, H, T, fm, len(chunks) == 1 or B == 1, segmented)
         if segmented:
-            o, lse, bufs = _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescaled, fm)
+            o, lse, bufs = _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescaled, fm, Hg, expand)
             mks = [packed_full] if packed_full is not None else None  # backward packs its own (cached)
         elif use_hip:
-            o, lse, qvg, mk = _whole_forward_hip(k, mask, packed_full, pending, n, H, scale, prescaled, fm, sbuf)
+            o, lse, qvg, mk = _whole_forward_hip(k, mask, packed_full, pending, n, H, scale, prescaled, fm, sbuf, Hg,
+                                                 expand)
             bufs, mks = [qvg], [mk]
         else:
             qvg = pending.wait(0)                            # (N, B, R, 2C)
-            o, lse = _forward_torch(k, qvg, mask, H, scale)
+            o, lse = _forward_torch(k, qvg, mask, H, scale, Hg)
             bufs, mks = [qvg], [mask]
         # the score buffers travel as saved tensors: autograd frees them after the backward unless
         # the graph is retained (a ctx attribute would keep 20-40 GB alive as long as the graph is
@@ -645,6 +722,7 @@ class SeqParallelAttention(torch.autograd.Function):
         ctx.save_for_backward(k, o, lse, *bufs, *sbt)
         ctx.mks, ctx.mask, ctx.chunks, ctx.H, ctx.scale, ctx.comm, ctx.use_hip = mks, mask, chunks, H, scale, comm, use_hip
         ctx.prescaled, ctx.fp32_mode = prescaled, fm
+        ctx.Hg, ctx.expand = Hg, expand
         # (has S buffer, has dS buffer); the in-place mode (S only) is consumed by the first backward
         ctx.sb_kind = (sbuf is not None, dsbuf is not None)
         return o
@@ -660,7 +738,7 @@ class SeqParallelAttention(torch.autograd.Function):
             dk, dqv = _backward_hip(ctx, do, k, o, lse, bufs, sbt)
         else:
             dk, dqv = _backward_torch(ctx, do, k, o, lse, bufs[0])
-        return dk.to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None, None
+        return dk.to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None, None, None
 
 
 def gather_plan(qv_shape, qv: Tensor, comm: _comm.Communicator, chunks: Optional[int] = None):
@@ -698,23 +776,36 @@ def _checked_mask(mask, k: Tensor, T: int):
 
 def seq_parallel_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
                                   comm: Optional[_comm.Communicator] = None,
-                                  pending: Optional["_PendingGather"] = None, k_prescaled: bool = False) -> Tensor:
+                                  pending: Optional["_PendingGather"] = None, k_prescaled: bool = False, *,
+                                  gathered_heads: Optional[int] = None) -> Tensor:
     """Fused sequence-parallel attention with a packed gathered side ``qv = [q | v]`` (B, R, 2C).
+
+    ``gathered_heads``: heads of ``q`` and of ``v`` when fewer than ``num_heads`` (grouped-query
+    attention: gathered head ``h // G`` serves row head ``h``, ``G = num_heads // gathered_heads``);
+    ``q`` is then the first ``gathered_heads * (C // num_heads)`` columns of ``qv``.  Everything that
+    crosses the wire or stays resident for the backward is that much narrower.
 
     ``pending``: the handle of :func:`start_gather` on this ``qv`` (the gather is issued here
     otherwise).  ``k_prescaled``: ``k`` already holds ``rows * scale * log2 e`` (only where
     :func:`prescale_wanted`; the gradient returned for it is w.r.t. the unscaled rows)."""
     comm = comm or _comm.get_comm()
-    if k.dim() != 3 or qv.dim() != 3 or qv.shape[-1] <= k.shape[-1]:
-        raise ValueError("seq_parallel_attention_packed expects k (B, R, C) and qv (B, R, C + Cv)")
+    Hg = gathered_heads_arg(num_heads, gathered_heads)
+    if k.dim() != 3 or qv.dim() != 3 or k.shape[-1] % num_heads or qv.shape[-1] <= _q_width(k, num_heads, Hg):
+        raise ValueError("seq_parallel_attention_packed expects k (B, R, C) and qv (B, R, Cq + Cv) with "
+                         "Cq = gathered_heads * C / num_heads")
+    if Hg and (qv.shape[-1] - _q_width(k, num_heads, Hg)) % Hg:
+        raise ValueError(f"the value half of qv ({qv.shape[-1] - _q_width(k, num_heads, Hg)} columns) does not "
+                         f"divide into {Hg} gathered heads")
     mask = _checked_mask(mask, k, qv.shape[1] * comm.world_size)
     return SeqParallelAttention.apply(k, qv, mask, num_heads, float(scale), comm, pending, bool(k_prescaled),
-                                      torch.is_grad_enabled())
+                                      torch.is_grad_enabled(), Hg)
 
 
 def seq_parallel_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tensor], num_heads: int,
-                           scale: float, comm: Optional[_comm.Communicator] = None, rope=None) -> Tensor:
-    """Fused sequence-parallel attention on projected, head-interleaved (B, R, H*d) tensors.
+                           scale: float, comm: Optional[_comm.Communicator] = None, rope=None, *,
+                           gathered_heads: Optional[int] = None) -> Tensor:
+    """Fused sequence-parallel attention on projected, head-interleaved (B, R, H*d) tensors
+    (``q`` / ``v``: ``gathered_heads * d`` columns when given, grouped-query attention).
 
     ``k``: row side (local rows), ``q``/``v``: gathered side (local shards), ``mask``: bool
     (B, R, T) with True = masked, a :class:`xdot.StructuredMask` (causal / window / lengths / documents; its
@@ -730,5 +821,6 @@ def seq_parallel_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tenso
 
         off = rope.resolve((comm or _comm.get_comm()).rank, k.shape[1])
         k = _rope(k, num_heads, rope, offset=off)
-        q = _rope(q, num_heads, rope, offset=off)
-    return seq_parallel_attention_packed(k, torch.cat([q, v], dim=-1), mask, num_heads, scale, comm)
+        q = _rope(q, gathered_heads_arg(num_heads, gathered_heads) or num_heads, rope, offset=off)
+    return seq_parallel_attention_packed(k, torch.cat([q, v], dim=-1), mask, num_heads, scale, comm,
+                                         gathered_heads=gathered_heads)

@@ -47,7 +47,8 @@ from ..utils.checks import check_consistent
 from ..utils.env import FLAGS
 from ..utils.streams import _on_stream, _side_stream
 from . import _ref
-from .attention import WIDE_F32_NEEDS_SCORES, _checked_mask, _hip_ok, _prescale_rows
+from .attention import (WIDE_F32_NEEDS_SCORES, _checked_mask, _expand_heads, _fold_heads, _hip_ok, _native_gqa,
+                        _prescale_rows, _q_width, gathered_heads_arg)
 
 __all__ = ["RingAttention", "ring_attention", "ring_attention_packed"]
 
@@ -157,10 +158,13 @@ def _bidir() -> bool:
     return FLAGS.ring_bidir
 
 
-def _forward_hip(k, rings, mask, H, scale, n):
+def _forward_hip(k, rings, mask, H, scale, n, Hg=None, expand=False):
     """-> (o, lse, the row side the kernels read (pre-scaled or not: saved for the backward), the
-    packed masks per step and launch, prescaled, fp32 kernel family)"""
+    packed masks per step and launch, prescaled, fp32 kernel family).  ``Hg``: gathered heads when
+    fewer than ``H``; ``expand``: the kernel family has no grouped form, every arriving block's
+    heads are repeated (one copy per block) and the ring slots stay ``Hg`` wide."""
     B, R, C = k.shape
+    Cq = _q_width(k, H, Hg)
     fm = flash.fp32_code(k.dtype)
     prescaled = _prescale_rows(k)
     kk = flash.prescale(k, scale) if prescaled else k.contiguous()
@@ -179,7 +183,12 @@ def _forward_hip(k, rings, mask, H, scale, n):
         for ui, (g, view, tag, _lanes) in enumerate(rings.units(s, mask, R)):
             mk = flash.prepare_mask_cached(mask, B, R, g.shape[1], tag=tag, view=view)
             step.append(mk)
-            flash.fwd_partial(kk, g[..., :C], g[..., C:], mk, H, scale, opart, lpart, 1 + ui * ns, ns, prescaled, fm)
+            if expand:
+                g = _expand_heads(g, H, Hg)
+                flash.fwd_partial(kk, g[..., :C], g[..., C:], mk, H, scale, opart, lpart, 1 + ui * ns, ns, prescaled, fm)
+                continue
+            flash.fwd_partial(kk, g[..., :Cq], g[..., Cq:], mk, H, scale, opart, lpart, 1 + ui * ns, ns, prescaled, fm,
+                              Hg)
         mks.append(step)
         if s < n - 1:
             flash.fwd_merge(opart, lpart, lrun, H)
@@ -189,12 +198,13 @@ def _forward_hip(k, rings, mask, H, scale, n):
     return o, lse, kk, mks, prescaled, fm
 
 
-def _forward_torch(k, qv, rings, mask, H, scale, n):
+def _forward_torch(k, qv, rings, mask, H, scale, n, Hg=None):
     """-> (o, lse, the mask slices per step and lane): a running log-sum-exp merge of the blocks'
     partials, as the kernels' slot 0."""
-    B, R, C = k.shape
+    B, R = k.shape[:2]
+    C = _q_width(k, H, Hg)
     cdt = _ref.compute_dtype(k)
-    acc = torch.zeros(B, H, R, (qv.shape[-1] - C) // H, dtype=cdt, device=k.device)
+    acc = torch.zeros(B, H, R, (qv.shape[-1] - C) // (Hg or H), dtype=cdt, device=k.device)
     lse = torch.full((B, H, R), -float("inf"), dtype=cdt, device=k.device)
     mks: List = []
     for s in range(n):
@@ -203,7 +213,7 @@ def _forward_torch(k, qv, rings, mask, H, scale, n):
         for (_d, a, b), ring in zip(rings.lanes, rings.rings):
             m = _block_mask(mask, ring.src(s), R, a, b)
             step.append(m)
-            ob, lb = _ref.block_fwd(k, ring.cur[..., :C], ring.cur[..., C:], m, H, scale)
+            ob, lb = _ref.block_fwd(k, ring.cur[..., :C], ring.cur[..., C:], m, H, scale, Hg)
             new = torch.logaddexp(lse, lb)
             live = torch.isfinite(new).unsqueeze(-1)
             w_old = torch.where(live, torch.exp(lse - new).unsqueeze(-1), torch.zeros_like(acc[..., :1]))
@@ -222,6 +232,8 @@ def _backward_hip(ctx, do, k, o, lse, rings):
     dk(): the row-side gradient after the last step)"""
     H, scale, n = ctx.H, ctx.scale, ctx.comm.world_size
     B, R, C = k.shape
+    Hg, expand = ctx.Hg, ctx.expand
+    kHg, kC = (None, C) if expand else (Hg, _q_width(k, H, Hg))  # what the kernels see
     lanes = rings.lanes
     cur = torch.cuda.current_stream(do.device)
     ov = FLAGS.ring_overlap
@@ -242,14 +254,20 @@ def _backward_hip(ctx, do, k, o, lse, rings):
         hi.wait_stream(cur)
         with _on_stream(hi, cur):
             for ui, (g, _v, _t, ls) in enumerate(units):
-                c_, _ = flash.bwd_cols(do, k, g[..., :C], g[..., C:], o, lse, ctx.mks[s][ui], H, scale, delta,
-                                       fp32_out=True, prescaled=ctx.prescaled, fp32_mode=ctx.fp32_mode)
+                if expand:  # (one copy per block; the row-side launch below makes its own)
+                    g = _expand_heads(g, H, Hg)
+                c_, _ = flash.bwd_cols(do, k, g[..., :kC], g[..., kC:], o, lse, ctx.mks[s][ui], H, scale, delta,
+                                       fp32_out=True, prescaled=ctx.prescaled, fp32_mode=ctx.fp32_mode, Hg=kHg)
+                if expand:  # the group sums, before the ring accumulator
+                    c_ = _fold_heads(c_, H, Hg, torch.float32)
                 full.append(c_)
                 # a merged launch covers both lanes: lane li's contribution is its row range
                 contribs.extend(c_ if len(ls) == 1 else c_[:, lanes[li][1]:lanes[li][2]] for li in ls)
         for ui, (g, _v, _t, _ls) in enumerate(units):
-            flash.bwd_rows_partial(do, k, g[..., :C], g[..., C:], lse, delta, ctx.mks[s][ui], H, scale, dpart,
-                                   1 + ui * nsr, nsr, ctx.prescaled, ctx.fp32_mode)
+            if expand:
+                g = _expand_heads(g, H, Hg)
+            flash.bwd_rows_partial(do, k, g[..., :kC], g[..., kC:], lse, delta, ctx.mks[s][ui], H, scale, dpart,
+                                   1 + ui * nsr, nsr, ctx.prescaled, ctx.fp32_mode, kHg)
         if s < n - 1:
             _ext.ops().sum_partials_into(dpart, dpart[0])
         cur.wait_stream(hi)
@@ -262,7 +280,7 @@ def _backward_hip(ctx, do, k, o, lse, rings):
 
 def _backward_torch(ctx, do, k, o, lse, rings):
     """As :func:`_backward_hip`, in torch."""
-    C = k.shape[-1]
+    C = _q_width(k, ctx.H, ctx.Hg)
     cdt = lse.dtype
     delta = _ref.delta(do, o, ctx.H, cdt)
     dk = torch.zeros(k.shape, dtype=cdt, device=k.device)
@@ -271,7 +289,7 @@ def _backward_torch(ctx, do, k, o, lse, rings):
         contribs = []
         for li, ring in enumerate(rings.rings):
             dkb, dq, dv = _ref.block_bwd(do, k, ring.cur[..., :C], ring.cur[..., C:], lse, delta, ctx.mks[s][li],
-                                         ctx.H, ctx.scale)
+                                         ctx.H, ctx.scale, ctx.Hg)
             dk.add_(dkb)
             contribs.append(torch.cat([dq, dv], dim=-1))
         return contribs
@@ -284,12 +302,13 @@ class RingAttention(torch.autograd.Function):
 
     @staticmethod
     @_ext.pinned
-    def forward(ctx, k, qv, mask, H, scale, comm):
-        check_consistent(comm, "ring_attention", k, qv, H)
+    def forward(ctx, k, qv, mask, H, scale, comm, Hg=None):
+        check_consistent(comm, "ring_attention", k, qv, H, Hg or H)
         B, R, C = k.shape
         n = comm.world_size
         # (the ring has no score buffer: exact fp32 heads past 256 run the torch path)
-        use_hip = _hip_ok(k, qv, H) and not (k.dtype == torch.float32 and C // H > WIDE_F32_NEEDS_SCORES)
+        use_hip = _hip_ok(k, qv, H, Hg) and not (k.dtype == torch.float32 and C // H > WIDE_F32_NEEDS_SCORES)
+        expand = bool(Hg) and use_hip and not _native_gqa(k, H)
         # a StructuredMask: bound to this rank's rows (packed masks generated per block), or its
         # dense tensor, built once, for the torch path
         mask = resolve_mask(mask, B, R, n * R, comm.rank, use_hip, k.device)
@@ -297,12 +316,13 @@ class RingAttention(torch.autograd.Function):
         rings = _Rings(comm, qv, _bidir())
         prescaled, fm = False, 0
         if use_hip:
-            o, lse, k, mks, prescaled, fm = _forward_hip(k, rings, mask, H, scale, n)
+            o, lse, k, mks, prescaled, fm = _forward_hip(k, rings, mask, H, scale, n, Hg, expand)
         else:
-            o, lse, mks = _forward_torch(k, qv, rings, mask, H, scale, n)
+            o, lse, mks = _forward_torch(k, qv, rings, mask, H, scale, n, Hg)
         ctx.save_for_backward(k, qv, o, lse)
         ctx.mks, ctx.H, ctx.scale, ctx.comm, ctx.use_hip, ctx.prescaled = mks, H, scale, comm, use_hip, prescaled
         ctx.fp32_mode, ctx.bidir = fm, len(rings.lanes) > 1
+        ctx.Hg, ctx.expand = Hg, expand
         return o
 
     @staticmethod
@@ -342,21 +362,28 @@ class RingAttention(torch.autograd.Function):
             acc_h.wait()
             accs = acc_in
         dqv = accs[0] if len(accs) == 1 else torch.cat(accs, dim=1)
-        return dk().to(k.dtype), dqv.to(k.dtype), None, None, None, None
+        return dk().to(k.dtype), dqv.to(k.dtype), None, None, None, None, None
 
 
 def ring_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
-                          comm: Optional[_comm.Communicator] = None) -> Tensor:
-    """Ring sequence-parallel attention with a packed gathered side ``qv = [q | v]`` (B, R, C + Cv);
-    ``mask``: bool (B, R, T) (True = masked), a :class:`xdot.StructuredMask`, or None.  Returns (B, R, Cv) in ``k``'s dtype."""
+                          comm: Optional[_comm.Communicator] = None, *, gathered_heads: Optional[int] = None) -> Tensor:
+    """Ring sequence-parallel attention with a packed gathered side ``qv = [q | v]`` (B, R, Cq + Cv);
+    ``mask``: bool (B, R, T) (True = masked), a :class:`xdot.StructuredMask`, or None.  Returns (B, R, Cv) in ``k``'s dtype.
+    ``gathered_heads``: heads of ``q`` / ``v`` when fewer than ``num_heads`` (grouped-query attention,
+    as :func:`xdot.parallel.attention.seq_parallel_attention_packed`): the ring blocks and the
+    gradient accumulators that ride the ring are that much narrower."""
     comm = comm or _comm.get_comm()
-    if k.dim() != 3 or qv.dim() != 3 or qv.shape[-1] <= k.shape[-1] or qv.shape[:2] != k.shape[:2]:
-        raise ValueError("ring_attention expects k (B, R, C) and qv (B, R, C + Cv) with equal R")
+    Hg = gathered_heads_arg(num_heads, gathered_heads)
+    if k.dim() != 3 or qv.dim() != 3 or k.shape[-1] % num_heads or qv.shape[-1] <= _q_width(k, num_heads, Hg) \
+            or qv.shape[:2] != k.shape[:2]:
+        raise ValueError("ring_attention expects k (B, R, C) and qv (B, R, Cq + Cv) with equal R")
     mask = _checked_mask(mask, k, qv.shape[1] * comm.world_size)
-    return RingAttention.apply(k, qv, mask, num_heads, float(scale), comm)
+    return RingAttention.apply(k, qv, mask, num_heads, float(scale), comm, Hg)
 
 
 def ring_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
-                   comm: Optional[_comm.Communicator] = None) -> Tensor:
-    """:func:`ring_attention_packed` on separate head-interleaved (B, R, H*d) ``k``, ``q``, ``v``."""
-    return ring_attention_packed(k, torch.cat([q, v], dim=-1), mask, num_heads, scale, comm)
+                   comm: Optional[_comm.Communicator] = None, *, gathered_heads: Optional[int] = None) -> Tensor:
+    """:func:`ring_attention_packed` on separate head-interleaved (B, R, H*d) ``k``, ``q``, ``v``
+    (``q`` / ``v``: ``gathered_heads * d`` columns when given)."""
+    return ring_attention_packed(k, torch.cat([q, v], dim=-1), mask, num_heads, scale, comm,
+                                 gathered_heads=gathered_heads)
