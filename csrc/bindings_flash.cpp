@@ -1,8 +1,9 @@
 // xdot — torch bindings of the flash-attention kernels (schemas: TORCH_LIBRARY in bindings.cpp).
 //
 // How many splits a launch takes and whether it runs on the head-heavy grid is decided by plan_fwd /
-// plan_rows / plan_cols, from the host-only models of flash_plan.h and the kernels' own occupancy;
-// the flash_*_plan ops return those functions' answers without launching anything.
+// plan_rows / plan_cols, from the host-only models of flash_plan.h and the occupancy of the very kernel
+// the launcher would pick (the kernel selectors of the family files, flash_launch.h); the flash_*_plan
+// ops return those functions' answers without launching anything.
 #include "bindings_common.h"
 #include "flash_plan.h"
 

@@ -22,7 +22,7 @@
 // Accumulator-as-operand orientation (see flash_fwd.hip): each product is arranged so the
 // following MFMA sums over the accumulator's ROW index, so P and dS feed the next MFMA as
 // packed registers; the one operand that must be transposed is read with ds_read_b64_tr_b16.
-#include "flash_common.h"
+#include "flash_launch.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -720,38 +720,17 @@ static void launch_bwd_rows(const BwdArgs& a, hipStream_t st) {
 }  // namespace fa
 }  // namespace xdot
 
-#define XB_DISPATCH(CALL)                                                                        \
-  if (dt == DT_BF16 && D == 32) { CALL(DT_BF16, 32); return 0; }                                 \
-  if (dt == DT_BF16 && D == 64) { CALL(DT_BF16, 64); return 0; }                                 \
-  if (dt == DT_BF16 && D == 96) { CALL(DT_BF16, 96); return 0; }                                 \
-  if (dt == DT_BF16 && D == 128) { CALL(DT_BF16, 128); return 0; }                               \
-  if (dt == DT_F16 && D == 32) { CALL(DT_F16, 32); return 0; }                                   \
-  if (dt == DT_F16 && D == 64) { CALL(DT_F16, 64); return 0; }                                   \
-  if (dt == DT_F16 && D == 96) { CALL(DT_F16, 96); return 0; }                                   \
-  if (dt == DT_F16 && D == 128) { CALL(DT_F16, 128); return 0; }                                 \
-  return -1;
-
-// the D-templated helpers (prep, row-partial sum) also for the wide heads of flash_wide.hip
-#define XB_DISPATCH_W(CALL)                                                                      \
-  if (dt == DT_BF16 && D == 160) { CALL(DT_BF16, 160); return 0; }                               \
-  if (dt == DT_BF16 && D == 192) { CALL(DT_BF16, 192); return 0; }                               \
-  if (dt == DT_BF16 && D == 256) { CALL(DT_BF16, 256); return 0; }                               \
-  if (dt == DT_BF16 && D == 384) { CALL(DT_BF16, 384); return 0; }                               \
-  if (dt == DT_F16 && D == 160) { CALL(DT_F16, 160); return 0; }                                 \
-  if (dt == DT_F16 && D == 192) { CALL(DT_F16, 192); return 0; }                                 \
-  if (dt == DT_F16 && D == 256) { CALL(DT_F16, 256); return 0; }                                 \
-  if (dt == DT_F16 && D == 384) { CALL(DT_F16, 384); return 0; }                                 \
-  XB_DISPATCH(CALL)
-
 extern "C" int xdot_flash_bwd_delta_launch(const xdot::fa::BwdArgs* a, const void* out, float* delta, int dt, int D,
                                            hipStream_t st) {
   using namespace xdot;
   using namespace xdot::fa;
   if (a->R == 0 || a->B == 0 || a->H == 0) return 0;
   if (dt == DT_F32) return xdot_flash_bwd_prep_f32_launch(a, out, delta, D, st);
-#define XP(DTV, DV) launch_bwd_delta<DTV, DV>(*a, out, delta, st)
-  XB_DISPATCH_W(XP)
-#undef XP
+  // the D-templated helpers (prep, row-partial sum) also for the wide heads of flash_wide.hip
+  return for_dtype16_any_head_dim(dt, D, -1, [&](auto t, auto d) {
+    launch_bwd_delta<decltype(t)::value, decltype(d)::value>(*a, out, delta, st);
+    return 0;
+  });
 }
 
 extern "C" int xdot_flash_bwd_cols_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st) {
@@ -760,9 +739,10 @@ extern "C" int xdot_flash_bwd_cols_launch(const xdot::fa::BwdArgs* a, int dt, in
   if (a->R == 0 || a->B == 0 || a->H == 0 || a->T == 0) return 0;
   if (D > 128) return xdot_flash_wide_cols_launch(a, dt, D, st);  // dV pass + dQ pass
   if (dt == DT_F32) return a->fp32_mode ? xdot_flash_bwd_cols_x3_launch(a, D, st) : xdot_flash_bwd_cols_f32_launch(a, D, st);
-#define XC(DTV, DV) launch_bwd_cols<DTV, DV>(*a, st)
-  XB_DISPATCH(XC)
-#undef XC
+  return for_dtype16_head_dim(dt, D, -1, [&](auto t, auto d) {
+    launch_bwd_cols<decltype(t)::value, decltype(d)::value>(*a, st);
+    return 0;
+  });
 }
 
 extern "C" int xdot_flash_cols_splits(const xdot::fa::BwdArgs* a, int dt, int D, int* sq, int* sv) {
@@ -821,9 +801,10 @@ extern "C" int xdot_flash_bwd_rows_sum_launch(const xdot::fa::BwdArgs* a, int dt
   using namespace xdot::fa;
   if (a->R == 0 || a->B == 0 || a->H == 0) return 0;
   if (dt == DT_F32) return xdot_flash_rows_sum_f32_launch(a, D, st);
-#define XS(DTV, DV) launch_rows_sum<DTV, DV>(*a, st)
-  XB_DISPATCH_W(XS)
-#undef XS
+  return for_dtype16_any_head_dim(dt, D, -1, [&](auto t, auto d) {
+    launch_rows_sum<decltype(t)::value, decltype(d)::value>(*a, st);
+    return 0;
+  });
 }
 
 extern "C" int xdot_flash_bwd_rows_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st) {
@@ -840,7 +821,8 @@ extern "C" int xdot_flash_bwd_rows_launch(const xdot::fa::BwdArgs* a, int dt, in
     if (rc == 0 && a->nsplit > 1 && !a->force_partial) return xdot_flash_rows_sum_f32_launch(a, D, st);
     return rc;
   }
-#define XR(DTV, DV) launch_bwd_rows<DTV, DV>(*a, st)
-  XB_DISPATCH(XR)
-#undef XR
+  return for_dtype16_head_dim(dt, D, -1, [&](auto t, auto d) {
+    launch_bwd_rows<decltype(t)::value, decltype(d)::value>(*a, st);
+    return 0;
+  });
 }

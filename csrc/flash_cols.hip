@@ -1,7 +1,7 @@
 // xdot — software-pipelined gathered-side flash backward kernel for gfx950 (MI355X).
 // (Split from csrc/flash_bwd.hip: that file holds the plain column kernel, the row kernel and
 // the prep / sum kernels; flash_bwd.hip's launcher routes pre-scaled D <= 96 launches here.)
-#include "flash_common.h"
+#include "flash_launch.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -352,21 +352,22 @@ extern "C" int xdot_flash_bwd_cols2_launch(const xdot::fa::BwdArgs* a, int dt, i
   const dim3 grid(((a->T + 127) / 128) * a->B * Hg * ns);
   const int odt = a->dkv16 ? dt : (int)DT_F32;
   const int64_t rows = (int64_t)a->B * a->T;
-#define XC2(DTV, DV)                                                                                   \
-  if (dt == DTV && D == DV) {                                                                          \
-    if (a->G > 1)                                                                                      \
-      hipLaunchKernelGGL((flash_bwd_cols2_kernel<DTV, DV, true>), grid, dim3(256), Cols2Cfg<DV>::LDS, st, *a); \
-    else                                                                                               \
-      hipLaunchKernelGGL((flash_bwd_cols2_kernel<DTV, DV>), grid, dim3(256), Cols2Cfg<DV>::LDS, st, *a); \
-    if (ns > 1) {                                                                                      \
-      xdot_flash_cols_sum_launch(a->cpq, a->dkc, ns, rows, Hg * D, a->ldg, odt, st);                   \
-      xdot_flash_cols_sum_launch(a->cpv, a->dvc, ns, rows, Hg * D, a->ldg, odt, st);                   \
-    }                                                                                                  \
-    return 0;                                                                                          \
-  }
-  XC2(DT_BF16, 32) XC2(DT_BF16, 64) XC2(DT_BF16, 96) XC2(DT_F16, 32) XC2(DT_F16, 64) XC2(DT_F16, 96)
-#undef XC2
-  return -1;
+  return for_dtype16_head_dim(dt, D, -1, [&](auto t, auto d) {
+    constexpr int DTV = decltype(t)::value, DV = decltype(d)::value;
+    if constexpr (DV > 96) {  // D = 128 runs the plain column kernel (flash_bwd.hip)
+      return -1;
+    } else {
+      if (a->G > 1)
+        hipLaunchKernelGGL((flash_bwd_cols2_kernel<DTV, DV, true>), grid, dim3(256), Cols2Cfg<DV>::LDS, st, *a);
+      else
+        hipLaunchKernelGGL((flash_bwd_cols2_kernel<DTV, DV>), grid, dim3(256), Cols2Cfg<DV>::LDS, st, *a);
+      if (ns > 1) {
+        xdot_flash_cols_sum_launch(a->cpq, a->dkc, ns, rows, Hg * D, a->ldg, odt, st);
+        xdot_flash_cols_sum_launch(a->cpv, a->dvc, ns, rows, Hg * D, a->ldg, odt, st);
+      }
+      return 0;
+    }
+  });
 }
 
 // row splits of the pipelined column kernel: XDOT_CSPLIT=n (opt-in); automatic only for grouped heads

@@ -252,18 +252,6 @@ template <int PF, class F> __device__ __forceinline__ void ring_loop(int beg, in
   }
 }
 
-// resident workgroups per CU of one kernel instantiation (256 threads, `lds` bytes), cached
-template <class K> int wg_per_cu(K kern, int lds) {
-  static int v = 0;
-  if (!v) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kern), 256, lds) != hipSuccess || n < 1)
-      n = 1;
-    v = n;
-  }
-  return v;
-}
-
 // Pin MFMA accumulators to AGPRs (an empty asm with an "a" constraint).  Where accumulators and
 // operand fragments together exceed the 256 VGPRs, the allocator otherwise keeps loop-carried
 // accumulators in VGPRs and copies them into AGPRs around every product (2 VALU moves per

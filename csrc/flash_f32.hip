@@ -41,7 +41,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "flash_common.h"
+#include "flash_launch.h"
 
 namespace xdot {
 namespace fa32 {
@@ -950,16 +950,13 @@ template <int D> constexpr int lds_bytes_ds() { return lds_bytes<D>(); }
 }  // namespace fa32
 }  // namespace xdot
 
-#define XF32_DISPATCH(CALL)            \
-  switch (D) {                         \
-    case 32: CALL(32); return 0;       \
-    case 64: CALL(64); return 0;       \
-    case 96: CALL(96); return 0;       \
-    case 128: CALL(128); return 0;     \
-    default: return -1;                \
-  }
-
 namespace {
+namespace fa = xdot::fa;
+namespace fa32 = xdot::fa32;
+using fa::ColsMode;
+using fa::Kern;
+using fa::kern;
+
 // The score-storing forward scatters S directly (three workgroups per CU at D <= 96): exact fp32
 // step 54.6-55.0 -> 53.6-54.0 ms on one box (profiles/r6_fp32.md).  XDOT_F32_FWD_DIRECT=0: the
 // LDS-transposed store at two workgroups per CU.
@@ -967,26 +964,52 @@ bool fwd_direct_store() {
   const char* e = std::getenv("XDOT_F32_FWD_DIRECT");  // read per call (A/B in one process)
   return !(e && *e == '0');
 }
+
+// ---- kernel selectors: the one place each (kernel, LDS) pair of this family is written; the
+// launchers and the planners below both ask them (empty: D is not a head dim of this family) ----
+Kern<fa::FwdArgs> fwd_kern(int D, bool sbuf, bool direct) {
+  return fa::for_head_dim(D, Kern<fa::FwdArgs>{}, [&](auto d) {
+    constexpr int DV = decltype(d)::value;
+    if (!sbuf) return kern<fa32::fwd_kernel<DV, false>, fa32::lds_bytes<DV>()>();
+    return direct ? kern<fa32::fwd_kernel<DV, true, true>, fa32::lds_bytes<DV>()>()
+                  : kern<fa32::fwd_kernel<DV, true>, fa32::lds_bytes_sb<DV>()>();
+  });
+}
+// reads_ds: the score-buffer modes (dS from the column kernel, Q image only)
+Kern<fa::BwdArgs> rows_kern(int D, bool reads_ds) {
+  return fa::for_head_dim(D, Kern<fa::BwdArgs>{}, [&](auto d) {
+    constexpr int DV = decltype(d)::value;
+    return reads_ds ? kern<fa32::bwd_rows_ds_kernel<DV>, 2 * fa32::Cfg<DV>::IMG * 4>()
+                    : kern<fa32::bwd_rows_kernel<DV>, fa32::lds_bytes<DV>()>();
+  });
+}
+// the dQ pass over S / the single pass of the other modes
+Kern<fa::BwdArgs> cols_kern(int D, ColsMode mode) {
+  return fa::for_head_dim(D, Kern<fa::BwdArgs>{}, [&](auto d) {
+    constexpr int DV = decltype(d)::value;
+    switch (mode) {
+      case ColsMode::fused: return kern<fa32::bwd_cols_kernel<DV, true, true, true>, fa32::lds_bytes_ds<DV>()>();
+      case ColsMode::from_s: return kern<fa32::bwd_cols_kernel<DV, true>, fa32::lds_bytes_ds<DV>()>();
+      case ColsMode::ds_only: return kern<fa32::bwd_cols_kernel<DV, false, true>, fa32::lds_bytes_ds<DV>()>();
+      default: return kern<fa32::bwd_cols_kernel<DV, false>, fa32::lds_bytes<DV>()>();
+    }
+  });
+}
+Kern<fa::BwdArgs> dv_kern(int D) {
+  return fa::for_head_dim(D, Kern<fa::BwdArgs>{}, [&](auto d) {
+    constexpr int DV = decltype(d)::value;
+    return kern<fa32::bwd_cols_dv_kernel<DV>, 2 * (fa32::Cfg<DV>::IMG + 32) * 4>();
+  });
+}
 }  // namespace
 
 extern "C" int xdot_flash_fwd_f32_launch(const xdot::fa::FwdArgs* a, int D, hipStream_t st) {
-  using namespace xdot::fa32;
   if (a->R == 0 || a->B == 0 || a->H == 0 || a->prescaled) return a->prescaled ? -1 : 0;
+  const auto k = fwd_kern(D, a->sbuf != nullptr, fwd_direct_store());
+  if (!k) return -1;
   const int nrb = (a->R + 127) / 128;
-  const dim3 grid(a->xrbs > 0 ? 8 * (a->xwhole + a->xrem * a->nsplit) : nrb * a->B * a->H * a->nsplit);
-  if (a->sbuf) {
-    if (fwd_direct_store()) {
-#define L(DV) hipLaunchKernelGGL((fwd_kernel<DV, true, true>), grid, dim3(256), lds_bytes<DV>(), st, *a)
-      XF32_DISPATCH(L)
-#undef L
-    }
-#define L(DV) hipLaunchKernelGGL((fwd_kernel<DV, true>), grid, dim3(256), lds_bytes_sb<DV>(), st, *a)
-    XF32_DISPATCH(L)
-#undef L
-  }
-#define L(DV) hipLaunchKernelGGL((fwd_kernel<DV, false>), grid, dim3(256), lds_bytes<DV>(), st, *a)
-  XF32_DISPATCH(L)
-#undef L
+  k.launch(dim3(a->xrbs > 0 ? 8 * (a->xwhole + a->xrem * a->nsplit) : nrb * a->B * a->H * a->nsplit), st, *a);
+  return 0;
 }
 
 extern "C" int xdot_flash_combine_f32_launch(const xdot::fa::FwdArgs* a, int D, hipStream_t st) {
@@ -1006,149 +1029,82 @@ extern "C" int xdot_flash_bwd_prep_f32_launch(const xdot::fa::BwdArgs* a, const 
                                               hipStream_t st) {
   if (a->R == 0 || a->B == 0 || a->H == 0) return 0;
   const int64_t n = (int64_t)a->B * a->R * a->H;
+  const float* o = reinterpret_cast<const float*>(out);
   if (delta && (D == 32 || D == 64 || D == 96 || D == 128)) {
     const dim3 grid((unsigned)((8 * n + 255) / 256));
-    const float* o = reinterpret_cast<const float*>(out);
     switch (D) {
       case 32: hipLaunchKernelGGL(xdot::fa32::prep8_kernel<32>, grid, dim3(256), 0, st, *a, o, delta); break;
       case 64: hipLaunchKernelGGL(xdot::fa32::prep8_kernel<64>, grid, dim3(256), 0, st, *a, o, delta); break;
       case 96: hipLaunchKernelGGL(xdot::fa32::prep8_kernel<96>, grid, dim3(256), 0, st, *a, o, delta); break;
       default: hipLaunchKernelGGL(xdot::fa32::prep8_kernel<128>, grid, dim3(256), 0, st, *a, o, delta); break;
     }
-    return 0;
+  } else {
+    hipLaunchKernelGGL(xdot::fa32::prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *a, o, delta, D);
   }
-  hipLaunchKernelGGL(xdot::fa32::prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *a,
-                     reinterpret_cast<const float*>(out), delta, D);
   return 0;
 }
 
 extern "C" int xdot_flash_bwd_rows_f32_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st) {
-  using namespace xdot::fa32;
   if (a->R == 0 || a->B == 0 || a->H == 0 || a->T == 0) return 0;
-  if (a->prescaled) return -1;
-  const int nrb = (a->R + 127) / 128;
-  const dim3 grid(nrb * a->B * a->H * a->nsplit);
-  if (a->sbuf || a->dsbuf) {  // score-buffer modes: dS from the column kernel, Q image only
-#define L(DV) hipLaunchKernelGGL(bwd_rows_ds_kernel<DV>, grid, dim3(256), 2 * Cfg<DV>::IMG * 4, st, *a)
-    XF32_DISPATCH(L)
-#undef L
-  }
-#define L(DV) hipLaunchKernelGGL(bwd_rows_kernel<DV>, grid, dim3(256), lds_bytes<DV>(), st, *a)
-  XF32_DISPATCH(L)
-#undef L
+  const auto k = rows_kern(D, a->sbuf || a->dsbuf);
+  if (a->prescaled || !k) return -1;
+  k.launch(dim3(((a->R + 127) / 128) * a->B * a->H * a->nsplit), st, *a);
+  return 0;
 }
 
 extern "C" int xdot_flash_bwd_cols_f32_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st) {
-  using namespace xdot::fa32;
   if (a->R == 0 || a->B == 0 || a->H == 0 || a->T == 0) return 0;
   if (a->prescaled || a->dkv16) return -1;
   const int W = ((a->T + 127) / 128) * a->B * a->H, sq = a->csq > 1 ? a->csq : 1, sv = a->csv > 1 ? a->csv : 1;
   if ((sq > 1 && (!a->cpq || (!a->sbuf && !a->cpv))) || (sv > 1 && !a->cpv) || (D & 3)) return -1;
-  const int64_t rows = (int64_t)a->B * a->T;
-  const int C = a->H * D;
-  // the split partials of one pass, summed into its grad half (fp32, ldg-strided)
-  auto sum_q = [&] {
-    if (sq > 1) xdot_flash_cols_sum_launch(a->cpq, a->dkc, sq, rows, C, a->ldg, xdot::DT_F32, st);
-  };
-  auto sum_v = [&](int s) {
-    if (s > 1) xdot_flash_cols_sum_launch(a->cpv, a->dvc, s, rows, C, a->ldg, xdot::DT_F32, st);
-  };
-  if (a->sbuf && a->sb_passes == 4 && a->xcb > 0) {  // fused pass on the head-heavy grid
+  const ColsMode mode = fa::cols_mode(*a, true);
+  const auto kq = cols_kern(D, mode), kv = dv_kern(D);
+  if (!kq || !kv) return -1;
+  if (mode == ColsMode::fused && a->xcb > 0) {  // fused pass on the head-heavy grid
     if (sq < 2 || !a->cpq || !a->cpv || 8 * a->xcb != W) return -1;
-    const dim3 grid(8 * (a->xwhole + a->xrem * sq));
+    kq.launch(dim3(8 * (a->xwhole + a->xrem * sq)), st, *a);
     const int64_t nt = (int64_t)8 * a->xrem * 128 * (D / 4);
-#define L(DV)                                                                                                  \
-  hipLaunchKernelGGL((bwd_cols_kernel<DV, true, true, true>), grid, dim3(256), lds_bytes_ds<DV>(), st, *a);     \
-  if (nt > 0) {                                                                                                  \
-    hipLaunchKernelGGL(cols_sum_tail_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, *a, a->cpq,   \
-                       reinterpret_cast<float*>(a->dkc), DV);                                                    \
-    hipLaunchKernelGGL(cols_sum_tail_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, *a, a->cpv,   \
-                       reinterpret_cast<float*>(a->dvc), DV);                                                    \
-  }                                                                                                              \
+    if (nt > 0) {
+      hipLaunchKernelGGL(xdot::fa32::cols_sum_tail_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, *a, a->cpq,
+                         reinterpret_cast<float*>(a->dkc), D);
+      hipLaunchKernelGGL(xdot::fa32::cols_sum_tail_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, *a, a->cpv,
+                         reinterpret_cast<float*>(a->dvc), D);
+    }
+    return 0;
+  }
+  // the split partials of one pass, summed into its grad half (fp32, ldg-strided); a single-pass
+  // kernel writes both halves in sq pieces
+  const bool two_pass = mode == ColsMode::from_s;
+  const int64_t rows = (int64_t)a->B * a->T;
+  const int C = a->H * D, nv = two_pass ? sv : sq;
+  fa::run_cols_passes(
+      two_pass, a->sb_passes, a->dsbuf != nullptr, [&] { kq.launch(dim3(W * sq), st, *a); },
+      [&] { kv.launch(dim3(W * sv), st, *a); },
+      [&] {
+        if (sq > 1) xdot_flash_cols_sum_launch(a->cpq, a->dkc, sq, rows, C, a->ldg, xdot::DT_F32, st);
+      },
+      [&] {
+        if (nv > 1) xdot_flash_cols_sum_launch(a->cpv, a->dvc, nv, rows, C, a->ldg, xdot::DT_F32, st);
+      });
   return 0;
-    XF32_DISPATCH(L)
-#undef L
-  }
-  if (a->sbuf && a->sb_passes == 4) {  // fused: dP, dQ and dV in one pass (S -> dS)
-#define L(DV)                                                                                                  \
-  hipLaunchKernelGGL((bwd_cols_kernel<DV, true, true, true>), dim3(W * sq), dim3(256), lds_bytes_ds<DV>(), st, *a); \
-  sum_q();                                                                                                       \
-  sum_v(sq)
-    XF32_DISPATCH(L)
-#undef L
-  }
-  if (a->sbuf) {  // in place: dV from S first, then dQ (S -> dS); with a dS buffer dQ first
-    const int ps = a->sb_passes ? a->sb_passes : 3;
-    const bool dv_first = !a->dsbuf;
-#define LDV(DV) hipLaunchKernelGGL(bwd_cols_dv_kernel<DV>, dim3(W * sv), dim3(256), 2 * (Cfg<DV>::IMG + 32) * 4, st, *a)
-#define LDQ(DV) hipLaunchKernelGGL((bwd_cols_kernel<DV, true>), dim3(W * sq), dim3(256), lds_bytes_ds<DV>(), st, *a)
-#define L(DV)                            \
-  if ((ps & 1) && dv_first) {            \
-    LDV(DV);                             \
-    sum_v(sv);                           \
-  }                                      \
-  if (ps & 2) {                          \
-    LDQ(DV);                             \
-    sum_q();                             \
-  }                                      \
-  if ((ps & 1) && !dv_first) {           \
-    LDV(DV);                             \
-    sum_v(sv);                           \
-  }
-    XF32_DISPATCH(L)
-#undef L
-#undef LDQ
-#undef LDV
-  }
-  if (a->dsbuf) {  // dS-only buffer: recompute S, store dS for the row kernel
-#define L(DV)                                                                                                     \
-  hipLaunchKernelGGL((bwd_cols_kernel<DV, false, true>), dim3(W * sq), dim3(256), lds_bytes_ds<DV>(), st, *a); \
-  sum_q();                                                                                                        \
-  sum_v(sq)
-    XF32_DISPATCH(L)
-#undef L
-  }
-#define L(DV)                                                                                                \
-  hipLaunchKernelGGL((bwd_cols_kernel<DV, false>), dim3(W * sq), dim3(256), lds_bytes<DV>(), st, *a); \
-  sum_q();                                                                                                   \
-  sum_v(sq)
-  XF32_DISPATCH(L)
-#undef L
 }
-
-namespace {
-template <int D> void f32_splits(const xdot::fa::BwdArgs* a, int* sq, int* sv) {
-  using namespace xdot::fa32;
-  const int64_t W = (int64_t)((a->T + 127) / 128) * a->B * a->H;
-  const int NRT = (a->R + 31) / 32, cus = xdot_num_cus();
-  if (a->sbuf && a->sb_passes == 4) {
-    // up to 8 splits priced at 0.4 % each (as the fp32 forward): a split costs the fused pass two
-    // fp32 partial copies of the gathered-side gradient (~0.06 ms at T = 25000), its last-round
-    // tail ~1.4 ms at 4 splits
-    *sq = *sv = xdot::fa::pick_csplit(W, NRT, cus * xdot::fa::wg_per_cu(bwd_cols_kernel<D, true, true, true>, lds_bytes_ds<D>()),
-                                      8, 0.004);
-  } else if (a->sbuf) {
-    *sq = xdot::fa::pick_csplit(W, NRT, cus * xdot::fa::wg_per_cu(bwd_cols_kernel<D, true>, lds_bytes_ds<D>()));
-    *sv = xdot::fa::pick_csplit(W, NRT, cus * xdot::fa::wg_per_cu(bwd_cols_dv_kernel<D>, 2 * (Cfg<D>::IMG + 32) * 4));
-  } else if (a->dsbuf) {
-    *sq = *sv = xdot::fa::pick_csplit(W, NRT, cus * xdot::fa::wg_per_cu(bwd_cols_kernel<D, false, true>, lds_bytes_ds<D>()));
-  } else {
-    *sq = *sv = xdot::fa::pick_csplit(W, NRT, cus * xdot::fa::wg_per_cu(bwd_cols_kernel<D, false>, lds_bytes<D>()));
-  }
-}
-}  // namespace
 
 extern "C" int xdot_flash_cols_splits_f32(const xdot::fa::BwdArgs* a, int D, int* sq, int* sv) {
   *sq = *sv = 1;
   // XDOT_CSPLIT: unset / "auto" = occupancy round model, "0" / "1" = no split, n = n splits (<= 8)
-  const int e = xdot::fa::env_int("XDOT_CSPLIT", 1, 8);
+  const int e = fa::env_int("XDOT_CSPLIT", 1, 8);
   if (e >= 0) {
     *sq = *sv = (a->R + 31) / 32 / e >= 1 ? e : 1;
     return 0;
   }
-#define L(DV) f32_splits<DV>(a, sq, sv)
-  XF32_DISPATCH(L)
-#undef L
+  const ColsMode mode = fa::cols_mode(*a, true);
+  const auto kq = cols_kern(D, mode), kv = dv_kern(D);
+  if (!kq || !kv) return -1;
+  const int64_t W = (int64_t)((a->T + 127) / 128) * a->B * a->H;
+  const int NRT = (a->R + 31) / 32;
+  *sq = mode == ColsMode::fused ? fa::csplit_f32_rows(W, NRT, kq.slots()) : fa::csplit_cols(W, NRT, kq.slots());
+  *sv = mode == ColsMode::from_s ? fa::csplit_cols(W, NRT, kv.slots()) : *sq;
+  return 0;
 }
 
 extern "C" int xdot_flash_rows_sum_f32_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st) {
@@ -1160,45 +1116,19 @@ extern "C" int xdot_flash_rows_sum_f32_launch(const xdot::fa::BwdArgs* a, int D,
 
 // head-heavy grid of the fused column pass (see kernels.h): the round model over 64-row tiles, against sq
 extern "C" int xdot_flash_f32_cols_heavy(const xdot::fa::BwdArgs* a, int D, int sq, int* whole, int* rem, int* split) {
-  using namespace xdot::fa32;
-  if (!xdot::fa::f32_heavy() || !a->sbuf || a->sb_passes != 4 || a->fp32_mode || D > 128) return 0;
-  int occ = 0;
-#define OC(DV) \
-  if (D == DV) occ = xdot::fa::wg_per_cu(bwd_cols_kernel<DV, true, true, true>, lds_bytes_ds<DV>());
-  OC(32) OC(64) OC(96) OC(128)
-#undef OC
+  if (!fa::f32_heavy() || !a->sbuf || a->sb_passes != 4 || a->fp32_mode || D > 128) return 0;
+  const int occ = cols_kern(D, ColsMode::fused).wgs_per_cu();
   const int64_t W = (int64_t)((a->T + 127) / 128) * a->B * a->H, S = (int64_t)occ * (xdot_num_cus() / 8);
-  return occ > 0 && xdot::fa::head_heavy_plan(W, (a->R + 63) / 64, S, std::max(sq, 1), whole, rem, split);
+  return occ > 0 && fa::head_heavy_plan(W, (a->R + 63) / 64, S, std::max(sq, 1), whole, rem, split);
 }
 
 // resident forward workgroups per CU of the exact-fp32 forward the launcher would pick (0: none)
-extern "C" int xdot_flash_f32_fwd_occ(int D, bool sbuf) {
-  using namespace xdot::fa32;
-  int occ = 0;
-#define OC(DV)                                                                                               \
-  if (D == DV)                                                                                               \
-    occ = sbuf ? (fwd_direct_store() ? xdot::fa::wg_per_cu(fwd_kernel<DV, true, true>, lds_bytes<DV>())      \
-                                     : xdot::fa::wg_per_cu(fwd_kernel<DV, true>, lds_bytes_sb<DV>()))        \
-               : xdot::fa::wg_per_cu(fwd_kernel<DV, false>, lds_bytes<DV>());
-  OC(32) OC(64) OC(96) OC(128)
-#undef OC
-  return occ;
-}
+extern "C" int xdot_flash_f32_fwd_occ(int D, bool sbuf) { return fwd_kern(D, sbuf, fwd_direct_store()).wgs_per_cu(); }
 
 // column splits of the exact-fp32 forward (kernel 0) / row-side backward (1), see kernels.h
 extern "C" int xdot_flash_f32_row_splits_exact(int kernel, int D, bool sbuf, int64_t W, int64_t T) {
-  using namespace xdot::fa32;
-  int occ = kernel == 0 ? xdot_flash_f32_fwd_occ(D, sbuf) : 0;
-#define OC(DV)                                                                                      \
-  if (kernel != 0 && D == DV)                                                                       \
-    occ = sbuf ? xdot::fa::wg_per_cu(bwd_rows_ds_kernel<DV>, 2 * Cfg<DV>::IMG * 4)                  \
-               : xdot::fa::wg_per_cu(bwd_rows_kernel<DV>, lds_bytes<DV>());
-  OC(32) OC(64) OC(96) OC(128)
-#undef OC
-  if (!occ) return 0;
-  // the forward's workgroups are long (a 32-column fp32 tile is ~16x a 16-bit one), so a split
-  // costs little beside a part-full last round: up to 32 splits at 0.1 % each (the N=8 rank's 200
-  // row blocks: 19 splits fill five rounds of 768 slots instead of 7 splits in two part-full ones)
-  if (kernel == 0) return xdot::fa::pick_csplit(W, (int)((T + 31) / 32), occ * xdot_num_cus(), 32, 0.001);
-  return xdot::fa::pick_csplit(W, (int)((T + 31) / 32), occ * xdot_num_cus(), 8, 0.004);
+  const int slots = kernel == 0 ? fwd_kern(D, sbuf, fwd_direct_store()).slots() : rows_kern(D, sbuf).slots();
+  if (!slots) return 0;
+  const int n = (int)((T + 31) / 32);
+  return kernel == 0 ? fa::csplit_f32_fwd(W, n, slots) : fa::csplit_f32_rows(W, n, slots);
 }

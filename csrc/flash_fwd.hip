@@ -24,7 +24,7 @@
 //     consumes, plus the natural-log LSE per row for the backward recomputation.
 // Workgroup ids are XCD-remapped so the row blocks that stream the same (b, h) columns share
 // an XCD L2.
-#include "flash_common.h"
+#include "flash_launch.h"
 
 #include <type_traits>
 
@@ -547,13 +547,10 @@ extern "C" int xdot_flash_fwd_combine_launch(const xdot::fa::FwdArgs* a, int dt,
   using namespace xdot::fa;
   if (a->R == 0 || a->B == 0 || a->H == 0) return 0;
   if (dt == DT_F32 && !a->out32) return xdot_flash_combine_f32_launch(a, D, st);
-#define XF(DTV, DV) if (dt == DTV && D == DV) { launch_combine<DTV, DV>(*a, st); return 0; }
-  XF(DT_BF16, 32) XF(DT_BF16, 64) XF(DT_BF16, 96) XF(DT_BF16, 128)
-  XF(DT_F16, 32) XF(DT_F16, 64) XF(DT_F16, 96) XF(DT_F16, 128)
-  XF(DT_BF16, 160) XF(DT_BF16, 192) XF(DT_BF16, 256) XF(DT_BF16, 384)  // wide heads (flash_wide.hip)
-  XF(DT_F16, 160) XF(DT_F16, 192) XF(DT_F16, 256) XF(DT_F16, 384)
-#undef XF
-  return -1;
+  return for_dtype16_any_head_dim(dt, D, -1, [&](auto t, auto d) {  // also the wide heads (flash_wide.hip)
+    launch_combine<decltype(t)::value, decltype(d)::value>(*a, st);
+    return 0;
+  });
 }
 
 extern "C" int xdot_flash_fwd_launch(const xdot::fa::FwdArgs* a, int dt, int D, hipStream_t st) {
@@ -573,9 +570,8 @@ extern "C" int xdot_flash_fwd_launch(const xdot::fa::FwdArgs* a, int dt, int D, 
     if (rc == 0 && a->nsplit > 1 && !a->force_partial) return xdot_flash_combine_f32_launch(a, D, st);
     return rc;
   }
-#define XF(DTV, DV) if (dt == DTV && D == DV) { launch_fwd<DTV, DV>(*a, st); return 0; }
-  XF(DT_BF16, 32) XF(DT_BF16, 64) XF(DT_BF16, 96) XF(DT_BF16, 128)
-  XF(DT_F16, 32) XF(DT_F16, 64) XF(DT_F16, 96) XF(DT_F16, 128)
-#undef XF
-  return -1;
+  return for_dtype16_head_dim(dt, D, -1, [&](auto t, auto d) {
+    launch_fwd<decltype(t)::value, decltype(d)::value>(*a, st);
+    return 0;
+  });
 }

@@ -61,10 +61,9 @@ inline int rows_split(int64_t B, int64_t R, int64_t T, int64_t H) {
 
 // Row splits of a column-side launch: W workgroups of `nrt` 32-row tiles each, `slots` of them
 // resident at once.  Fewest splits minimising ceil(W s / slots) / s (the idle share of the last
-// round), each split >= 16 row tiles, 2 % charged per extra split (partials + their sum).
-// (The fp32 forward / row kernels use it with up to 8 splits at 0.4 % each: their partials are
-// ~1 % of an exact-fp32 kernel's time.)
-inline int pick_csplit(int64_t W, int nrt, int slots, int maxs = 4, double per = 0.02) {
+// round), each split >= 16 tiles, at most `maxs` splits, `per` charged per extra split (partials +
+// their sum).  The kernels go through the csplit_* models below.
+inline int pick_csplit(int64_t W, int nrt, int slots, int maxs, double per) {
   int best = 1;
   double bc = 1e300;
   for (int s = 1; s <= maxs && (s == 1 || nrt / s >= 16); ++s) {
@@ -76,6 +75,23 @@ inline int pick_csplit(int64_t W, int nrt, int slots, int maxs = 4, double per =
   }
   return best;
 }
+
+// The split models of the occupancy-planned kernels: W unsplit workgroups, n tiles (32 wide) of the
+// split dimension, `slots` = resident workgroups of the kernel over the whole GPU.
+// Column side (fp32 and wide row splits of the dQ / dV / recompute passes): up to 4 splits at 2 %
+// each (fp32 partials of the whole gathered-side gradient per split).
+inline int csplit_cols(int64_t W, int n, int slots) { return pick_csplit(W, n, slots, 4, 0.02); }
+// The exact-fp32 forward's workgroups are long (a 32-column fp32 tile is ~16x a 16-bit one), so a
+// split costs little beside a part-full last round: up to 32 splits at 0.1 % each (the N=8 rank's 200
+// row blocks: 19 splits fill five rounds of 768 slots instead of 7 splits in two part-full ones).
+inline int csplit_f32_fwd(int64_t W, int n, int slots) { return pick_csplit(W, n, slots, 32, 0.001); }
+// fp32 row side and split-bf16 forward: up to 8 splits at 0.4 % each (their partials are ~1 % of an
+// fp32 kernel's time).  The fused exact-fp32 column pass is priced the same: a split costs it two
+// fp32 partial copies of the gathered-side gradient (~0.06 ms at T = 25000), its last-round tail
+// ~1.4 ms at 4 splits.
+inline int csplit_f32_rows(int64_t W, int n, int slots) { return pick_csplit(W, n, slots, 8, 0.004); }
+// Wide (D > 128) forward and row side: partials of a wide 16-bit kernel cost ~1 % per split.
+inline int csplit_wide_rows(int64_t W, int n, int slots) { return pick_csplit(W, n, slots, 8, 0.01); }
 
 // Head-heavy grid (the 16-bit and exact-fp32 forward over column tiles, the fused exact-fp32
 // column pass over row tiles; whole-GPU launches).  A uniform split makes every block pay the

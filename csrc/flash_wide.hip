@@ -28,7 +28,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "flash_common.h"
+#include "flash_launch.h"
 
 namespace xdot {
 namespace faw {
@@ -753,146 +753,101 @@ template <class Pl, bool DQ, bool LS, bool AUXS = false> constexpr int cols_lds(
 }  // namespace xdot
 
 // ---- launchers ------------------------------------------------------------------------------
-// D dispatch of the wide family; -1 = not a wide (dtype, D) this file instantiates
-#define XW_DISPATCH(CALL)                                                   \
-  switch (dt * 1000 + D) {                                                  \
-    case xdot::DT_BF16 * 1000 + 160: CALL(xdot::DT_BF16, 160); return 0;   \
-    case xdot::DT_BF16 * 1000 + 192: CALL(xdot::DT_BF16, 192); return 0;   \
-    case xdot::DT_BF16 * 1000 + 256: CALL(xdot::DT_BF16, 256); return 0;   \
-    case xdot::DT_BF16 * 1000 + 384: CALL(xdot::DT_BF16, 384); return 0;   \
-    case xdot::DT_F16 * 1000 + 160: CALL(xdot::DT_F16, 160); return 0;     \
-    case xdot::DT_F16 * 1000 + 192: CALL(xdot::DT_F16, 192); return 0;     \
-    case xdot::DT_F16 * 1000 + 256: CALL(xdot::DT_F16, 256); return 0;     \
-    case xdot::DT_F16 * 1000 + 384: CALL(xdot::DT_F16, 384); return 0;     \
-    case xdot::DT_F32 * 1000 + 160: CALL(xdot::DT_F32, 160); return 0;     \
-    case xdot::DT_F32 * 1000 + 192: CALL(xdot::DT_F32, 192); return 0;     \
-    case xdot::DT_F32 * 1000 + 256: CALL(xdot::DT_F32, 256); return 0;     \
-    case xdot::DT_F32 * 1000 + 384: CALL(xdot::DT_F32, 384); return 0;     \
-    default: return -1;                                                     \
-  }
-
 namespace {
-template <int DT, int D>
-void wide_fwd(const xdot::fa::FwdArgs* a, hipStream_t st) {
-  using namespace xdot::faw;
-  using Pl = Pol<DT, D>;
-  const dim3 grid(((a->R + 127) / 128) * a->B * a->H * a->nsplit);
-  if constexpr (DT == xdot::DT_F32) {
-    if (a->sbuf) {
-      hipLaunchKernelGGL((fwd_kernel<DT, D, true>), grid, dim3(256), fwd_lds<Pl>(), st, *a);
-      return;
-    }
+namespace fa = xdot::fa;
+namespace faw = xdot::faw;
+using fa::Ic;
+using fa::Kern;
+using fa::kern;
+
+// f(Ic<DT>{}, Ic<D>{}) for a (dtype, D) this file instantiates, else `none`
+template <class R, class F> R for_wide(int dt, int D, R none, F&& f) {
+  switch (dt) {
+    case xdot::DT_BF16: return fa::for_wide_head_dim(D, none, [&](auto d) -> R { return f(Ic<xdot::DT_BF16>{}, d); });
+    case xdot::DT_F16: return fa::for_wide_head_dim(D, none, [&](auto d) -> R { return f(Ic<xdot::DT_F16>{}, d); });
+    case xdot::DT_F32: return fa::for_wide_head_dim(D, none, [&](auto d) -> R { return f(Ic<xdot::DT_F32>{}, d); });
+    default: return none;
   }
-  hipLaunchKernelGGL((fwd_kernel<DT, D, false>), grid, dim3(256), fwd_lds<Pl>(), st, *a);
 }
 
 // fp32 D > 256 has no recompute variant (three D-wide register sets): it needs the score buffer
 template <int DT, int D> constexpr bool recompute_ok() { return DT != xdot::DT_F32 || D <= 256; }
 
-template <int DT, int D>
-int wide_rows(const xdot::fa::BwdArgs* a, hipStream_t st) {
-  using namespace xdot::faw;
-  using Pl = Pol<DT, D>;
-  const dim3 grid(((a->R + 127) / 128) * a->B * a->H * a->nsplit);
-  if constexpr (DT == xdot::DT_F32) {
-    if (a->sbuf) {
-      hipLaunchKernelGGL((bwd_rows_kernel<DT, D, true>), grid, dim3(256), (rows_lds<Pl, true>()), st, *a);
-      return 0;
-    }
-  }
-  if constexpr (recompute_ok<DT, D>()) {
-    hipLaunchKernelGGL((bwd_rows_kernel<DT, D, false>), grid, dim3(256), (rows_lds<Pl, false>()), st, *a);
-    return 0;
-  }
-  return -2;
+// ---- kernel selectors: the one place each (kernel, LDS) pair of this family is written; the
+// launchers and xdot_flash_wide_splits both ask them.  sbuf counts for fp32 only.  Empty: not a wide
+// (dtype, D); bwd_kern also for fp32 D > 256 without the score buffer (the forward runs there) ----
+Kern<fa::FwdArgs> fwd_kern(int dt, int D, bool sbuf) {
+  return for_wide(dt, D, Kern<fa::FwdArgs>{}, [&](auto t, auto d) {
+    constexpr int DT = decltype(t)::value, DV = decltype(d)::value;
+    using Pl = faw::Pol<DT, DV>;
+    if constexpr (DT == xdot::DT_F32)
+      if (sbuf) return kern<faw::fwd_kernel<DT, DV, true>, faw::fwd_lds<Pl>()>();
+    return kern<faw::fwd_kernel<DT, DV, false>, faw::fwd_lds<Pl>()>();
+  });
 }
-
-template <int DT, int D>
-int wide_cols(const xdot::fa::BwdArgs* a, hipStream_t st) {
-  using namespace xdot::faw;
-  using Pl = Pol<DT, D>;
-  const int W = ((a->T + 127) / 128) * a->B * a->H, sq = a->csq > 1 ? a->csq : 1, sv = a->csv > 1 ? a->csv : 1;
-  if ((sq > 1 && !a->cpq) || (sv > 1 && !a->cpv)) return -1;
-  const int odt = a->dkv16 ? DT : (int)xdot::DT_F32;
-  const int64_t rows = (int64_t)a->B * a->T;
-  // split partials of a pass summed into its grad half (output dtype)
-  auto fin = [&](bool dq) {
-    const int s = dq ? sq : sv;
-    if (s > 1) xdot_flash_cols_sum_launch(dq ? a->cpq : a->cpv, dq ? a->dkc : a->dvc, s, rows, a->H * D, a->ldg, odt, st);
-  };
-  auto dvp = [&](auto LSC) {
-    constexpr bool LSV = decltype(LSC)::value;
-    hipLaunchKernelGGL((bwd_cols_kernel<DT, D, false, LSV>), dim3(W * sv), dim3(256), (cols_lds<Pl, false, LSV, aux_in_slack<DT, D, false, LSV>()>()), st, *a);
-    fin(false);
-  };
-  auto dqp = [&](auto LSC) {
-    constexpr bool LSV = decltype(LSC)::value;
-    hipLaunchKernelGGL((bwd_cols_kernel<DT, D, true, LSV>), dim3(W * sq), dim3(256), (cols_lds<Pl, true, LSV>()), st, *a);
-    fin(true);
-  };
-  if constexpr (DT == xdot::DT_F32) {
-    if (a->sbuf) {  // in place: dV first (the dQ pass overwrites S with dS); with a dS buffer dQ first
-      const int ps = a->sb_passes ? a->sb_passes : 3;
-      const bool dv_first = !a->dsbuf;
-      if ((ps & 1) && dv_first) dvp(std::true_type{});
-      if (ps & 2) dqp(std::true_type{});
-      if ((ps & 1) && !dv_first) dvp(std::true_type{});
-      return 0;
+// the backward roles, numbered as xdot_flash_wide_splits numbers its kernels
+enum WideRole { WIDE_ROWS = 1, WIDE_DQ = 2, WIDE_DV = 3 };
+Kern<fa::BwdArgs> bwd_kern(int role, int dt, int D, bool sbuf) {
+  return for_wide(dt, D, Kern<fa::BwdArgs>{}, [&](auto t, auto d) -> Kern<fa::BwdArgs> {
+    constexpr int DT = decltype(t)::value, DV = decltype(d)::value;
+    using Pl = faw::Pol<DT, DV>;
+    if constexpr (DT == xdot::DT_F32) {
+      if (sbuf) {  // S / dS from the score buffer
+        if (role == WIDE_ROWS) return kern<faw::bwd_rows_kernel<DT, DV, true>, faw::rows_lds<Pl, true>()>();
+        if (role == WIDE_DQ) return kern<faw::bwd_cols_kernel<DT, DV, true, true>, faw::cols_lds<Pl, true, true>()>();
+        return kern<faw::bwd_cols_kernel<DT, DV, false, true>,
+                    faw::cols_lds<Pl, false, true, faw::aux_in_slack<DT, DV, false, true>()>()>();
+      }
     }
-  }
-  if constexpr (recompute_ok<DT, D>()) {
-    dvp(std::false_type{});
-    dqp(std::false_type{});
-    return 0;
-  }
-  return -2;
-}
-
-// occupancy (workgroups per CU) of a wide instantiation: kernel 0 forward, 1 row side, 2 / 3
-// the column side's dQ / dV pass
-template <int DT, int D>
-int wide_occ(int kernel, bool sbuf) {
-  using namespace xdot::faw;
-  using xdot::fa::wg_per_cu;
-  using Pl = Pol<DT, D>;
-  const bool sb = DT == xdot::DT_F32 && sbuf;
-  if constexpr (DT == xdot::DT_F32) {
-    if (sb) {
-      if (kernel == 0) return wg_per_cu(fwd_kernel<DT, D, true>, fwd_lds<Pl>());
-      if (kernel == 1) return wg_per_cu(bwd_rows_kernel<DT, D, true>, rows_lds<Pl, true>());
-      if (kernel == 2) return wg_per_cu(bwd_cols_kernel<DT, D, true, true>, cols_lds<Pl, true, true>());
-      return wg_per_cu(bwd_cols_kernel<DT, D, false, true>, cols_lds<Pl, false, true>());
+    if constexpr (recompute_ok<DT, DV>()) {
+      if (role == WIDE_ROWS) return kern<faw::bwd_rows_kernel<DT, DV, false>, faw::rows_lds<Pl, false>()>();
+      if (role == WIDE_DQ) return kern<faw::bwd_cols_kernel<DT, DV, true, false>, faw::cols_lds<Pl, true, false>()>();
+      return kern<faw::bwd_cols_kernel<DT, DV, false, false>,
+                  faw::cols_lds<Pl, false, false, faw::aux_in_slack<DT, DV, false, false>()>()>();
     }
-  }
-  if constexpr (recompute_ok<DT, D>()) {
-    if (kernel == 0) return wg_per_cu(fwd_kernel<DT, D, false>, fwd_lds<Pl>());
-    if (kernel == 1) return wg_per_cu(bwd_rows_kernel<DT, D, false>, rows_lds<Pl, false>());
-    if (kernel == 2) return wg_per_cu(bwd_cols_kernel<DT, D, true, false>, cols_lds<Pl, true, false>());
-    return wg_per_cu(bwd_cols_kernel<DT, D, false, false>, cols_lds<Pl, false, false, aux_in_slack<DT, D, false, false>()>());
-  }
-  return 0;
+    return {};
+  });
 }
 }  // namespace
 
 extern "C" int xdot_flash_wide_fwd_launch(const xdot::fa::FwdArgs* a, int dt, int D, hipStream_t st) {
   if (a->R == 0 || a->B == 0 || a->H == 0) return 0;
-#define L(DTV, DV) wide_fwd<DTV, DV>(a, st)
-  XW_DISPATCH(L)
-#undef L
+  const auto k = fwd_kern(dt, D, a->sbuf != nullptr);
+  if (!k) return -1;
+  k.launch(dim3(((a->R + 127) / 128) * a->B * a->H * a->nsplit), st, *a);
+  return 0;
 }
 
 extern "C" int xdot_flash_wide_rows_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st) {
   if (a->R == 0 || a->B == 0 || a->H == 0 || a->T == 0) return 0;
-#define L(DTV, DV) return wide_rows<DTV, DV>(a, st)
-  XW_DISPATCH(L)
-#undef L
+  const auto k = bwd_kern(WIDE_ROWS, dt, D, a->sbuf != nullptr);
+  if (!k) return -1;
+  k.launch(dim3(((a->R + 127) / 128) * a->B * a->H * a->nsplit), st, *a);
+  return 0;
 }
 
 extern "C" int xdot_flash_wide_cols_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st) {
   if (a->R == 0 || a->B == 0 || a->H == 0 || a->T == 0) return 0;
-#define L(DTV, DV) return wide_cols<DTV, DV>(a, st)
-  XW_DISPATCH(L)
-#undef L
+  const bool sb = dt == xdot::DT_F32 && a->sbuf;
+  const auto kq = bwd_kern(WIDE_DQ, dt, D, sb), kv = bwd_kern(WIDE_DV, dt, D, sb);
+  if (!kq || !kv) return -1;
+  const int W = ((a->T + 127) / 128) * a->B * a->H, sq = a->csq > 1 ? a->csq : 1, sv = a->csv > 1 ? a->csv : 1;
+  if ((sq > 1 && !a->cpq) || (sv > 1 && !a->cpv)) return -1;
+  const int odt = a->dkv16 ? dt : (int)xdot::DT_F32;
+  const int64_t rows = (int64_t)a->B * a->T;
+  // always two passes; from the score buffer in the order of sb_passes / the dS buffer (the dQ pass
+  // overwrites S with dS in place), recomputing: dV, then dQ.  The split partials of a pass are summed
+  // into its grad half (output dtype)
+  fa::run_cols_passes(
+      true, sb ? a->sb_passes : 3, sb && a->dsbuf, [&] { kq.launch(dim3(W * sq), st, *a); },
+      [&] { kv.launch(dim3(W * sv), st, *a); },
+      [&] {
+        if (sq > 1) xdot_flash_cols_sum_launch(a->cpq, a->dkc, sq, rows, a->H * D, a->ldg, odt, st);
+      },
+      [&] {
+        if (sv > 1) xdot_flash_cols_sum_launch(a->cpv, a->dvc, sv, rows, a->H * D, a->ldg, odt, st);
+      });
+  return 0;
 }
 
 // Split counts of the wide kernels from their own occupancy (one workgroup per CU at these
@@ -901,31 +856,14 @@ extern "C" int xdot_flash_wide_cols_launch(const xdot::fa::BwdArgs* a, int dt, i
 // of the split dimension.
 extern "C" int xdot_flash_wide_splits(int kernel, int dt, int D, bool sbuf, int64_t W, int64_t n) {
   // XDOT_WIDE_SPLIT: unset / auto = the round model, 0 = the caller's old model, n = forced
-  const int e = xdot::fa::env_int("XDOT_WIDE_SPLIT", 0);
+  const int e = fa::env_int("XDOT_WIDE_SPLIT", 0);
   if (e == 0) return kernel >= 2 ? 1 : 0;
   if (e > 0) return (int)std::min<int64_t>(e, n);
-  int occ = 0;
-#define L(DTV, DV) occ = wide_occ<DTV, DV>(kernel, sbuf); break
-  switch (dt * 1000 + D) {
-    case xdot::DT_BF16 * 1000 + 160: L(xdot::DT_BF16, 160);
-    case xdot::DT_BF16 * 1000 + 192: L(xdot::DT_BF16, 192);
-    case xdot::DT_BF16 * 1000 + 256: L(xdot::DT_BF16, 256);
-    case xdot::DT_BF16 * 1000 + 384: L(xdot::DT_BF16, 384);
-    case xdot::DT_F16 * 1000 + 160: L(xdot::DT_F16, 160);
-    case xdot::DT_F16 * 1000 + 192: L(xdot::DT_F16, 192);
-    case xdot::DT_F16 * 1000 + 256: L(xdot::DT_F16, 256);
-    case xdot::DT_F16 * 1000 + 384: L(xdot::DT_F16, 384);
-    case xdot::DT_F32 * 1000 + 160: L(xdot::DT_F32, 160);
-    case xdot::DT_F32 * 1000 + 192: L(xdot::DT_F32, 192);
-    case xdot::DT_F32 * 1000 + 256: L(xdot::DT_F32, 256);
-    case xdot::DT_F32 * 1000 + 384: L(xdot::DT_F32, 384);
-    default: break;
-  }
-#undef L
-  if (occ <= 0) return kernel >= 2 ? 1 : 0;
-  // forward / row side: partials of a wide 16-bit kernel cost ~1 % per split; the column side's
-  // row splits are capped at 4 (fp32 partials of the whole D-wide gradient per split)
-  return kernel >= 2 ? xdot::fa::pick_csplit(W, (int)n, occ * xdot_num_cus(), 4, 0.02)
-                     : xdot::fa::pick_csplit(W, (int)n, occ * xdot_num_cus(), 8, 0.01);
+  // A configuration without backward kernels (fp32 D > 256 with no score buffer: forward only) keeps
+  // the caller's model for its forward too, as it always has: nobody has measured this model there
+  const bool planned = (bool)bwd_kern(WIDE_ROWS, dt, D, sbuf);
+  const int slots = !planned ? 0 : kernel == 0 ? fwd_kern(dt, D, sbuf).slots() : bwd_kern(kernel, dt, D, sbuf).slots();
+  if (slots <= 0) return kernel >= 2 ? 1 : 0;
+  // the column side's row splits are capped at 4 (fp32 partials of the whole D-wide gradient per split)
+  return kernel >= 2 ? fa::csplit_cols(W, (int)n, slots) : fa::csplit_wide_rows(W, (int)n, slots);
 }
-

@@ -26,7 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "flash_common.h"
+#include "flash_launch.h"
 
 namespace xdot {
 namespace fa3 {
@@ -757,159 +757,109 @@ __global__ __launch_bounds__(256, 2) void bwd_rows_ds_kernel(BwdArgs a) {
 }  // namespace fa3
 }  // namespace xdot
 
-#define X3_DISPATCH(CALL)              \
-  switch (D) {                         \
-    case 32: CALL(32); return 0;       \
-    case 64: CALL(64); return 0;       \
-    case 96: CALL(96); return 0;       \
-    case 128: CALL(128); return 0;     \
-    default: return -1;                \
-  }
-
-extern "C" int xdot_flash_fwd_x3_launch(const xdot::fa::FwdArgs* a, int D, hipStream_t st) {
-  using namespace xdot::fa3;
-  if (a->R == 0 || a->B == 0 || a->H == 0 || a->prescaled) return a->prescaled ? -1 : 0;
-  const dim3 grid(((a->R + 127) / 128) * a->B * a->H * a->nsplit);
-  if (a->sbuf) {
-#define L(DV) hipLaunchKernelGGL((fwd_kernel<DV, true>), grid, dim3(256), FwdL<DV>::LDS_SB, st, *a)
-    X3_DISPATCH(L)
-#undef L
-  }
-#define L(DV) hipLaunchKernelGGL((fwd_kernel<DV, false>), grid, dim3(256), FwdL<DV>::LDS, st, *a)
-  X3_DISPATCH(L)
-#undef L
-}
-
-extern "C" int xdot_flash_bwd_rows_x3_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st) {
-  using namespace xdot::fa3;
-  if (a->R == 0 || a->B == 0 || a->H == 0 || a->T == 0) return 0;
-  if (a->prescaled) return -1;
-  const dim3 grid(((a->R + 127) / 128) * a->B * a->H * a->nsplit);
-  if (a->sbuf || a->dsbuf) {  // score-buffer modes: dS from the column kernel, Q image only
-#define L(DV) hipLaunchKernelGGL(bwd_rows_ds_kernel<DV>, grid, dim3(256), RowsDsL<DV>::LDS, st, *a)
-    X3_DISPATCH(L)
-#undef L
-  }
-#define L(DV) hipLaunchKernelGGL(bwd_rows_kernel<DV>, grid, dim3(256), RowsL<DV>::LDS, st, *a)
-  X3_DISPATCH(L)
-#undef L
-}
-
 namespace {
-// dS-only column launch: the recompute kernel's two-image stages plus the transpose tiles exceed
-// the 160 KiB of LDS at D = 128 (refused: -1)
-template <int D> int launch_cols_ds(const xdot::fa::BwdArgs& a, dim3 grid, hipStream_t st) {
-  using namespace xdot::fa3;
-  if constexpr (ColsL<D, false, true>::LDS > 160 * 1024) {
-    (void)a; (void)grid; (void)st;
-    return -1;
-  } else {
-    hipLaunchKernelGGL((bwd_cols_kernel<D, false, true>), grid, dim3(256), (ColsL<D, false, true>::LDS), st, a);
-    return 0;
-  }
+namespace fa = xdot::fa;
+namespace fa3 = xdot::fa3;
+using fa::ColsMode;
+using fa::Kern;
+using fa::kern;
+
+// ---- kernel selectors: the one place each (kernel, LDS) pair of this family is written; the
+// launchers and the planners below both ask them (empty: no such kernel) ----
+Kern<fa::FwdArgs> fwd_kern(int D, bool sbuf) {
+  return fa::for_head_dim(D, Kern<fa::FwdArgs>{}, [&](auto d) {
+    constexpr int DV = decltype(d)::value;
+    return sbuf ? kern<fa3::fwd_kernel<DV, true>, fa3::FwdL<DV>::LDS_SB>() : kern<fa3::fwd_kernel<DV, false>, fa3::FwdL<DV>::LDS>();
+  });
+}
+// reads_ds: the score-buffer modes (dS from the column kernel, Q image only)
+Kern<fa::BwdArgs> rows_kern(int D, bool reads_ds) {
+  return fa::for_head_dim(D, Kern<fa::BwdArgs>{}, [&](auto d) {
+    constexpr int DV = decltype(d)::value;
+    return reads_ds ? kern<fa3::bwd_rows_ds_kernel<DV>, fa3::RowsDsL<DV>::LDS>() : kern<fa3::bwd_rows_kernel<DV>, fa3::RowsL<DV>::LDS>();
+  });
+}
+// the dQ pass over S / the single pass of the other modes.  dS-only at D = 128: the recompute
+// kernel's two-image stages plus the transpose tiles exceed the 160 KiB of LDS (empty)
+Kern<fa::BwdArgs> cols_kern(int D, ColsMode mode) {
+  return fa::for_head_dim(D, Kern<fa::BwdArgs>{}, [&](auto d) {
+    constexpr int DV = decltype(d)::value;
+    switch (mode) {
+      case ColsMode::from_s: return kern<fa3::bwd_cols_kernel<DV, true>, fa3::ColsL<DV, true>::LDS>();
+      case ColsMode::ds_only: return kern<fa3::bwd_cols_kernel<DV, false, true>, fa3::ColsL<DV, false, true>::LDS>();
+      default: return kern<fa3::bwd_cols_kernel<DV, false>, fa3::ColsL<DV, false>::LDS>();
+    }
+  });
+}
+Kern<fa::BwdArgs> dv_kern(int D) {
+  return fa::for_head_dim(D, Kern<fa::BwdArgs>{}, [&](auto d) {
+    constexpr int DV = decltype(d)::value;
+    return kern<fa3::bwd_cols_dv_kernel<DV>, fa3::DvL<DV>::LDS>();
+  });
 }
 }  // namespace
 
+extern "C" int xdot_flash_fwd_x3_launch(const xdot::fa::FwdArgs* a, int D, hipStream_t st) {
+  if (a->R == 0 || a->B == 0 || a->H == 0 || a->prescaled) return a->prescaled ? -1 : 0;
+  const auto k = fwd_kern(D, a->sbuf != nullptr);
+  if (!k) return -1;
+  k.launch(dim3(((a->R + 127) / 128) * a->B * a->H * a->nsplit), st, *a);
+  return 0;
+}
+
+extern "C" int xdot_flash_bwd_rows_x3_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st) {
+  if (a->R == 0 || a->B == 0 || a->H == 0 || a->T == 0) return 0;
+  const auto k = rows_kern(D, a->sbuf || a->dsbuf);
+  if (a->prescaled || !k) return -1;
+  k.launch(dim3(((a->R + 127) / 128) * a->B * a->H * a->nsplit), st, *a);
+  return 0;
+}
+
 extern "C" int xdot_flash_bwd_cols_x3_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st) {
-  using namespace xdot::fa3;
   if (a->R == 0 || a->B == 0 || a->H == 0 || a->T == 0) return 0;
   if (a->prescaled || a->dkv16) return -1;
   const int W = ((a->T + 127) / 128) * a->B * a->H, sq = a->csq > 1 ? a->csq : 1, sv = a->csv > 1 ? a->csv : 1;
   if ((sq > 1 && (!a->cpq || (!a->sbuf && !a->cpv))) || (sv > 1 && !a->cpv) || (D & 3)) return -1;
+  const ColsMode mode = fa::cols_mode(*a, false);
+  const auto kq = cols_kern(D, mode), kv = dv_kern(D);
+  if (!kq || !kv) return -1;
+  // split partials of a pass summed into its grad half (BwdArgs::csq / csv); a single-pass kernel
+  // writes both halves in sq pieces
+  const bool two_pass = mode == ColsMode::from_s;
   const int64_t rows = (int64_t)a->B * a->T;
-  const int C = a->H * D;
-  auto sum_q = [&] {  // split partials of a pass summed into its grad half (BwdArgs::csq / csv)
-    if (sq > 1) xdot_flash_cols_sum_launch(a->cpq, a->dkc, sq, rows, C, a->ldg, xdot::DT_F32, st);
-  };
-  auto sum_v = [&](int s) {
-    if (s > 1) xdot_flash_cols_sum_launch(a->cpv, a->dvc, s, rows, C, a->ldg, xdot::DT_F32, st);
-  };
-  if (a->sbuf) {  // in place: dV from S first, then dQ (S -> dS); with a dS buffer dQ first
-    const int ps = a->sb_passes ? a->sb_passes : 3;
-    const bool dv_first = !a->dsbuf;
-#define LDV(DV) hipLaunchKernelGGL(bwd_cols_dv_kernel<DV>, dim3(W * sv), dim3(256), DvL<DV>::LDS, st, *a)
-#define LDQ(DV) hipLaunchKernelGGL((bwd_cols_kernel<DV, true>), dim3(W * sq), dim3(256), (ColsL<DV, true>::LDS), st, *a)
-#define L(DV)                            \
-  if ((ps & 1) && dv_first) {            \
-    LDV(DV);                             \
-    sum_v(sv);                           \
-  }                                      \
-  if (ps & 2) {                          \
-    LDQ(DV);                             \
-    sum_q();                             \
-  }                                      \
-  if ((ps & 1) && !dv_first) {           \
-    LDV(DV);                             \
-    sum_v(sv);                           \
-  }
-    X3_DISPATCH(L)
-#undef L
-#undef LDQ
-#undef LDV
-  }
-  if (a->dsbuf) {  // dS-only buffer: recompute S, store dS for the row kernel (D <= 96: LDS)
-    int rc = -1;
-    switch (D) {
-      case 32: rc = launch_cols_ds<32>(*a, dim3(W * sq), st); break;
-      case 64: rc = launch_cols_ds<64>(*a, dim3(W * sq), st); break;
-      case 96: rc = launch_cols_ds<96>(*a, dim3(W * sq), st); break;
-      case 128: rc = launch_cols_ds<128>(*a, dim3(W * sq), st); break;
-      default: break;
-    }
-    if (rc) return rc;
-    sum_q();
-    sum_v(sq);
-    return 0;
-  }
-#define L(DV)                                                                                                          \
-  hipLaunchKernelGGL((bwd_cols_kernel<DV, false>), dim3(W * sq), dim3(256), (ColsL<DV, false>::LDS), st, *a); \
-  sum_q();                                                                                                             \
-  sum_v(sq)
-  X3_DISPATCH(L)
-#undef L
+  const int C = a->H * D, nv = two_pass ? sv : sq;
+  fa::run_cols_passes(
+      two_pass, a->sb_passes, a->dsbuf != nullptr, [&] { kq.launch(dim3(W * sq), st, *a); },
+      [&] { kv.launch(dim3(W * sv), st, *a); },
+      [&] {
+        if (sq > 1) xdot_flash_cols_sum_launch(a->cpq, a->dkc, sq, rows, C, a->ldg, xdot::DT_F32, st);
+      },
+      [&] {
+        if (nv > 1) xdot_flash_cols_sum_launch(a->cpv, a->dvc, nv, rows, C, a->ldg, xdot::DT_F32, st);
+      });
+  return 0;
 }
-
-namespace {
-template <int D> void x3_splits(const xdot::fa::BwdArgs* a, int* sq, int* sv) {
-  using namespace xdot::fa3;
-  const int64_t W = (int64_t)((a->T + 127) / 128) * a->B * a->H;
-  const int NRT = (a->R + 31) / 32, cus = xdot_num_cus();
-  if (a->sbuf) {
-    *sq = xdot::fa::pick_csplit(W, NRT, cus * xdot::fa::wg_per_cu(bwd_cols_kernel<D, true>, ColsL<D, true>::LDS));
-    *sv = xdot::fa::pick_csplit(W, NRT, cus * xdot::fa::wg_per_cu(bwd_cols_dv_kernel<D>, DvL<D>::LDS));
-  } else if (a->dsbuf) {
-    *sq = *sv =
-        xdot::fa::pick_csplit(W, NRT, cus * xdot::fa::wg_per_cu(bwd_cols_kernel<D, false, true>, ColsL<D, false, true>::LDS));
-  } else {
-    *sq = *sv = xdot::fa::pick_csplit(W, NRT, cus * xdot::fa::wg_per_cu(bwd_cols_kernel<D, false>, ColsL<D, false>::LDS));
-  }
-}
-}  // namespace
 
 extern "C" int xdot_flash_cols_splits_x3(const xdot::fa::BwdArgs* a, int D, int* sq, int* sv) {
   *sq = *sv = 1;
-  const int e = xdot::fa::env_int("XDOT_CSPLIT", 1, 4);  // as in flash_f32.hip, <= 4
+  const int e = fa::env_int("XDOT_CSPLIT", 1, 4);  // as in flash_f32.hip, <= 4
   if (e >= 0) {
     *sq = *sv = (a->R + 31) / 32 / e >= 1 ? e : 1;
     return 0;
   }
-#define L(DV) x3_splits<DV>(a, sq, sv)
-  X3_DISPATCH(L)
-#undef L
+  const ColsMode mode = fa::cols_mode(*a, false);
+  const auto kq = cols_kern(D, mode), kv = dv_kern(D);
+  if (!kq || !kv) return -1;
+  const int64_t W = (int64_t)((a->T + 127) / 128) * a->B * a->H;
+  const int NRT = (a->R + 31) / 32;
+  *sq = fa::csplit_cols(W, NRT, kq.slots());
+  *sv = mode == ColsMode::from_s ? fa::csplit_cols(W, NRT, kv.slots()) : *sq;
+  return 0;
 }
 
 // column splits of the split-bf16 forward (kernel 0) / row-side backward (1), see kernels.h
 extern "C" int xdot_flash_f32_row_splits_x3(int kernel, int D, bool sbuf, int64_t W, int64_t T) {
-  using namespace xdot::fa3;
-  int occ = 0;
-#define OC(DV)                                                                                                   \
-  if (D == DV)                                                                                                   \
-    occ = kernel == 0 ? (sbuf ? xdot::fa::wg_per_cu(fwd_kernel<DV, true>, FwdL<DV>::LDS_SB)                    \
-                              : xdot::fa::wg_per_cu(fwd_kernel<DV, false>, FwdL<DV>::LDS))                     \
-                      : (sbuf ? xdot::fa::wg_per_cu(bwd_rows_ds_kernel<DV>, RowsDsL<DV>::LDS)                  \
-                              : xdot::fa::wg_per_cu(bwd_rows_kernel<DV>, RowsL<DV>::LDS));
-  OC(32) OC(64) OC(96) OC(128)
-#undef OC
-  if (!occ) return 0;
-  return xdot::fa::pick_csplit(W, (int)((T + 31) / 32), occ * xdot_num_cus(), 8, 0.004);
+  const int slots = kernel == 0 ? fwd_kern(D, sbuf).slots() : rows_kern(D, sbuf).slots();
+  if (!slots) return 0;
+  return fa::csplit_f32_rows(W, (int)((T + 31) / 32), slots);
 }

@@ -299,21 +299,23 @@ int xdot_flash_bwd_prep_f32_launch(const xdot::fa::BwdArgs* a, const void* out, 
 int xdot_flash_bwd_rows_f32_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st);
 int xdot_flash_bwd_cols_f32_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st);
 // row splits the fp32 column launch would use (occupancy-aware round model): *sq for the dQ /
-// recompute pass, *sv for the dV pass (score-buffer mode); both 1 for other families
+// recompute pass, *sv for the dV pass (score-buffer mode); both 1 for other families.  _f32 / _x3:
+// the exact and split-bf16 families, -1 where the launcher has no kernel for the mode either
 int xdot_flash_cols_splits(const xdot::fa::BwdArgs* a, int dt, int D, int* sq, int* sv);
 int xdot_flash_cols_splits_f32(const xdot::fa::BwdArgs* a, int D, int* sq, int* sv);
+int xdot_flash_cols_splits_x3(const xdot::fa::BwdArgs* a, int D, int* sq, int* sv);
 // head-heavy plan of the exact-fp32 fused column pass (sbuf, 4 passes, D <= 128): 1 and
 // (whole, rem, split) per XCD when the round model prefers it over the uniform split sq, else 0
 int xdot_flash_f32_cols_heavy(const xdot::fa::BwdArgs* a, int D, int sq, int* whole, int* rem, int* split);
-int xdot_flash_cols_splits_x3(const xdot::fa::BwdArgs* a, int D, int* sq, int* sv);
 // out[r * ldo + c] = Σ_s part[(s * rows + r) * C + c] for r < rows, c < C (C % 4 == 0): fp32
 // partials, output in dtype `dt` (DT_F32 / DT_BF16 / DT_F16)
 int xdot_flash_cols_sum_launch(const float* part, void* out, int S, int64_t rows, int C, int64_t ldo, int dt,
                                hipStream_t st);
 int xdot_flash_cols_splits_cols2(const xdot::fa::BwdArgs* a, int dt, int D, int* sq);
-// column splits of the fp32 row-block kernels (kernel 0: forward, 1: row-side backward) for W
-// unsplit workgroups over T columns: occupancy of the instantiation x CUs, round model
-// (XDOT_F32_SPLIT: unset / auto = model, "old" = the 16-bit model, n = forced); 0: not handled
+// column splits of the fp32 row-block kernels (kernel 0: forward, 1: row-side backward; sbuf: the
+// kernel the launcher picks with a score / dS buffer) for W unsplit workgroups over T columns:
+// occupancy of that instantiation x CUs, round model (XDOT_F32_SPLIT: unset / auto = model, "old" =
+// the 16-bit model, n = forced); 0: not handled.  _exact / _x3: the two families' own kernels
 int xdot_flash_f32_row_splits(int kernel, int fp32_mode, int D, bool sbuf, int64_t W, int64_t T);
 int xdot_flash_f32_row_splits_exact(int kernel, int D, bool sbuf, int64_t W, int64_t T);
 int xdot_flash_f32_row_splits_x3(int kernel, int D, bool sbuf, int64_t W, int64_t T);
@@ -323,7 +325,8 @@ int xdot_flash_f32_row_splits_x3(int kernel, int D, bool sbuf, int64_t W, int64_
 int xdot_flash_wide_splits(int kernel, int dt, int D, bool sbuf, int64_t W, int64_t n);
 int xdot_flash_rows_sum_f32_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st);
 // wide head dims (csrc/flash_wide.hip): D = 160 / 192 / 256 / 384, 16-bit and exact fp32 (a wide
-// fp32 launch always runs exact); -1 = not a wide (dtype, D), -2 = needs the score buffer (fp32 D > 256)
+// fp32 launch always runs exact); -1 = no kernel: not a wide (dtype, D), or fp32 D > 256 without the
+// score buffer
 int xdot_flash_wide_fwd_launch(const xdot::fa::FwdArgs* a, int dt, int D, hipStream_t st);
 int xdot_flash_wide_rows_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st);
 int xdot_flash_wide_cols_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st);

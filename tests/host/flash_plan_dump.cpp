@@ -59,5 +59,15 @@ int main(int argc, char** argv) {
   // the spot values tests/test_flash_plan.py asserts literally
   std::printf("pick_csplit 200 782 768 32 0.001 -> %d\n", pick_csplit(200, 782, 768, 32, 0.001));
   std::printf("pick_csplit 776 32 768 32 0.001 -> %d\n", pick_csplit(776, 32, 768, 32, 0.001));
+  // the named models the kernel files call (each pick_csplit with its own cap and price per split)
+  const struct { const char* name; int (*fn)(int64_t, int, int); } named[] = {
+      {"csplit_cols", csplit_cols}, {"csplit_f32_fwd", csplit_f32_fwd}, {"csplit_f32_rows", csplit_f32_rows},
+      {"csplit_wide_rows", csplit_wide_rows}};
+  for (const auto& m : named)
+    for (int64_t b : blocks)
+      for (int64_t T : Ts)
+        for (int64_t sl : slots)
+          std::printf("%s %lld %d %lld -> %d\n", m.name, (long long)b, (int)((T + 31) / 32), (long long)sl,
+                      m.fn(b, (int)((T + 31) / 32), (int)sl));
   return 0;
 }
