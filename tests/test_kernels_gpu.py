@@ -1,4 +1,4 @@
-"""Numerics of the gfx950 HIP kernels against plain fp32 PyTorch references (GPU only)."""
+"""Numerics of the gfx950 HIP kernels against plain fp32 / fp64 PyTorch references (GPU only)."""
 import math
 
 import pytest
@@ -63,6 +63,9 @@ def test_gemm_integer_exact_fp32(gpu):
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("T", [8, 100, 2048, 25000, 70000])
 def test_softmax_fwd_bwd(gpu, dt, T):
+    """Forward against fp64 under the element bound of tests/_elementwise.py (row sums and exact zeros
+    at the hidden entries included), backward against the fp64 formula on the kernel's own y."""
+    import _elementwise as ew
     from xdot.ops.softmax import scale_mask_softmax_fwd, scale_mask_softmax_bwd
 
     B, H, R = 1, 2, 3
@@ -71,14 +74,11 @@ def test_softmax_fwd_bwd(gpu, dt, T):
     mask[..., 0] = False
     scale = 0.37
     y = scale_mask_softmax_fwd(x, mask, scale)
-    ref = torch.softmax((x.float() * scale).masked_fill(mask.unsqueeze(1), -float("inf")), -1)
-    atol = 1e-6 if dt == torch.float32 else 8e-3
-    assert torch.allclose(y.float(), ref, atol=atol, rtol=2e-2)
+    r = ew.assert_ratios("forward", ew.softmax_fwd_ratios(y, x, mask, scale))
     dy = torch.randn_like(x)
     dx = scale_mask_softmax_bwd(y, dy, scale)
-    yf = y.float()
-    dref = scale * yf * (dy.float() - (dy.float() * yf).sum(-1, keepdim=True))
-    assert torch.allclose(dx.float(), dref, atol=atol * 4, rtol=3e-2)
+    r.update(ew.assert_ratios("backward", ew.softmax_bwd_ratios(dx, y, dy, scale)))
+    print(f"\nRATIO kernel=softmax case={ew.case_id(T)} dtype={ew.DT_IDS[dt]} " + " ".join(f"{k}={v:.3f}" for k, v in r.items()))
 
 
 def test_softmax_fully_masked_row_is_nan(gpu):
@@ -121,9 +121,25 @@ def test_linear_fn_grads(gpu):
         torch.testing.assert_close(a.float(), r, rtol=2e-2, atol=2e-2 * r.abs().max().item())
 
 
+def _adamw_run_check(what, ours, p32, grads_per_step, dtype, kw):
+    """Every parameter after the run against fp64 AdamW that rounds the parameter to ``dtype`` after each
+    step (tests/_elementwise.py::adamw_run_ref: one rounding of the parameter and the fp32 roundings of
+    the update per step, times F = 2)."""
+    import _elementwise as ew
+
+    worst = 0.0
+    for i, (p, p0) in enumerate(zip(ours, p32)):
+        want, bound = ew.adamw_run_ref(p0, [g[i].cpu() for g in grads_per_step], dtype, kw["lr"], kw["betas"],
+                                       kw["eps"], kw["weight_decay"])
+        ratio = ((p.detach().cpu().double() - want).abs() / (bound / ew.F)).max().item()
+        ew.assert_ratios(f"{what}: parameter {i}", {"run": ratio})
+        worst = max(worst, ratio)
+    print(f"\nRATIO kernel={what} case=t1-3 dtype={ew.DT_IDS[dtype]} run={worst:.3f}")
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_fused_adamw_kernel(gpu, dtype):
-    """One multi-tensor HIP launch == torch.optim.AdamW on fp32 copies (fp32 moments)."""
+    """One multi-tensor HIP launch per step == fp64 AdamW on the same gradients (fp32 moments)."""
     from xdot.ops.optim import FusedAdamW
 
     g = torch.Generator(device="cpu").manual_seed(5)
@@ -136,17 +152,14 @@ def test_fused_adamw_kernel(gpu, dtype):
     buf = torch.zeros(1 + p32[3].numel(), device=gpu, dtype=dtype)
     buf[1:].copy_(p32[3].flatten().to(gpu, dtype))
     ours[3] = buf[1:].view(p32[3].shape).detach().requires_grad_(True)
-    ref = [p.to(gpu).requires_grad_(True) for p in p32]
-    o1, o2 = FusedAdamW(ours, **kw), torch.optim.AdamW(ref, **kw)
+    o1 = FusedAdamW(ours, **kw)
+    used = []
     for s in range(3):
-        for p, q, x in zip(ours, ref, gr):
+        for p, x in zip(ours, gr):
             p.grad = (x * (s + 1)).to(gpu, dtype)
-            q.grad = p.grad.float()
+        used.append([p.grad.clone() for p in ours])
         o1.step()
-        o2.step()
-    for p, q in zip(ours, ref):
-        tol = 1e-6 if dtype == torch.float32 else 2e-2
-        torch.testing.assert_close(p.float(), q.detach(), rtol=tol, atol=tol)
+    _adamw_run_check("adamw", ours, p32, used, dtype, kw)
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
@@ -192,7 +205,7 @@ def test_cast_multi_kernel(gpu):
 def test_fused_adamw_fp32_grads(gpu):
     """FusedAdamW.step(params=, grads=) with fp32 gradients of bf16 parameters (GradSync's reduced
     sums): the update uses the fp32 values and writes each, rounded, into p.grad (one launch);
-    == torch.optim.AdamW on fp32 copies; a parameter without an override uses its own p.grad."""
+    == fp64 AdamW on the same gradients; a parameter without an override uses its own p.grad."""
     from xdot.ops.optim import FusedAdamW
 
     g = torch.Generator(device="cpu").manual_seed(9)
@@ -204,19 +217,15 @@ def test_fused_adamw_fp32_grads(gpu):
     buf = torch.zeros(1 + p32[3].numel(), device=gpu, dtype=torch.bfloat16)  # unaligned: scalar path
     buf[1:].copy_(p32[3].flatten().to(gpu, torch.bfloat16))
     ours[3] = buf[1:].view(p32[3].shape).detach().requires_grad_(True)
-    ref = [p.to(gpu).requires_grad_(True) for p in p32]
-    o1, o2 = FusedAdamW(ours, **kw), torch.optim.AdamW(ref, **kw)
+    o1 = FusedAdamW(ours, **kw)
+    used = []
     for s in range(3):
         g32 = [(x * (s + 1)).to(gpu) for x in gr]
-        for p, q, x in zip(ours, ref, g32):
-            q.grad = x.clone()
+        for p in ours:
             p.grad = None
         ours[2].grad = g32[2].to(torch.bfloat16)  # no override: its own bf16 gradient
-        q2 = ref[2]
-        q2.grad = ours[2].grad.float()
+        used.append([g32[0], g32[1], ours[2].grad.clone(), g32[3]])
         o1.step(params=ours, grads=[g32[0], g32[1], None, g32[3]])
-        o2.step()
         for i in (0, 1, 3):
             torch.testing.assert_close(ours[i].grad, g32[i].to(torch.bfloat16), rtol=0, atol=0)
-    for p, q in zip(ours, ref):
-        torch.testing.assert_close(p.float(), q.detach(), rtol=2e-2, atol=2e-2)
+    _adamw_run_check("adamw-fp32-grads", ours, p32, used, torch.bfloat16, kw)

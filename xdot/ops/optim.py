@@ -171,6 +171,17 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
+        # torch casts every loaded floating-point state tensor to its parameter's dtype: the fp32
+        # moments of a 16-bit parameter come back rounded to 16 bits (and the kernel then refuses
+        # them).  Take them again, in fp32, from the state that was handed in.
+        saved = state_dict["state"]
+        ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        for i, p in zip(ids, (p for g in self.param_groups for p in g["params"])):
+            st = self.state.get(p)
+            if st and i in saved:
+                for k in ("exp_avg", "exp_avg_sq"):
+                    if k in st and st[k].dtype != torch.float32:
+                        st[k] = saved[i][k].detach().to(device=p.device, dtype=torch.float32, copy=True)
         if self.capturable:  # re-home loaded step counts on the parameters' devices now
             for group in self.param_groups:
                 for p in group["params"]:
