@@ -143,7 +143,7 @@ def main(argv=None):
     # reference's precision; "split" = hi/lo bf16 halves, opt-in via XDOT_FP32_MODE=split)
     fp32_mode = _F.fp32_mode if a.dtype == "fp32" else None
     # which GEMMs ran the products: the xdot kernels unless XDOT_GEMM_LIB routes them to the
-    # library (csrc/bindings.cpp gemm_lib: unset / 0 = none, "fp32" = exact-fp32 ones, 1 = all)
+    # library (csrc/bindings_gemm.cpp gemm_lib: unset / 0 = none, "fp32" = exact-fp32 ones, 1 = all)
     lib = (os.environ.get("XDOT_GEMM_LIB") or "0").strip().lower()
     on_lib = lib.startswith("1") or (lib.startswith("f") and a.dtype == "fp32")
     rec = {"mode": a.mode, "schedule": a.schedule or "gather", "world_size": n, "emulated": bool(a.emulate), "T": T, "D": D, "offset": a.offset, "dtype": a.dtype,

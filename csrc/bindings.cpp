@@ -4,7 +4,8 @@
 // header (fast rebuilds); this file only validates arguments on the host, resolves the
 // current HIP stream and calls the C-ABI launchers.  Every launch is bounds-checked on
 // the host against the tensors' storage so a bad stride can never turn into a GPU fault.
-// The flash-attention ops are implemented (and bound to their schemas below) in bindings_flash.cpp.
+// The flash-attention ops are implemented (and bound to their schemas below) in bindings_flash.cpp,
+// the GEMM ops (gemm, gemm_plan, proj, wgrad, wgrad2) in bindings_gemm.cpp.
 #include "bindings_common.h"
 
 #include <algorithm>
@@ -20,346 +21,6 @@ using namespace xdot::bind;
 namespace {
 
 std::string build_id() { return std::string(xdot_build_id + 14); }  // after "XDOT_BUILD_ID="
-
-// XDOT_GEMM_LIB: which plain large products may take the library GEMM (at::baddbmm ->
-// hipBLASLt) on in-place strided views.  Default (unset / 0) = none: 16-bit products run gemm3
-// (matches or beats the library), exact-fp32 products the 128x128 f32-MFMA kernel of
-// csrc/gemm_f32.hip.  "fp32" = exact-fp32 plain products on the library (the round-4 default,
-// kept for A/B); 1 = 16-bit products too (round-2 route).
-int gemm_lib() {
-  static const int v = [] {
-    const char* e = std::getenv("XDOT_GEMM_LIB");
-    if (e && e[0] == '1') return 2;
-    if (e && (e[0] == 'f' || e[0] == 'F')) return 1;  // fp32 only
-    return 0;
-  }();
-  return v;
-}
-
-// exact-fp32 products: the f32-MFMA kernel of csrc/gemm_f32.hip (fp32 out); anything else (an
-// fp32 -> 16-bit output) the generic kernel
-int gemm_exact(const xdot::GemmArgs* g, int batches, int dt_in, int dt_out, bool a_mc, bool b_mc, bool vec,
-               hipStream_t st) {
-  if (dt_in == xdot::DT_F32 && dt_out == xdot::DT_F32) return xdot_gemm_f32_launch(g, batches, a_mc, b_mc, vec, st);
-  return xdot_gemm_launch(g, batches, dt_in, dt_out, a_mc, b_mc, vec, st);
-}
-
-// The library route of xdot.gemm: true when it ran.  opA / opB / C are expressed as strided
-// views of the operands' storage (no copies; the BLAS reads leading dimensions / batch
-// strides directly).  Measured (scripts/gemm_lib_ab.sh, MI355X): hipBLASLt 1.2-1.35x the
-// 256x256 kernel on bf16 nt 75000^2 x 768 and all 75000 x 768 x 75000, 1.2x the 128x128 fp32
-// kernel; the xdot kernels stay ahead on skinny long-K bf16 products (all3: 25000 x 768 x
-// 75000, split-K: 1.4x) and own every layout a single strided batch cannot express (two batch
-// levels, scattered K segments, mixed dtypes, small products).
-// split-K: fewest k-slices S minimising ceil(items / CUs) / S (idle CUs of the last round),
-// each slice >= 4 k-tiles of 64, with a 3 % charge per slice for the fp32 partial round trip
-int64_t pick_splits(int64_t tiles, int64_t kt64) {
-  const int64_t ncu = 256;
-  int64_t S = 1;
-  double best = 1e300;
-  for (int64_t s = 1; s <= 64 && (s == 1 || kt64 / s >= 4); ++s) {
-    const double cost = (double)((tiles * s + ncu - 1) / ncu) / (double)s * (1.0 + 0.03 * (s - 1));
-    if (cost < best * 0.98) { best = cost; S = s; }
-  }
-  return S;
-}
-
-// XDOT_GEMM3: 1 (default) = the automatic path tries the 8-phase kernel first (csrc/gemm3.hip)
-int gemm3_auto() {
-  static const int v = [] {
-    const char* e = std::getenv("XDOT_GEMM3");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return v;
-}
-
-bool gemm_library(const at::Tensor& A, const at::Tensor& B, at::Tensor& C, int64_t M, int64_t N, int64_t K,
-                  int64_t nseg, int64_t nb1, int64_t nb2, int64_t lda, int64_t ldb, int64_t ldc, int64_t sA1,
-                  int64_t sA2, int64_t sB1, int64_t sB2, int64_t sC1, int64_t sC2, int64_t sAseg, int64_t sBseg,
-                  bool a_mc, bool b_mc, double alpha, double beta) {
-  if (C.scalar_type() != A.scalar_type() || K == 0) return false;
-  // one batch level
-  int64_t nb = nb1 * nb2, sa = 0, sb = 0, sc = 0;
-  if (nb1 == 1) { sa = sA2; sb = sB2; sc = sC2; }
-  else if (nb2 == 1) { sa = sA1; sb = sB1; sc = sC1; }
-  else if (sA1 == nb2 * sA2 && sB1 == nb2 * sB2 && sC1 == nb2 * sC2) { sa = sA2; sb = sB2; sc = sC2; }
-  else return false;
-  // K segments that continue each other are one longer K
-  if (nseg > 1) {
-    if (sAseg != (a_mc ? K * lda : K) || sBseg != (b_mc ? K * ldb : K)) return false;
-    K *= nseg;
-  }
-  // conservative output layouts only: every output batch its own dense matrix (no batches
-  // interleaved inside one output row -- the per-rank column blocks of nt's (P, R, T) output,
-  // which faulted on this route, stay on the xdot kernels); input batches may interleave or be
-  // broadcast (tn's column blocks of `left` against one `right`: verified against torch in
-  // tests/test_gemm2_gpu.py); 16-byte aligned bases, leading dims and batch strides
-  if (nb > 1 && (sa < 0 || sb < 0 || sc < M * ldc)) return false;
-  const int64_t ev = 16 / (int64_t)A.element_size();
-  auto al = [&](int64_t v) { return v % ev == 0; };
-  if (ldc != N) return false;  // whole output rows (no column-slice views)
-  if (!aligned16(A.data_ptr()) || !aligned16(B.data_ptr()) || !aligned16(C.data_ptr()) || !al(lda) || !al(ldb) ||
-      !al(ldc) || (nb > 1 && (!al(sa) || !al(sb) || !al(sc))))
-    return false;
-  // 16-bit: only where the output alone fills >= 2 rounds of 256x256 tiles (skinny long-K
-  // products keep the split-K kernel); fp32: the library's exact-fp32 GEMM is ahead everywhere
-  // measured (1.1-1.2x the 128x128 kernel), so every large plain product
-  const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256) * nb;
-  const double flop = 2.0 * (double)M * (double)N * (double)K * (double)nb;
-  if (flop < 2e10 || (A.element_size() == 2 && tiles < 512)) return false;
-  const int64_t oa = A.storage_offset(), ob = B.storage_offset(), oc = C.storage_offset();
-  at::Tensor a = A.as_strided({nb, M, K}, {nb > 1 ? sa : M * K, a_mc ? 1 : lda, a_mc ? lda : 1}, oa);
-  at::Tensor b = B.as_strided({nb, K, N}, {nb > 1 ? sb : K * N, b_mc ? ldb : 1, b_mc ? 1 : ldb}, ob);
-  at::Tensor c = C.as_strided({nb, M, N}, {nb > 1 ? sc : M * N, ldc, 1}, oc);
-  if (nb == 1) {
-    at::Tensor c2 = c.select(0, 0);
-    at::addmm_out(c2, c2, a.select(0, 0), b.select(0, 0), beta, alpha);
-  } else {
-    at::baddbmm_out(c, c, a, b, beta, alpha);
-  }
-  return true;
-}
-
-// ------------------------------------------------------------------------------------
-void gemm(const at::Tensor& A, const at::Tensor& B, at::Tensor& C, int64_t M, int64_t N,
-          int64_t K, int64_t nseg, int64_t nb1, int64_t nb2, int64_t lda, int64_t ldb,
-          int64_t ldc, int64_t sA1, int64_t sA2, int64_t sB1, int64_t sB2, int64_t sC1,
-          int64_t sC2, int64_t sAseg, int64_t sBseg, bool a_mc, bool b_mc, double alpha, double beta,
-          int64_t path) {
-  Range rr_("xdot.gemm");
-  TORCH_CHECK(A.is_cuda() && B.is_cuda() && C.is_cuda(), "xdot.gemm: tensors must be on GPU");
-  TORCH_CHECK(A.scalar_type() == B.scalar_type(), "xdot.gemm: A/B dtype mismatch");
-  TORCH_CHECK(M >= 0 && N >= 0 && K >= 0 && nseg >= 1 && nb1 >= 1 && nb2 >= 1, "xdot.gemm: bad sizes");
-  if (M == 0 || N == 0) return;
-  TORCH_CHECK(M < (1LL << 31) && N < (1LL << 31) && K < (1LL << 31), "xdot.gemm: dim too large");
-  TORCH_CHECK(nb1 * nb2 <= 65535, "xdot.gemm: too many batches");
-  // host-side bounds check of the furthest element each operand touches
-  auto last = [](int64_t b1, int64_t s1, int64_t b2, int64_t s2, int64_t ns, int64_t ss) {
-    return (b1 - 1) * s1 + (b2 - 1) * s2 + (ns - 1) * ss;
-  };
-  if (K > 0) {
-    const int64_t la = last(nb1, sA1, nb2, sA2, nseg, sAseg) + (a_mc ? (K - 1) * lda + (M - 1) : (M - 1) * lda + (K - 1));
-    const int64_t lb = last(nb1, sB1, nb2, sB2, nseg, sBseg) + (b_mc ? (K - 1) * ldb + (N - 1) : (N - 1) * ldb + (K - 1));
-    TORCH_CHECK(la < avail_elems(A), "xdot.gemm: A access out of bounds (", la, " >= ", avail_elems(A), ")");
-    TORCH_CHECK(lb < avail_elems(B), "xdot.gemm: B access out of bounds (", lb, " >= ", avail_elems(B), ")");
-  }
-  const int64_t lc = last(nb1, sC1, nb2, sC2, 1, 0) + (M - 1) * ldc + (N - 1);
-  TORCH_CHECK(lc < avail_elems(C), "xdot.gemm: C access out of bounds");
-
-  const int eps = 16 / (int)A.element_size();
-  auto mult = [&](int64_t v) { return v % eps == 0; };
-  // operand loads vectorise on A/B alignment alone; the output is stored 16 bytes at a time
-  // wherever the address allows, element by element elsewhere (the kernels test each strip's
-  // address: an odd column block of nt's (P, R, T) output at T/N = 3125 must not turn every
-  // operand load of the GEMM into element loads)
-  bool vec = aligned16(A.data_ptr()) && aligned16(B.data_ptr()) &&
-             mult(lda) && mult(ldb) && mult(sA1) && mult(sA2) && mult(sB1) && mult(sB2) &&
-             mult(sAseg) && mult(sBseg);
-
-  xdot::GemmArgs g{};
-  g.A = A.data_ptr(); g.B = B.data_ptr(); g.C = C.data_ptr();
-  g.M = (int)M; g.N = (int)N; g.K = (int)K; g.nseg = (int)nseg; g.nb2 = (int)nb2;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.sA1 = sA1; g.sA2 = sA2; g.sB1 = sB1; g.sB2 = sB2; g.sC1 = sC1; g.sC2 = sC2;
-  g.sAseg = sAseg; g.sBseg = sBseg; g.alpha = (float)alpha; g.beta = (float)beta;
-  c10::DeviceGuard guard(A.device());
-  // v2 (256x256 tiles, LDS-DMA, csrc/gemm2.hip) for 16-bit operands whose layout meets its
-  // alignment rules and whose output fills 256-wide tiles; split-K when the tiles alone would
-  // leave CUs idle.  path: 0 = auto, 1 = v1, 2 = v2 whenever its layout rules hold (per call)
-  int mode = (int)path;
-  // fp32 operands on the bf16 matrix pipe (path 6 = automatic with split allowed, which Python
-  // passes under XDOT_FP32_MODE=split; path 4 forces it): hi/lo bf16 copies, three bf16 products
-  // in one gemm3 call (csrc/gemm3.hip, split3_kernel).  The mode is decided in Python only
-  // (xdot.ops.gemm.strided_gemm reads FLAGS.fp32_mode per call): no second source of truth here.
-  if (A.scalar_type() == at::kFloat && (mode == 4 || (mode == 6 && gemm3_auto()))) {
-    const int64_t tpb = ((M + 255) / 256) * ((N + 255) / 256);
-    // worth it when three bf16 products plus the operand copies (read 4 B, write 6 B per
-    // element) beat one exact fp32 product: a product whose operand is far larger than its
-    // output (the materialised P.V: 2.5 GB of P per head) keeps the exact kernel
-    // Both sides are priced at the fraction of the 256 CUs their grid fills: the exact kernel
-    // has no split-K (128x128 tiles), gemm3 splits K (pick_splits), so a product with few
-    // output tiles and a long K (the K = T weight-side products of the autograd ops) goes split.
-    const double flop = 2.0 * (double)M * N * K * nseg * nb1 * nb2;
-    const double elems = (double)nb1 * nb2 * nseg * K * ((double)M + (double)N);
-    const int64_t t128 = ((M + 127) / 128) * ((N + 127) / 128) * nb1 * nb2;
-    const int64_t s3 = pick_splits(tpb * nb1 * nb2, 3 * nseg * ((K + 63) / 64));
-    const double fill1 = std::min(1.0, (double)t128 / 256.0);
-    const double fill3 = std::min(1.0, (double)(tpb * nb1 * nb2 * s3) / 256.0);
-    const double t_split = 3.0 * flop / (1.1e15 * fill3) + 10.0 * elems / 5e12 +
-                           (s3 > 1 ? 8.0 * (double)s3 * M * N * nb1 * nb2 / 5e12 : 0.0);
-    const double t_exact = flop / (1.15e14 * fill1);
-    // the hi/lo copies are transient HBM (6 B per operand element): never more than a quarter of
-    // what is free, else the exact kernel (no extra memory) runs
-    const double copy_bytes = 6.0 * elems;
-    bool fits = copy_bytes < 1e9;
-    if (!fits) {
-      size_t fr = 0, tot = 0;
-      fits = hipMemGetInfo(&fr, &tot) == hipSuccess && copy_bytes < 0.25 * (double)fr;
-    }
-    const bool big = flop >= 2e9 && t_split < t_exact && fits;
-    const bool ok = beta == 0.0 && K > 0 && M >= 256 && N >= 256 && K % 8 == 0 && (!a_mc || M % 8 == 0) &&
-                    (!b_mc || N % 8 == 0) && C.scalar_type() == at::kFloat && nb1 * nb2 * 3 * nseg <= 65535;
-    TORCH_CHECK(mode != 4 || ok, "xdot.gemm: path 4 (split fp32) not eligible for this call");
-    if (ok && (mode == 4 || big)) {
-      const int64_t Ra = a_mc ? K : M, Ca = a_mc ? M : K, Rb = b_mc ? K : N, Cb = b_mc ? N : K;
-      at::Tensor a3 = at::empty({nb1 * nb2 * 3 * nseg * Ra * Ca}, A.options().dtype(at::kBFloat16));
-      at::Tensor b3 = at::empty({nb1 * nb2 * 3 * nseg * Rb * Cb}, A.options().dtype(at::kBFloat16));
-      hipStream_t st = cur_stream(A);
-      // A' = [hi, lo, hi], B' = [hi, hi, lo]: hi.hi + lo.hi + hi.lo
-      xdot_split3_launch(A.data_ptr<float>(), a3.data_ptr(), sA1, sA2, sAseg, lda, (int)nb1, (int)nb2, (int)nseg,
-                         (int)Ra, (int)Ca, 0b010, st);
-      xdot_split3_launch(B.data_ptr<float>(), b3.data_ptr(), sB1, sB2, sBseg, ldb, (int)nb1, (int)nb2, (int)nseg,
-                         (int)Rb, (int)Cb, 0b100, st);
-      check_launch(hipGetLastError(), "split3");
-      xdot::GemmArgs g3a = g;
-      g3a.A = a3.data_ptr();
-      g3a.B = b3.data_ptr();
-      g3a.nseg = (int)(3 * nseg);
-      g3a.lda = Ca;
-      g3a.ldb = Cb;
-      g3a.sAseg = Ra * Ca;
-      g3a.sBseg = Rb * Cb;
-      g3a.sA2 = 3 * nseg * Ra * Ca;
-      g3a.sA1 = nb2 * g3a.sA2;
-      g3a.sB2 = 3 * nseg * Rb * Cb;
-      g3a.sB1 = nb2 * g3a.sB2;
-      const int64_t tiles = tpb * nb1 * nb2;
-      const int64_t kt64 = 3 * nseg * ((K + 63) / 64);
-      const int64_t S = pick_splits(tiles, kt64);
-      at::Tensor ws;
-      if (S > 1) ws = at::empty({S * nb1 * nb2 * M * N}, A.options().dtype(at::kFloat));
-      const int rc3 = xdot_gemm3_launch(&g3a, (int)(nb1 * nb2), xdot::DT_BF16, xdot::DT_F32, a_mc, b_mc, (int)S,
-                                        S > 1 ? ws.data_ptr<float>() : nullptr, st);
-      TORCH_CHECK(rc3 == 0, "xdot.gemm: split fp32 gemm3 launch declined (", rc3, ")");
-      check_launch(hipGetLastError(), "gemm3 (split fp32)");
-      return;
-    }
-  }
-  if (mode == 6) mode = 0;
-  if (mode == 0 && (gemm_lib() == 2 || (gemm_lib() == 1 && A.scalar_type() == at::kFloat)) &&
-      gemm_library(A, B, C, M, N, K, nseg, nb1, nb2, lda, ldb, ldc, sA1, sA2, sB1, sB2, sC1, sC2, sAseg, sBseg, a_mc,
-                   b_mc, alpha, beta))
-    return;
-  // exact fp32: the persistent 256x256 LDS-DMA kernel (csrc/gemm2_f32.hip) where its layout rules
-  // hold and the output has at least one 128-wide tile in each direction; split-K
-  // (pick_splits over 32-deep k-tiles, partials <= 512 MB) when the tiles alone leave CUs idle.
-  // path 1 keeps the 128x128 kernel, path 2 forces this one.
-  if (A.scalar_type() == at::kFloat && C.scalar_type() == at::kFloat && vec && K > 0 && mode != 1) {
-    const bool ok = (a_mc || K % 4 == 0) && (b_mc || K % 4 == 0) && (!a_mc || M % 4 == 0) && (!b_mc || N % 4 == 0);
-    TORCH_CHECK(mode != 2 || ok, "xdot.gemm: path 2 (fp32 v2) needs K % 4 == 0 for k-contiguous operands and "
-                                 "an mn extent % 4 == 0 for mn-contiguous ones");
-    const int64_t nb = nb1 * nb2;
-    const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256) * nb;
-    // auto: >= 2 rounds of 256x256 tiles, or a long K (split-K fills the GPU).  Short-K products
-    // with few tiles (the 25000 x 768 x 768 projections: 294 tiles, K = 768) stay on the 128x128
-    // kernel: 82-94 TF/s there vs 63-65 for this one split 4-6 ways (r5s9)
-    if (ok && (mode == 2 || (M >= 128 && N >= 128 && (tiles >= 2 * 256 || (int64_t)K * nseg >= 4096)))) {
-      int64_t S = pick_splits(tiles, nseg * ((K + 31) / 32));
-      while (S > 1 && S * nb * M * N > (128LL << 20)) --S;
-      at::Tensor ws;
-      if (S > 1) ws = at::empty({S * nb * M * N}, A.options().dtype(at::kFloat));
-      const int rc = xdot_gemm2_f32_launch(&g, (int)nb, a_mc, b_mc, (int)S, S > 1 ? ws.data_ptr<float>() : nullptr,
-                                           cur_stream(A));
-      if (rc == 0) {
-        check_launch(hipGetLastError(), "gemm2_f32");
-        return;
-      }
-    }
-  }
-  const bool half = A.element_size() == 2;
-  bool v2 = half && vec && mode != 1;
-  if (v2 && (!a_mc || !b_mc)) v2 = K % 8 == 0;
-  if (v2 && a_mc) v2 = M % 8 == 0;
-  if (v2 && b_mc) v2 = N % 8 == 0;
-  if (v2 && mode != 2 && mode != 3 && mode != 5) {
-    // auto: enough 256x256 tiles (>= 32 per batch entry or >= 512 overall) -- small outputs
-    // batched over K slabs (the split-K weight gradients of xdot.ops.linear) keep the 128x128
-    // kernel, which fills the GPU without a second split.  Skinny outputs (one side 64..191,
-    // e.g. N = head dim 96 in the materialised path) still go to v2: streaming the long operand
-    // through its deeper LDS-DMA ring beats v1's register staging even with 62 % of the tile
-    // idle (materialised step 39.3 -> 34.2 ms at T = 25000)
-    const int64_t tpb = ((M + 255) / 256) * ((N + 255) / 256);
-    v2 = M >= 64 && N >= 64 && (tpb >= 32 || tpb * nb1 * nb2 >= 512);
-  }
-  TORCH_CHECK(mode != 3 || (v2 && K > 0), "xdot.gemm: path 3 (gemm3) needs 16-bit operands with aligned layouts");
-  if (v2 && K > 0) {
-    // split-K: fewest k-slices S minimising ceil(items / CUs) / S (idle CUs of the last round),
-    // each slice >= 4 k-tiles of 64, with a 3 % charge per slice for the fp32 partial round trip
-    const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256) * nb1 * nb2;
-    const int64_t kt64 = nseg * ((K + 63) / 64);
-    const int64_t ncu = 256;
-    const int64_t S = pick_splits(tiles, kt64);
-    at::Tensor ws;
-    if (S > 1) ws = at::empty({S * nb1 * nb2 * M * N}, A.options().dtype(at::kFloat));
-    // v3 (8-phase 16x16x32, csrc/gemm3.hip) first: beta = 0, M and N >= 256; it declines
-    // (-3) the rest, which the v2 kernel takes
-    if (mode == 3 || mode == 5 || (mode == 0 && gemm3_auto())) {
-      const int rc3 = xdot_gemm3_launch(&g, (int)(nb1 * nb2), dt_code(A.scalar_type()), dt_code(C.scalar_type()),
-                                        a_mc, b_mc, (int)S, S > 1 ? ws.data_ptr<float>() : nullptr, cur_stream(A));
-      TORCH_CHECK(mode != 3 || rc3 == 0, "xdot.gemm: path 3 (gemm3) not eligible for this call (", rc3, ")");
-      if (rc3 == 0) {
-        check_launch(hipGetLastError(), "gemm3");
-        return;
-      }
-    }
-    const int rc2 = xdot_gemm2_launch(&g, (int)(nb1 * nb2), dt_code(A.scalar_type()), dt_code(C.scalar_type()),
-                                      a_mc, b_mc, (int)S, S > 1 ? ws.data_ptr<float>() : nullptr, cur_stream(A));
-    if (rc2 == 0) {
-      check_launch(hipGetLastError(), "gemm2");
-      return;
-    }
-  }
-  // K slabs for the 128x128 kernel (the exact-fp32 path): a product with few output tiles and a
-  // long K (the K = T weight-side products of the autograd ops: e.g. 1562 x 768 x 12496 = 78
-  // tiles) would leave most CUs idle.  Slab s of every (batch, segment) is one outer batch entry
-  // writing an fp32 partial; one ordered sum (gemm2_reduce) applies alpha / beta / the cast.
-  if (mode == 0 && nb1 == 1 && K >= 1024) {
-    const int64_t tiles = ((M + 127) / 128) * ((N + 127) / 128) * nb2;
-    if (tiles < 384) {
-      int64_t S = std::min<int64_t>(std::min<int64_t>((768 + tiles - 1) / tiles, K / 256), 32);
-      S = std::min<int64_t>(S, (int64_t)(64 << 20) / std::max<int64_t>(1, nb2 * M * N));  // partials <= 256 MB
-      int64_t Ks = ((K + S - 1) / S + 15) / 16 * 16;
-      S = (K + Ks - 1) / Ks;
-      if (S >= 2) {
-        at::Tensor ws = at::empty({S * nb2 * M * N}, A.options().dtype(at::kFloat));
-        xdot::GemmArgs gs = g;
-        gs.C = ws.data_ptr();
-        gs.ldc = N;
-        gs.sC2 = M * N;
-        gs.sC1 = nb2 * M * N;
-        gs.alpha = 1.f;
-        gs.beta = 0.f;
-        gs.sA1 = a_mc ? Ks * lda : Ks;
-        gs.sB1 = b_mc ? Ks * ldb : Ks;
-        gs.K = (int)Ks;
-        const int full = (int)(K / Ks) == S ? (int)S : (int)S - 1;
-        const bool vs = vec && (Ks * (a_mc ? lda : 1)) % eps == 0 && (Ks * (b_mc ? ldb : 1)) % eps == 0;
-        int rc1 = gemm_exact(&gs, full * (int)nb2, dt_code(A.scalar_type()), xdot::DT_F32, a_mc, b_mc, vs,
-                             cur_stream(A));
-        if (rc1 == 0 && full < S) {  // the short last slab
-          xdot::GemmArgs gl = gs;
-          const int64_t k0 = (int64_t)full * Ks;
-          gl.A = static_cast<const char*>(A.data_ptr()) + A.element_size() * (a_mc ? k0 * lda : k0);
-          gl.B = static_cast<const char*>(B.data_ptr()) + B.element_size() * (b_mc ? k0 * ldb : k0);
-          gl.C = ws.data_ptr<float>() + (int64_t)full * nb2 * M * N;
-          gl.K = (int)(K - k0);
-          const bool vl = vs && (a_mc ? k0 * lda : k0) % eps == 0 && (b_mc ? k0 * ldb : k0) % eps == 0;
-          rc1 = gemm_exact(&gl, (int)nb2, dt_code(A.scalar_type()), xdot::DT_F32, a_mc, b_mc, vl, cur_stream(A));
-        }
-        TORCH_CHECK(rc1 == 0, "xdot.gemm: unsupported dtype combination ", A.scalar_type(), " -> fp32 slabs");
-        check_launch(hipGetLastError(), "gemm (K slabs)");
-        TORCH_CHECK(xdot_gemm_reduce_launch(&g, ws.data_ptr<float>(), (int)S, (int)nb2, dt_code(C.scalar_type()),
-                                            cur_stream(A)) == 0, "xdot.gemm: slab reduce dtype");
-        check_launch(hipGetLastError(), "gemm slab reduce");
-        return;
-      }
-    }
-  }
-  const int rc = gemm_exact(&g, (int)(nb1 * nb2), dt_code(A.scalar_type()), dt_code(C.scalar_type()), a_mc, b_mc,
-                            vec, cur_stream(A));
-  TORCH_CHECK(rc == 0, "xdot.gemm: unsupported dtype combination ", A.scalar_type(), " -> ", C.scalar_type());
-  check_launch(hipGetLastError(), "gemm");
-}
 
 // ------------------------------------------------------------------------------------
 at::Tensor softmax_fwd(const at::Tensor& x, const c10::optional<at::Tensor>& mask, double scale,
@@ -469,157 +130,6 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> mask_gen(int64_t B, int64_t R, in
   return {bits, flags, bitsT};
 }
 
-// Projection GEMM (csrc/gemm_proj.hip): nn = false: y = x Wᵀ (+ bias), W (N, K); nn = true:
-// dx = dy W, W (K, N) (the input gradient of the same Linear).  x: (..., K) with unit last
-// stride; out (optional): an (M, N) row-major view to write (e.g. this rank's block of the
-// all-gather buffer).  Shapes / layouts the kernel does not take, and (force = 0) products
-// large enough for the library to be faster, run on the library GEMM.
-at::Tensor proj(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias, bool nn,
-                const c10::optional<at::Tensor>& out, int64_t force, double alpha) {
-  Range rr_("xdot.proj");
-  TORCH_CHECK(x.is_cuda() && w.is_cuda() && w.dim() == 2 && x.dim() >= 1 && x.scalar_type() == w.scalar_type(),
-              "xdot.proj: device tensors of one dtype, 2-D weight");
-  const int64_t K = x.size(-1);
-  const int64_t N = nn ? w.size(1) : w.size(0);
-  TORCH_CHECK((nn ? w.size(0) : w.size(1)) == K, "xdot.proj: weight ", w.sizes(), " does not match input features ", K);
-  at::Tensor a = x.dim() == 2 ? x : x.reshape({-1, K});
-  if (a.stride(1) != 1) a = a.contiguous();
-  const int64_t M = a.size(0);
-  std::vector<int64_t> oshape(x.sizes().begin(), x.sizes().end() - 1);
-  oshape.push_back(N);
-  at::Tensor c;
-  if (out.has_value()) {
-    c = *out;
-    TORCH_CHECK(c.is_cuda() && c.dim() == 2 && c.size(0) == M && c.size(1) == N && c.stride(1) == 1 &&
-                    c.scalar_type() == x.scalar_type(),
-                "xdot.proj: out must be an (M, N) row-major view of the input dtype");
-  } else {
-    c = at::empty({M, N}, x.options());
-  }
-  const bool has_b = bias.has_value() && bias->defined();
-  TORCH_CHECK(!has_b || (!nn && bias->numel() == N && bias->is_contiguous() && bias->scalar_type() == x.scalar_type()),
-              "xdot.proj: bias must be a contiguous (N,) tensor of the input dtype (forward only)");
-  int rc = -3;
-  if (M > 0 && (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf) && w.stride(1) == 1 &&
-      M <= INT32_MAX && N <= INT32_MAX && K <= INT32_MAX) {
-    xdot::ProjArgs p{};
-    p.A = a.data_ptr();
-    p.B = w.data_ptr();
-    p.bias = has_b ? bias->data_ptr() : nullptr;
-    p.C = c.data_ptr();
-    p.M = (int)M;
-    p.N = (int)N;
-    p.K = (int)K;
-    p.lda = a.stride(0);
-    p.ldb = w.stride(0);
-    p.ldc = c.stride(0);
-    p.alpha = (float)alpha;
-    // every address the kernel can touch lies inside the operands' storage
-    TORCH_CHECK((M - 1) * p.lda + K <= avail_elems(a) && (nn ? (K - 1) * p.ldb + N : (N - 1) * p.ldb + K) <= avail_elems(w) &&
-                    (M - 1) * p.ldc + N <= avail_elems(c),
-                "xdot.proj: operand extents exceed their storage");
-    c10::DeviceGuard guard(x.device());
-    rc = xdot_gemm_proj_launch(&p, dt_code(x.scalar_type()), nn ? 1 : 0, (int)force, cur_stream(x));
-    if (rc != -3) check_launch((hipError_t)rc, "gemm_proj");
-  }
-  if (rc == -3) {  // library GEMM (alpha scales the bias too: C = alpha (A op(B) + bias), one rounding)
-    const at::Tensor wt = nn ? w : w.t();
-    if (has_b) at::addmm_out(c, *bias, a, wt, alpha, alpha);
-    else if (alpha == 1.0) at::mm_out(c, a, wt);
-    else at::addmm_out(c, c, a, wt, 0.0, alpha);
-  }
-  return out.has_value() ? c : c.view(oshape);
-}
-
-// Weight gradient of a Linear: dy (K, M), x (K, N) row-major 16-bit -> dyᵀ x (M, N) in out_dtype,
-// fp32 accumulation (csrc/gemm_wgrad.hip: S slabs of K -> fp32 partials -> one ordered sum).
-// splits 0: the slab count from a round / partial-traffic cost model.  Returns an undefined tensor
-// when the shape is not eligible (the caller takes another route).
-struct WgradProb {
-  at::Tensor dy, x, part;
-  int64_t K, M, N, S;
-};
-
-bool wgrad_prob(const at::Tensor& dy, const at::Tensor& x, int64_t splits, WgradProb& q) {
-  TORCH_CHECK(dy.is_cuda() && x.is_cuda() && dy.dim() == 2 && x.dim() == 2 && dy.size(0) == x.size(0) &&
-                  dy.scalar_type() == x.scalar_type() && dy.stride(1) == 1 && x.stride(1) == 1,
-              "xdot.wgrad: (K, M) and (K, N) row-major device tensors of one dtype");
-  const int64_t K = dy.size(0), M = dy.size(1), N = x.size(1);
-  if (K < 1 || M % 128 || N % 128 || (dy.scalar_type() != at::kBFloat16 && dy.scalar_type() != at::kHalf) ||
-      M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
-    return false;
-  const int64_t KT = (K + 63) / 64, tiles = (M / 128) * (N / 128);
-  // slab count: rounds of 512 workgroup slots x (k-tiles per slab + a per-workgroup overhead of
-  // ~4 k-tiles) + the fp32 partials' write and ordered-sum read (~0.07 k-tile per tile and slab);
-  // fitted to the S sweep of benchmarks/micro/wgrad_splits.py (profiles/r4_s2.md §12)
-  int64_t S = splits;
-  if (S <= 0) {
-    double best = 1e300;
-    for (int64_t s = 1; s <= std::min<int64_t>(KT, 64); ++s) {
-      const double cost = (double)((tiles * s + 511) / 512) * ((double)KT / s + 4.0) + 0.07 * (double)(tiles * s);
-      if (cost < best) { best = cost; S = s; }
-    }
-  }
-  S = std::max<int64_t>(1, std::min<int64_t>(S, KT));
-  TORCH_CHECK((K - 1) * dy.stride(0) + M <= avail_elems(dy) && (K - 1) * x.stride(0) + N <= avail_elems(x),
-              "xdot.wgrad: operand extents exceed their storage");
-  q = WgradProb{dy, x, at::empty({S, M, N}, dy.options().dtype(at::kFloat)), K, M, N, S};
-  return true;
-}
-
-// launch 1 or 2 products in one kernel, then one ordered sum per product; empty when not eligible
-std::vector<at::Tensor> wgrad_run(std::vector<WgradProb>& qs, at::ScalarType out_dtype) {
-  const int np = (int)qs.size();
-  const void* A[2];
-  const void* B[2];
-  float* part[2];
-  int M[2], N[2], K[2], S[2];
-  int64_t lda[2], ldb[2];
-  for (int i = 0; i < np; ++i) {
-    A[i] = qs[i].dy.data_ptr(); B[i] = qs[i].x.data_ptr(); part[i] = qs[i].part.data_ptr<float>();
-    M[i] = (int)qs[i].M; N[i] = (int)qs[i].N; K[i] = (int)qs[i].K; S[i] = (int)qs[i].S;
-    lda[i] = qs[i].dy.stride(0); ldb[i] = qs[i].x.stride(0);
-  }
-  const at::Tensor& d0 = qs[0].dy;
-  c10::DeviceGuard guard(d0.device());
-  const int rc = xdot_gemm_wgrad_launch(np, A, B, part, M, N, K, S, lda, ldb, dt_code(d0.scalar_type()), cur_stream(d0));
-  if (rc == -3) return {};
-  check_launch((hipError_t)rc, "gemm_wgrad");
-  std::vector<at::Tensor> outs;
-  for (int i = 0; i < np; ++i) outs.push_back(at::empty({qs[i].M, qs[i].N}, d0.options().dtype(out_dtype)));
-  if (np == 2) {  // both ordered sums in one launch
-    TORCH_CHECK(xdot_sum_partials2_launch(part[0], outs[0].data_ptr(), S[0], qs[0].M * qs[0].N, part[1],
-                                          outs[1].data_ptr(), S[1], qs[1].M * qs[1].N, dt_code(out_dtype),
-                                          cur_stream(d0)) == 0, "xdot.wgrad2: out dtype");
-    check_launch(hipGetLastError(), "wgrad2 sum");
-    return outs;
-  }
-  for (int i = 0; i < np; ++i) {
-    TORCH_CHECK(xdot_sum_partials_launch(part[i], outs[i].data_ptr(), S[i], qs[i].M * qs[i].N, dt_code(out_dtype),
-                                         cur_stream(d0)) == 0, "xdot.wgrad: out dtype");
-    check_launch(hipGetLastError(), "wgrad sum");
-  }
-  return outs;
-}
-
-at::Tensor wgrad(const at::Tensor& dy, const at::Tensor& x, at::ScalarType out_dtype, int64_t splits) {
-  Range rr_("xdot.wgrad");
-  std::vector<WgradProb> qs(1);
-  if (!wgrad_prob(dy, x, splits, qs[0])) return at::Tensor();
-  auto outs = wgrad_run(qs, out_dtype);
-  return outs.empty() ? at::Tensor() : outs[0];
-}
-
-// two weight gradients in ONE launch (the fused backward's dWk and dW[q|v]); [] when either
-// shape is not eligible
-std::vector<at::Tensor> wgrad2(const at::Tensor& dy0, const at::Tensor& x0, const at::Tensor& dy1,
-                               const at::Tensor& x1, at::ScalarType out_dtype) {
-  Range rr_("xdot.wgrad2");
-  TORCH_CHECK(dy0.scalar_type() == dy1.scalar_type() && dy0.device() == dy1.device(), "xdot.wgrad2: dtype / device");
-  std::vector<WgradProb> qs(2);
-  if (!wgrad_prob(dy0, x0, 0, qs[0]) || !wgrad_prob(dy1, x1, 0, qs[1])) return {};
-  return wgrad_run(qs, out_dtype);
-}
 
 // fused MSE loss forward: (mean (y - t)^2 in y's dtype, dy = 2 (y - t) / n)
 std::tuple<at::Tensor, at::Tensor> mse_fwd(const at::Tensor& y, const at::Tensor& t) {
@@ -889,6 +399,9 @@ TORCH_LIBRARY(xdot, m) {
   m.def("gemm(Tensor A, Tensor B, Tensor(a!) C, int M, int N, int K, int nseg, int nb1, int nb2, "
         "int lda, int ldb, int ldc, int sA1, int sA2, int sB1, int sB2, int sC1, int sC2, "
         "int sAseg, int sBseg, bool a_mc, bool b_mc, float alpha, float beta=0.0, int path=0) -> ()");
+  m.def("gemm_plan(int M, int N, int K, int nseg, int nb1, int nb2, int lda, int ldb, int ldc, int sA1, int sA2, "
+        "int sB1, int sB2, int sC1, int sC2, int sAseg, int sBseg, bool a_mc, bool b_mc, float beta, ScalarType dt_in, "
+        "ScalarType dt_out, bool a16, bool b16, bool c16, int path) -> int[]");
   m.def("softmax_fwd(Tensor x, Tensor? mask, float scale, int mdiv, int mmul, int mmod) -> Tensor");
   m.def("softmax_bwd(Tensor y, Tensor dy, float scale) -> Tensor");
   m.def("mask_pack(Tensor mask) -> (Tensor, Tensor, Tensor)");
@@ -961,15 +474,11 @@ TORCH_LIBRARY_IMPL(xdot, CompositeExplicitAutograd, m) {
 }
 
 TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
-  m.impl("gemm", &gemm);
   m.impl("softmax_fwd", &softmax_fwd);
   m.impl("softmax_bwd", &softmax_bwd);
   m.impl("mask_pack", &mask_pack);
   m.impl("mask_gen", &mask_gen);
   m.impl("mse_fwd", &mse_fwd);
-  m.impl("proj", &proj);
-  m.impl("wgrad", &wgrad);
-  m.impl("wgrad2", &wgrad2);
   m.impl("adamw_step", &adamw_step);
   m.impl("cast_multi", &cast_multi);
   m.impl("ipc_all_gather", &ipc_all_gather);

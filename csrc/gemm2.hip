@@ -504,15 +504,6 @@ static void launch2_t(const GemmArgs& a, int batches, int splits, float* ws, hip
   if (pst) G2LAUNCH(true, LDS);
   else G2LAUNCH(false, LDS - 32768);
 #undef G2LAUNCH
-  if (splits > 1) {
-    const int64_t n = (int64_t)a.M * a.N * batches;
-    const bool v4 = a.N % 4 == 0 && a.ldc % 4 == 0 && a.sC1 % 4 == 0 && a.sC2 % 4 == 0 &&
-                    (reinterpret_cast<uintptr_t>(a.C) & 15) == 0;
-    if (v4)
-      hipLaunchKernelGGL((gemm2_reduce4<DTO>), dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, a, ws, splits, batches);
-    else
-      hipLaunchKernelGGL((gemm2_reduce<DTO>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, ws, splits, batches);
-  }
 }
 
 template <int DTI, int DTO>
@@ -525,7 +516,7 @@ static void launch2_d(const GemmArgs& a, int batches, bool amc, bool bmc, int sp
 
 }  // namespace xdot
 
-// Eligibility (checked by the caller, csrc/bindings.cpp): 16-bit A/B, every operand address
+// Eligibility (checked by the planner: plan_gemm's 16-bit rules, csrc/gemm_plan.h): 16-bit A/B, every operand address
 // 16-byte aligned with lda/ldb/batch/segment strides multiples of 8 elements, K % 8 == 0 when
 // an operand is k-contiguous, the mn extent of an mn-contiguous operand a multiple of 8.
 extern "C" int xdot_gemm2_launch(const xdot::GemmArgs* a, int batches, int dt_in, int dt_out, int a_mc, int b_mc,
@@ -537,10 +528,13 @@ extern "C" int xdot_gemm2_launch(const xdot::GemmArgs* a, int batches, int dt_in
   if (g.tiles_m == 0 || g.tiles_n == 0 || batches == 0) return 0;
   if (splits < 1 || (splits > 1 && !ws)) return -2;
 #define G2_DT(I, O) \
-  if (dt_in == I && dt_out == O) { launch2_d<I, O>(g, batches, a_mc, b_mc, splits, ws, st); return 0; }
+  if (dt_in == I && dt_out == O) { launch2_d<I, O>(g, batches, a_mc, b_mc, splits, ws, st); goto done; }
   G2_DT(DT_BF16, DT_BF16) G2_DT(DT_BF16, DT_F32) G2_DT(DT_F16, DT_F16) G2_DT(DT_F16, DT_F32)
 #undef G2_DT
   return -1;
+done:
+  if (splits > 1) return xdot_gemm_reduce_launch(&g, ws, splits, batches, dt_out, st);
+  return 0;
 }
 
 extern "C" int xdot_num_cus() { return xdot::num_cus(); }

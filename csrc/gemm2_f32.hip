@@ -397,7 +397,7 @@ __global__ __launch_bounds__(512) void gemm2_f32_kernel(GemmArgs p, float* __res
 
 }  // namespace xdot
 
-// Eligibility (checked by the caller, csrc/bindings.cpp): fp32 A/B/C, operand bases 16-byte
+// Eligibility (checked by the planner: plan_gemm's exact-fp32 rules, csrc/gemm_plan.h): fp32 A/B/C, operand bases 16-byte
 // aligned with lda/ldb/batch/segment strides multiples of 4 elements, K % 4 == 0 when an operand
 // is k-contiguous, the mn extent of an mn-contiguous operand a multiple of 4.  splits > 1 needs
 // ws (splits * batches * M * N floats); the ordered sum runs after (xdot_gemm_reduce_launch).

@@ -31,6 +31,8 @@
 // operand bases, lda/ldb/batch/segment strides multiples of 8 elements, K % 8 == 0 unless both
 // operands are mn-contiguous.
 #include "flash_common.h"
+#include "gemm_plan.h"
+#include "kernels.h"
 
 namespace xdot {
 namespace g3 {
@@ -602,29 +604,20 @@ static void launch3_d(const GemmArgs& a, int batches, bool amc, bool bmc, int sp
 
 }  // namespace xdot
 
-extern "C" int xdot_num_cus();
-extern "C" int xdot_gemm_reduce_launch(const xdot::GemmArgs* a, const float* ws, int splits, int batches, int dt_out,
-                                       hipStream_t st);
-
-// Eligibility: see the file header.  -3 = shape/layout not eligible (caller falls back).
+// Eligibility: gemm3_takes (csrc/gemm_plan.h, which the planner of xdot.gemm asks before it routes a
+// call here).  -3 = shape/layout not eligible, -2 = bad split arguments, -1 = dtype pair.
+static_assert(xdot::gp::G3_BM == xdot::g3::BM && xdot::gp::G3_BN == xdot::g3::BN && xdot::gp::G3_BK == xdot::g3::BK &&
+                  xdot::gp::G3_MAX_ITEMS == xdot::g3::MAX_ITEMS,
+              "gemm_plan.h's gemm3 geometry is this file's");
 extern "C" int xdot_gemm3_launch(const xdot::GemmArgs* a, int batches, int dt_in, int dt_out, int a_mc, int b_mc,
                                  int splits, float* ws, hipStream_t st) {
   using namespace xdot;
   GemmArgs g = *a;
-  // K % 8: a k-contiguous operand's K tail is zero-filled per 16-byte chunk; two mn-contiguous
-  // operands (the weight gradients dYᵀ·X, K = the sequence rows) are tail-filled per k row, any K
-  if (g.M < g3::BM || g.N < g3::BN || ((g.K % 8) != 0 && !(a_mc && b_mc)) || g.beta != 0.f) return -3;
+  if (splits < 1 || (splits > 1 && !ws)) return -2;
+  const int ncu = xdot_num_cus();
+  if (!gp::gemm3_takes(g.M, g.N, g.K, g.nseg, batches, splits, a_mc, b_mc, g.beta == 0.f, ncu)) return -3;
   g.tiles_m = (g.M + g3::BM - 1) / g3::BM;
   g.tiles_n = (g.N + g3::BN - 1) / g3::BN;
-  if (batches == 0 || g.K == 0) return -3;
-  if (splits < 1 || (splits > 1 && !ws)) return -2;
-  const int ncu_ = xdot_num_cus();
-  if ((int64_t)((g.K + g3::BK - 1) / g3::BK) * g.nseg < splits) return -3;  // every item >= 1 k-tile
-  {
-    const int64_t W = (int64_t)g.tiles_m * g.tiles_n * batches * splits;
-    if ((W + ncu_ - 1) / ncu_ > g3::MAX_ITEMS || g.tiles_m > 65535 || g.tiles_n > 65535) return -3;
-  }
-  const int ncu = xdot_num_cus();
 #define G3_DT(I, O) \
   if (dt_in == I && dt_out == O) { launch3_d<I, O>(g, batches, a_mc, b_mc, splits, ws, ncu, st); goto done; }
   G3_DT(DT_BF16, DT_BF16) G3_DT(DT_BF16, DT_F32) G3_DT(DT_F16, DT_F16) G3_DT(DT_F16, DT_F32)

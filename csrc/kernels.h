@@ -213,10 +213,11 @@ int xdot_gemm_launch(const xdot::GemmArgs* a, int batches, int dt_in, int dt_out
                      int b_mc, int vec, hipStream_t st);
 // exact-fp32 GEMM (csrc/gemm_f32.hip): fp32 in / out, same arguments as xdot_gemm_launch
 int xdot_gemm_f32_launch(const xdot::GemmArgs* a, int batches, int a_mc, int b_mc, int vec, hipStream_t st);
-// 256x256 LDS-DMA 16-bit GEMM (csrc/gemm2.hip); splits > 1 needs ws: splits*batches*M*N fp32
+// 256x256 LDS-DMA 16-bit GEMM (csrc/gemm2.hip); splits > 1 needs ws (splits*batches*M*N fp32) and
+// runs the ordered sum itself
 int xdot_gemm2_launch(const xdot::GemmArgs* a, int batches, int dt_in, int dt_out, int a_mc, int b_mc,
                       int splits, float* ws, hipStream_t st);
-// persistent 256x256 LDS-DMA exact-fp32 GEMM (csrc/gemm2_f32.hip); eligibility in the file;
+// persistent 256x256 LDS-DMA exact-fp32 GEMM (csrc/gemm2_f32.hip); eligibility: plan_gemm, gemm_plan.h;
 // splits > 1 needs ws (splits*batches*M*N fp32) and runs the ordered sum itself
 int xdot_gemm2_f32_launch(const xdot::GemmArgs* a, int batches, int a_mc, int b_mc, int splits, float* ws,
                           hipStream_t st);
@@ -225,7 +226,7 @@ int xdot_num_cus();
 // C = alpha * (ordered sum of `splits` fp32 partials ws[s][z][M][N]) + beta * C  (csrc/gemm2.hip)
 int xdot_gemm_reduce_launch(const xdot::GemmArgs* a, const float* ws, int splits, int batches, int dt_out,
                             hipStream_t st);
-// 8-phase 16x16x32 16-bit GEMM (csrc/gemm3.hip): M, N >= 256, K % 8 == 0; -3 = not eligible
+// 8-phase 16x16x32 16-bit GEMM (csrc/gemm3.hip); -3 = not eligible (gemm3_takes, gemm_plan.h)
 int xdot_gemm3_launch(const xdot::GemmArgs* a, int batches, int dt_in, int dt_out, int a_mc, int b_mc,
                       int splits, float* ws, hipStream_t st);
 // projection GEMM; -3 = not eligible (16-bit, K % 64 == 0, N % 64 == 0 (NN: % 128), 16-byte

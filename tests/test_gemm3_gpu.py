@@ -201,10 +201,10 @@ def test_split_fp32_non_finite_inputs(gpu):
 @pytest.mark.parametrize("a_mc,b_mc", LAYOUTS)
 @pytest.mark.parametrize("K", [4096, 5000])
 def test_exact_fp32_k_slabs(gpu, a_mc, b_mc, K):
-    """Exact fp32 with few output tiles and a long K runs as K slabs of the 128x128 kernel
-    (fp32 partials + one ordered sum; a short last slab when the slab length does not divide
-    K): exact-fp32 accuracy vs fp64, alpha / beta applied once."""
-    from xdot.ops.gemm import strided_gemm
+    """Exact fp32 with few output tiles and a long K splits K (fp32 partials + one ordered sum): these
+    aligned layouts on the 256x256 kernel (csrc/gemm2_f32.hip; the K slabs of the 128x128 kernel take
+    what it does not, tests/test_gemm_plan_gpu.py): exact-fp32 accuracy vs fp64, alpha / beta applied once."""
+    from xdot.ops.gemm import gemm_plan, strided_gemm
     from xdot.utils.env import FLAGS
 
     g = torch.Generator(device="cpu").manual_seed(K)
@@ -216,9 +216,12 @@ def test_exact_fp32_k_slabs(gpu, a_mc, b_mc, K):
     old = FLAGS.fp32_mode
     try:
         FLAGS.fp32_mode = "exact"
-        strided_gemm(A.float().to(gpu), B.float().to(gpu), C, M=M, N=N, K=K, nb2=nb, lda=(M if a_mc else K),
-                     ldb=(N if b_mc else K), ldc=N, sA2=M * K, sB2=N * K, sC2=M * N, a_mc=a_mc, b_mc=b_mc,
-                     alpha=0.5, beta=2.0)
+        kw = dict(M=M, N=N, K=K, nb2=nb, lda=(M if a_mc else K), ldb=(N if b_mc else K), ldc=N, sA2=M * K, sB2=N * K,
+                  sC2=M * N, a_mc=a_mc, b_mc=b_mc, alpha=0.5, beta=2.0)
+        Ag, Bg = A.float().to(gpu), B.float().to(gpu)
+        plan = gemm_plan(Ag, Bg, C, **kw)
+        assert plan.route == "G2_F32" and plan.splits > 1, plan
+        strided_gemm(Ag, Bg, C, **kw)
     finally:
         FLAGS.fp32_mode = old
     Af, Bf = A.float().double(), B.float().double()

@@ -49,7 +49,7 @@ def test_gemm2_f32_layouts(gpu, a_mc, b_mc, M, N, K):
     """The persistent 256x256 LDS-DMA kernel (path 2, csrc/gemm2_f32.hip): ragged M / N tiles,
     K tails (K % 32) zero-patched in LDS, alpha / beta, every storage order; the long-K shape
     goes split-K through path 0 (ordered fp32 partial sum)."""
-    from xdot.ops.gemm import strided_gemm
+    from xdot.ops.gemm import gemm_plan, strided_gemm
 
     if not _eligible_v2(M, N, K, a_mc, b_mc):
         pytest.skip("layout rules of the 256x256 kernel")
@@ -59,17 +59,20 @@ def test_gemm2_f32_layouts(gpu, a_mc, b_mc, M, N, K):
     C = torch.randn(M, N, device=gpu, generator=g)
     C0 = C.clone()
     path = 0 if K > 4096 else 2
-    strided_gemm(A, B, C, M=M, N=N, K=K, lda=A.shape[1], ldb=B.shape[1], ldc=N, a_mc=a_mc, b_mc=b_mc,
-                 alpha=0.5, beta=-2.0, path=path)
+    kw = dict(M=M, N=N, K=K, lda=A.shape[1], ldb=B.shape[1], ldc=N, a_mc=a_mc, b_mc=b_mc, alpha=0.5, beta=-2.0, path=path)
+    plan = gemm_plan(A, B, C, **kw)
+    assert plan.route == "G2_F32" and (path == 2 or plan.splits > 1), plan
+    strided_gemm(A, B, C, **kw)
     opA = A.double().t() if a_mc else A.double()
     opB = B.double() if b_mc else B.double().t()
     assert _rel(C, 0.5 * opA @ opB - 2.0 * C0.double()) <= 2e-6
 
 
 def test_gemm2_f32_batched_segments_exact_ints(gpu):
-    """Two batch levels + K segments with a K tail per segment (K = 36) on the 256x256 kernel and
-    through the automatic route (split-K): integer data, exact."""
-    from xdot.ops.gemm import strided_gemm
+    """Two batch levels + K segments with a K tail per segment (K = 36) on the 256x256 kernel (path 2) and
+    through the automatic route, which keeps these 8 tiles of K x nseg = 108 on the 128x128 kernel:
+    integer data, exact."""
+    from xdot.ops.gemm import gemm_plan, strided_gemm
 
     g = torch.Generator(device=gpu).manual_seed(3)
     nb1, nb2, nseg, M, N, K = 2, 2, 3, 260, 132, 36
@@ -78,9 +81,11 @@ def test_gemm2_f32_batched_segments_exact_ints(gpu):
     ref = torch.einsum("xyskm,xysnk->xymn", A.double(), B.double())
     for path in (2, 0):
         C = torch.full((nb1, nb2, M, N), float("nan"), device=gpu)
-        strided_gemm(A, B, C, M=M, N=N, K=K, nseg=nseg, nb1=nb1, nb2=nb2, lda=M, ldb=K, ldc=N,
-                     sA1=nb2 * nseg * K * M, sA2=nseg * K * M, sB1=nb2 * nseg * N * K, sB2=nseg * N * K,
-                     sC1=nb2 * M * N, sC2=M * N, sAseg=K * M, sBseg=N * K, a_mc=True, path=path)
+        kw = dict(M=M, N=N, K=K, nseg=nseg, nb1=nb1, nb2=nb2, lda=M, ldb=K, ldc=N,
+                  sA1=nb2 * nseg * K * M, sA2=nseg * K * M, sB1=nb2 * nseg * N * K, sB2=nseg * N * K,
+                  sC1=nb2 * M * N, sC2=M * N, sAseg=K * M, sBseg=N * K, a_mc=True, path=path)
+        assert gemm_plan(A, B, C, **kw).route == {2: "G2_F32", 0: "G1"}[path]
+        strided_gemm(A, B, C, **kw)
         assert torch.equal(C.double(), ref), f"path {path}"
 
 
@@ -101,15 +106,18 @@ def test_gemm_f32_batched_segments_exact_ints(gpu):
 
 
 def test_gemm_f32_long_k_slabs(gpu):
-    """Few output tiles and a long K (the weight gradients, the autograd ops' K = T products):
-    K slabs of the kernel + one ordered sum."""
-    from xdot.ops.gemm import strided_gemm
+    """Few output tiles and a long K (the weight gradients, the autograd ops' K = T products): aligned
+    as here, the split-K 256x256 kernel (csrc/gemm2_f32.hip) + one ordered sum.  The K slabs of the
+    128x128 kernel take the layouts that kernel does not (tests/test_gemm_plan_gpu.py)."""
+    from xdot.ops.gemm import gemm_plan, strided_gemm
 
     g = torch.Generator(device=gpu).manual_seed(1)
     M, N, K = 768, 768, 25000
     A = torch.randn(K, M, device=gpu, generator=g)
     B = torch.randn(K, N, device=gpu, generator=g)
     C = torch.empty(M, N, device=gpu)
+    plan = gemm_plan(A, B, C, M=M, N=N, K=K, lda=M, ldb=N, ldc=N, a_mc=True, b_mc=True)
+    assert plan.route == "G2_F32" and plan.splits > 1, plan
     strided_gemm(A, B, C, M=M, N=N, K=K, lda=M, ldb=N, ldc=N, a_mc=True, b_mc=True)
     assert _rel(C, A.double().t() @ B.double()) <= 2e-6
 

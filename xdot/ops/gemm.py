@@ -7,7 +7,7 @@ CPU, for dtypes the kernel does not take (float64 / integer) and for testing.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -34,12 +34,45 @@ def strided_gemm(A, B, C, *, M, N, K, nseg=1, nb1=1, nb2=1, lda, ldb, ldc, sA1=0
     ``XDOT_FP32_MODE=split``; the default ``exact`` keeps fp32 products on the exact fp32 MFMA kernel).
     ``FLAGS.fp32_mode`` is read here on every call: the one source of truth for the GEMMs too.
     ``split_ok=False`` keeps an fp32 call on the exact kernels under either mode."""
-    if path == 0 and split_ok and A.dtype == torch.float32 and FLAGS.fp32_mode == "split":
-        path = 6
     _ext.ops().gemm(A, B, C, int(M), int(N), int(K), int(nseg), int(nb1), int(nb2), int(lda),
                     int(ldb), int(ldc), int(sA1), int(sA2), int(sB1), int(sB2), int(sC1), int(sC2),
                     int(sAseg), int(sBseg), bool(a_mc), bool(b_mc), float(alpha),
-                    float(beta), int(path))
+                    float(beta), _kernel_path(A, path, split_ok))
+
+
+def _kernel_path(A, path, split_ok) -> int:
+    """the ``path`` the op is given: automatic fp32 calls allow the split route under ``XDOT_FP32_MODE=split``"""
+    if path == 0 and split_ok and A.dtype == torch.float32 and FLAGS.fp32_mode == "split":
+        return 6
+    return int(path)
+
+
+ROUTES = ("SPLIT3", "LIBRARY", "G2_F32", "G3", "G2", "SLABS", "G1")
+
+
+class GemmPlan(NamedTuple):
+    """What ``strided_gemm`` would run for a call (csrc/gemm_plan.h): ``route`` one of ``ROUTES``, ``splits`` the
+    split-K slices; for ``SLABS`` ``slabs`` K slabs of length ``Ks``, the first ``full`` of them whole, with 16-byte
+    operand loads in the full / the last slab (``vec_full`` / ``vec_last``); ``vec``: those of a plain launch."""
+    route: str
+    splits: int
+    Ks: int
+    full: int
+    vec: bool
+    slabs: int
+    vec_full: bool
+    vec_last: bool
+
+
+def gemm_plan(A, B, C, *, M, N, K, nseg=1, nb1=1, nb2=1, lda, ldb, ldc, sA1=0, sA2=0,
+              sB1=0, sB2=0, sC1=0, sC2=0, sAseg=0, sBseg=0, a_mc=False, b_mc=False,
+              alpha=1.0, beta=0.0, path=0, split_ok=True) -> GemmPlan:
+    """The plan of ``strided_gemm(A, B, C, ...)`` with the same arguments; launches nothing, raises where it raises."""
+    r = _ext.ops().gemm_plan(int(M), int(N), int(K), int(nseg), int(nb1), int(nb2), int(lda), int(ldb), int(ldc),
+                             int(sA1), int(sA2), int(sB1), int(sB2), int(sC1), int(sC2), int(sAseg), int(sBseg),
+                             bool(a_mc), bool(b_mc), float(beta), A.dtype, C.dtype, A.data_ptr() % 16 == 0,
+                             B.data_ptr() % 16 == 0, C.data_ptr() % 16 == 0, _kernel_path(A, path, split_ok))
+    return GemmPlan(ROUTES[r[0]], r[1], r[2], r[3], bool(r[4]), r[5], bool(r[6]), bool(r[7]))
 
 
 def _flat(t: torch.Tensor, lead: int) -> torch.Tensor:

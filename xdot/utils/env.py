@@ -87,7 +87,7 @@ variable                    default   effect
                                       (two xGMI links per hop), 16-bit accumulators  [collective]
 ``XDOT_ROCTX`` (C++)        0         roctx ranges around every native op (rocprofv3 markers)
 ``XDOT_GEMM_LIB`` (C++)     0         which plain large products may run on the library GEMM
-                                      (hipBLASLt, ``csrc/bindings.cpp``): unset / 0 = none (every
+                                      (hipBLASLt, ``csrc/gemm_plan.h``): unset / 0 = none (every
                                       product on the xdot kernels: exact fp32 on csrc/gemm2_f32.hip
                                       / gemm_f32.hip), ``fp32`` = exact-fp32 ones (the round-4
                                       default, kept for A/B), 1 = 16-bit ones too
