@@ -89,11 +89,13 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> mask_pack(const at::Tensor& mask)
 
 // mask_pack's outputs for the mask `causal / window / lengths / doc_starts` describe
 // (xdot.StructuredMask), the packed columns being the runs of `segs` (nseg, 3) int32 (packed_start,
-// length, global_start); doc_starts: (n,) shared or (B, n) sorted int32 document starts
+// length, global_start); doc_starts: (n,) shared or (B, n) sorted int32 document starts; row_runs:
+// (nrun, 3) int32 (local_start, length, global_start) tiling the R rows, in place of row_offset
 std::tuple<at::Tensor, at::Tensor, at::Tensor> mask_gen(int64_t B, int64_t R, int64_t T, bool causal, int64_t window,
                                                         int64_t row_offset, const c10::optional<at::Tensor>& lengths,
                                                         const at::Tensor& segs,
-                                                        const c10::optional<at::Tensor>& doc_starts) {
+                                                        const c10::optional<at::Tensor>& doc_starts,
+                                                        const c10::optional<at::Tensor>& row_runs) {
   Range rr_("xdot.mask_gen");
   TORCH_CHECK(B >= 0 && R >= 0 && T >= 0, "xdot.mask_gen: negative shape");
   TORCH_CHECK(segs.is_cuda() && segs.scalar_type() == at::kInt && segs.dim() == 2 && segs.size(1) == 3 &&
@@ -116,6 +118,16 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> mask_gen(int64_t B, int64_t R, in
   }
   TORCH_CHECK(window >= 0 && window < (1LL << 40) && row_offset >= 0 && row_offset < (1LL << 40),
               "xdot.mask_gen: window / row_offset out of range");
+  const int* rows = nullptr;
+  int64_t nrows = 0;
+  if (row_runs.has_value()) {
+    const at::Tensor& t = *row_runs;
+    TORCH_CHECK(t.is_cuda() && t.device() == segs.device() && t.scalar_type() == at::kInt && t.dim() == 2 &&
+                    t.size(1) == 3 && t.is_contiguous() && t.size(0) < (1LL << 20),
+                "xdot.mask_gen: row_runs must be a contiguous (nrun, 3) int32 tensor on the segment table's device");
+    nrows = t.size(0);
+    if (nrows > 0) rows = t.data_ptr<int>();
+  }
   const int64_t NKT = (T + 63) / 64, NRT = (R + 63) / 64, Tpad = (T + 127) / 128 * 128;
   TORCH_CHECK(B * R * NKT < (1LL << 40) && T < (1LL << 31) && R < (1LL << 31) && B < (1LL << 31), "xdot.mask_gen: too large");
   auto bits = at::empty({B, NKT, R}, segs.options().dtype(at::kLong));
@@ -125,7 +137,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> mask_gen(int64_t B, int64_t R, in
   xdot_mask_gen_launch(reinterpret_cast<uint64_t*>(bits.data_ptr()), reinterpret_cast<uint64_t*>(bitsT.data_ptr()),
                        flags.data_ptr<uint8_t>(), lengths.has_value() ? lengths->data_ptr<int>() : nullptr,
                        segs.data_ptr<int>(), (int)segs.size(0), causal ? 1 : 0, window, row_offset, (int)B, (int)R, (int)T,
-                       starts, starts == nullptr ? 0 : (int)nstarts, starts_stride, cur_stream(segs));
+                       starts, starts == nullptr ? 0 : (int)nstarts, starts_stride, rows, (int)nrows, cur_stream(segs));
   check_launch(hipGetLastError(), "mask_gen");
   return {bits, flags, bitsT};
 }
@@ -405,7 +417,7 @@ TORCH_LIBRARY(xdot, m) {
   m.def("softmax_fwd(Tensor x, Tensor? mask, float scale, int mdiv, int mmul, int mmod) -> Tensor");
   m.def("softmax_bwd(Tensor y, Tensor dy, float scale) -> Tensor");
   m.def("mask_pack(Tensor mask) -> (Tensor, Tensor, Tensor)");
-  m.def("mask_gen(int B, int R, int T, bool causal, int window, int row_offset, Tensor? lengths, Tensor segs, Tensor? doc_starts=None) -> (Tensor, Tensor, Tensor)");
+  m.def("mask_gen(int B, int R, int T, bool causal, int window, int row_offset, Tensor? lengths, Tensor segs, Tensor? doc_starts=None, Tensor? row_runs=None) -> (Tensor, Tensor, Tensor)");
   m.def("flash_fwd(Tensor rows, Tensor kc, Tensor vc, Tensor? bits, Tensor? flags, int H, float scale, int nsplit=0, bool prescaled=False, int fp32_mode=0, Tensor(a!)? sbuf=None, int Hg=0) -> (Tensor, Tensor)");
   m.def("flash_bwd_cols(Tensor dout, Tensor rows, Tensor kc, Tensor vc, Tensor out, Tensor lse, Tensor? bits, "
         "Tensor? flags, int H, float scale, Tensor? delta=None, bool fp32_out=True, bool prescaled=False, "

@@ -251,10 +251,11 @@ int xdot_mask_pack_launch(const uint8_t* mask, uint64_t* bits, uint64_t* bt, uin
 // the same three outputs generated from a description (causal / window / lengths / document
 // starts, row offset) and a column segment table (nseg, 3) int32 (packed_start, length,
 // global_start); no (B, R, T) input.  starts: nstarts sorted int32 per batch (batch stride
-// starts_stride, 0: shared) or null
+// starts_stride, 0: shared) or null.  rows: (nrows, 3) int32 row runs (local_start, length,
+// global_start) tiling [0, R), in place of row_off, or null
 int xdot_mask_gen_launch(uint64_t* bits, uint64_t* bt, uint8_t* flags, const int* lengths, const int* segs, int nseg,
                          int causal, int64_t window, int64_t row_off, int B, int R, int T, const int* starts, int nstarts,
-                         int64_t starts_stride, hipStream_t st);
+                         int64_t starts_stride, const int* rows, int nrows, hipStream_t st);
 int xdot_flash_fwd_launch(const xdot::fa::FwdArgs* a, int dt, int D, hipStream_t st);
 // δ = rowsum(dO ⊙ O) (reads a->dout, a->B/R/H)
 int xdot_flash_bwd_delta_launch(const xdot::fa::BwdArgs* a, const void* out, float* delta, int dt, int D, hipStream_t st);

@@ -168,6 +168,15 @@ __global__ __launch_bounds__(256) void mask_pack_kernel(const uint8_t* __restric
 // is searched the same way and a lane bisects [k0, k1] in memory.  Whatever the table holds,
 // every index read is in [0, n) and every search shrinks its range, so an unsorted (unvalidated
 // device) table gives an unspecified mask, not a fault.  Without DOCS the code is what it was.
+//
+// Row runs (ROWS; rows: `nrow` runs (local_start, length, global_start) of consecutive global rows
+// that tile [0, R), built and checked by the host): local row r is global row global_start +
+// (r - local_start) of the run that holds it, in place of row_off + r (a rank whose rows are not
+// one range: the zigzag layout's two chunks).  The interval arithmetic is per lane already.  The
+// wave's document search is not: it takes the tile's 64 rows for the consecutive global rows
+// [g0, g1].  A tile inside one run keeps it, with g0 / g1 from its run.  A tile that holds a run
+// boundary (at most one per boundary) has rows from far-apart ranges: every lane bisects the whole
+// table for its own row and the hull is left open.  Without ROWS the code is what it was.
 
 constexpr int64_t kNoBound = (int64_t)1 << 60;  // (the run arithmetic below stays in range)
 
@@ -195,13 +204,26 @@ __device__ __forceinline__ int doc_upper_wave(const int* __restrict__ s, int a, 
   return a + __popcll(__ballot(i < e && (int64_t)s[i < e ? i : 0] <= x));  // (n > 0: s[0] exists)
 }
 
-template <bool DOCS>
+// global row of local row r (rows outside every run, past R: a position nobody uses)
+template <bool ROWS>
+__device__ __forceinline__ int64_t run_row(const int* __restrict__ rows, int nrow, int64_t row_off, int r) {
+  if (!ROWS) return row_off + r;
+  int64_t g = 0;
+  for (int s = 0; s < nrow; ++s) {  // wave-uniform loads
+    const int ls = rows[3 * s], len = rows[3 * s + 1];
+    if (r >= ls && r - ls < len) g = (int64_t)rows[3 * s + 2] + (r - ls);
+  }
+  return g;
+}
+
+template <bool DOCS, bool ROWS>
 __global__ __launch_bounds__(256) void mask_gen_kernel(uint64_t* __restrict__ bits, uint64_t* __restrict__ bt,
                                                         uint8_t* __restrict__ flags, const int* __restrict__ lengths,
                                                         const int* __restrict__ segs, int nseg, int causal,
                                                         int64_t window, int64_t row_off, int B, int R, int T, int NKT,
                                                         int NKT4, int NRT, int Tpad, int KT_ALL,
-                                                        const int* __restrict__ starts, int n, int64_t dstride) {
+                                                        const int* __restrict__ starts, int n, int64_t dstride,
+                                                        const int* __restrict__ rows, int nrow) {
   const int lane = threadIdx.x & 63;
   const int KT2 = (KT_ALL + 1) / 2;
   const int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -212,37 +234,58 @@ __global__ __launch_bounds__(256) void mask_gen_kernel(uint64_t* __restrict__ bi
   const int r = rt * 64 + lane;
   uint64_t wv[2] = {0, 0};
   const int64_t c0 = (int64_t)kt0 * 64;
+  const int64_t grow = run_row<ROWS>(rows, nrow, row_off, r);  // this lane's global row
   // the lane's own document [dlo, dhi], and the hull of the wave's documents [wlo, whi]: global
   // columns outside the hull are masked in every row of the wave
   int64_t dlo = 0, dhi = kNoBound, wlo = 0, whi = kNoBound;
   if (DOCS && (int64_t)__builtin_amdgcn_readfirstlane(kt0) * 64 < T) {  // all 64 lanes enter (ballots, shuffles)
     const int rtu = __builtin_amdgcn_readfirstlane(rt), bu = __builtin_amdgcn_readfirstlane(b);
     const int* __restrict__ ds = starts + (int64_t)bu * dstride;
-    const int64_t g0 = row_off + (int64_t)rtu * 64, g1 = row_off + min(rtu * 64 + 63, R - 1);
-    const int64_t gr = row_off + r;  // rows past R: bounds nobody uses
-    const int k0 = doc_upper_wave(ds, 0, n, g0, lane);
-    if (k0 > 0) wlo = ds[k0 - 1];
-    const int i = k0 + lane;
-    const int v = ds[i < n ? i : 0];  // lane j: start k0 + j
-    const int cnt = __popcll(__ballot(i < n && (int64_t)v <= g1));
-    if (cnt < 64) {  // the starts in (g0, g1] are lanes 0 .. cnt - 1; k1 = k0 + cnt
-      if (k0 + cnt < n) whi = (int64_t)__builtin_amdgcn_readlane(v, cnt) - 1;
-      int k = 0;  // of them, those <= gr
-      for (int j = 0; j < cnt; ++j) k += (int64_t)__builtin_amdgcn_readlane(v, j) <= gr;
-      k = min(k, cnt);
-      const int below = __shfl(v, max(k - 1, 0), 64), above = __shfl(v, min(k, 63), 64);
-      dlo = k > 0 ? (int64_t)below : wlo;
-      dhi = k < cnt ? (int64_t)above - 1 : whi;
-    } else {
-      const int k1 = doc_upper_wave(ds, k0 + 64, n, g1, lane);
-      if (k1 < n) whi = (int64_t)ds[k1] - 1;
-      const int k = doc_upper(ds, k0, k1, gr);
+    int64_t g0 = row_off + (int64_t)rtu * 64, g1 = row_off + min(rtu * 64 + 63, R - 1);
+    bool one_run = true;  // wave-uniform: the tile's rows are the consecutive global rows [g0, g1]
+    if (ROWS) {
+      const int r0 = rtu * 64, r1 = min(rtu * 64 + 63, R - 1);
+      one_run = false;
+      for (int s = 0; s < nrow; ++s) {
+        const int ls = rows[3 * s], len = rows[3 * s + 1];
+        if (r0 >= ls && r1 >= r0 && r1 - ls < len) {
+          one_run = true;
+          g0 = (int64_t)rows[3 * s + 2] + (r0 - ls);
+          g1 = g0 + (r1 - r0);
+        }
+      }
+    }
+    // rows past R: bounds nobody uses
+    const int64_t gr = ROWS ? (one_run ? g0 + lane : grow) : row_off + r;
+    if (ROWS && !one_run) {  // a run boundary inside the tile: per-lane rows, no hull
+      const int k = doc_upper(ds, 0, n, gr);
       dlo = k > 0 ? (int64_t)ds[k - 1] : 0;
       dhi = k < n ? (int64_t)ds[k] - 1 : kNoBound;
+    } else {
+      const int k0 = doc_upper_wave(ds, 0, n, g0, lane);
+      if (k0 > 0) wlo = ds[k0 - 1];
+      const int i = k0 + lane;
+      const int v = ds[i < n ? i : 0];  // lane j: start k0 + j
+      const int cnt = __popcll(__ballot(i < n && (int64_t)v <= g1));
+      if (cnt < 64) {  // the starts in (g0, g1] are lanes 0 .. cnt - 1; k1 = k0 + cnt
+        if (k0 + cnt < n) whi = (int64_t)__builtin_amdgcn_readlane(v, cnt) - 1;
+        int k = 0;  // of them, those <= gr
+        for (int j = 0; j < cnt; ++j) k += (int64_t)__builtin_amdgcn_readlane(v, j) <= gr;
+        k = min(k, cnt);
+        const int below = __shfl(v, max(k - 1, 0), 64), above = __shfl(v, min(k, 63), 64);
+        dlo = k > 0 ? (int64_t)below : wlo;
+        dhi = k < cnt ? (int64_t)above - 1 : whi;
+      } else {
+        const int k1 = doc_upper_wave(ds, k0 + 64, n, g1, lane);
+        if (k1 < n) whi = (int64_t)ds[k1] - 1;
+        const int k = doc_upper(ds, k0, k1, gr);
+        dlo = k > 0 ? (int64_t)ds[k - 1] : 0;
+        dhi = k < n ? (int64_t)ds[k] - 1 : kNoBound;
+      }
     }
   }
   if (r < R && c0 < T) {
-    const int64_t gr = row_off + r;
+    const int64_t gr = grow;
     int64_t lo = 0, hi = kNoBound;
     if (causal) hi = gr;
     if (window > 0) {
@@ -300,18 +343,23 @@ extern "C" int xdot_mask_pack_launch(const uint8_t* mask, uint64_t* bits, uint64
 
 // lengths: (B,) int32 or null; segs: (nseg, 3) int32 (packed_start, length, global_start) covering
 // [0, T); window <= 0: none; starts: nstarts sorted int32 document starts per batch (batch b's at
-// starts + b * starts_stride, stride 0: one shared table) or null
+// starts + b * starts_stride, stride 0: one shared table) or null; rows: (nrows, 3) int32 (local_start,
+// length, global_start) tiling [0, R) in place of row_off, or null
 extern "C" int xdot_mask_gen_launch(uint64_t* bits, uint64_t* bt, uint8_t* flags, const int* lengths, const int* segs,
                                     int nseg, int causal, int64_t window, int64_t row_off, int B, int R, int T,
-                                    const int* starts, int nstarts, int64_t starts_stride, hipStream_t st) {
+                                    const int* starts, int nstarts, int64_t starts_stride, const int* rows, int nrows,
+                                    hipStream_t st) {
   using namespace xdot;
   const int NKT = (T + 63) / 64, NKT4 = (NKT + 3) & ~3, NRT = (R + 63) / 64, Tpad = (T + 127) / 128 * 128;
   const int KT_ALL = max(NKT4, Tpad / 64);
   const int64_t nblk = (int64_t)B * NRT * ((KT_ALL + 1) / 2);
   if (nblk == 0) return 0;
   const bool docs = starts != nullptr && nstarts > 0;
-  hipLaunchKernelGGL(docs ? mask_gen_kernel<true> : mask_gen_kernel<false>, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0,
-                     st, bits, bt, flags, lengths, segs, nseg, causal, window, row_off, B, R, T, NKT, NKT4, NRT, Tpad,
-                     KT_ALL, starts, nstarts, starts_stride);
+  const bool runs = rows != nullptr && nrows > 0;
+  auto kern = runs ? (docs ? mask_gen_kernel<true, true> : mask_gen_kernel<false, true>)
+                   : (docs ? mask_gen_kernel<true, false> : mask_gen_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, st, bits, bt, flags, lengths, segs, nseg, causal,
+                     window, row_off, B, R, T, NKT, NKT4, NRT, Tpad, KT_ALL, starts, nstarts, starts_stride, rows,
+                     runs ? nrows : 0);
   return 0;
 }

@@ -13,7 +13,7 @@ from .utils.comm import (init, get_rank, get_world_size, is_main_process, synchr
 from .parallel import (distributed_matmul_nt, distributed_matmul_all, distributed_matmul_tn,  # noqa: E402,F401
                        distributed_matmul_block, RightTransposeMultiplication, FullMultiplication,
                        LeftTransposeMultiplication, seq_parallel_attention, broadcast_parameters,
-                       allreduce_gradients, GradSync, gather_sequence)
+                       allreduce_gradients, GradSync, gather_sequence, shard_rows, unshard_rows)
 from .models import DistributedDotProductAttn  # noqa: E402,F401
 from .ops import (scale_mask_softmax, linear, FusedAdamW, MSELoss, mse_loss, StructuredMask,  # noqa: E402,F401
                   Rotary, rope)

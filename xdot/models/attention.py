@@ -51,6 +51,16 @@ Keyword-only knobs (each mirrors an environment flag, the argument
                 :mod:`xdot.ops.rope`) after their projections, at this rank's global positions
                 (``rank * R`` unless the object carries an offset; 0 with ``distributed=False``),
                 on every path; ``v`` is untouched.  ``None`` (default): no rotation, no launch.
+``layout``      the row sharding of the sequence tensors: ``'contiguous'`` (default, the reference's:
+                rank ``r`` holds the global rows ``[rR, (r+1)R)``) or ``'zigzag'`` (the sequence cut
+                into ``2N`` chunks, rank ``r`` holds chunks ``r`` and ``2N-1-r``:
+                :mod:`xdot.parallel.layout`), under which every rank has about half live score
+                tiles of a causal mask instead of ``1/(2N)`` .. ``(2N-1)/(2N)`` of them.  The inputs
+                are this rank's rows in that layout (``xdot.shard_rows`` / ``xdot.unshard_rows``); a
+                ``StructuredMask`` and ``rope`` follow it (an explicit ``row_offset`` / ``offset``
+                contradicts ``'zigzag'``), a dense ``attn_mask`` keeps local rows and GLOBAL columns.
+                Communication, gather chunks and kernels are layout-blind; ``distributed=False``
+                ignores it (a world of one is the identity).
 """
 from __future__ import annotations
 
@@ -67,6 +77,7 @@ from ..ops.mask import StructuredMask
 from ..ops.rope import Rotary, rope as _rope, rope_packed
 from ..ops.softmax import scale_mask_softmax
 from ..parallel.autograd import FullMultiplication, RightTransposeMultiplication
+from ..parallel.layout import check_layout
 from ..utils import comm as _comm
 from ..utils.env import FLAGS
 
@@ -124,8 +135,9 @@ class DistributedDotProductAttn(nn.Module):
                  distributed: bool = True, *, impl: str = "auto", fused: Optional[bool] = None,
                  backend: str = "auto", dtype: Optional[torch.dtype] = None, chunk_plan: Optional[int] = None,
                  comm: Optional[_comm.Communicator] = None, rope: Optional[Rotary] = None,
-                 num_gathered_heads: Optional[int] = None):
+                 num_gathered_heads: Optional[int] = None, layout: str = "contiguous"):
         super().__init__()
+        check_layout(layout)
         if fused is not None:
             if impl not in ("auto", "flash" if fused else "materialized"):
                 raise ValueError(f"fused={fused} contradicts impl={impl!r}")
@@ -165,6 +177,7 @@ class DistributedDotProductAttn(nn.Module):
         self.chunk_plan = None if chunk_plan is None else int(chunk_plan)
         self.comm = comm
         self.rope = rope
+        self.layout = layout
         self.keys = nn.Linear(key_dim, key_dim, bias=add_bias)
         # the gathered side: num_gathered_heads heads (key_dim / value_dim wide by default)
         self.queries = nn.Linear(query_dim, self.num_gathered_heads * self.dim, bias=add_bias)
@@ -205,6 +218,7 @@ class DistributedDotProductAttn(nn.Module):
 
     def _forward(self, keys: Tensor, queries: Tensor, values: Tensor, attn_mask: Optional[Tensor]) -> Tensor:
         scale = 1.0 / math.sqrt(self.dim)
+        lay = self.layout if self.distributed else "contiguous"  # (a world of one: the identity)
         if self._pick_impl(keys) == "flash":
             from ..parallel import attention as pa
             from ..parallel.attention import seq_parallel_attention_packed, start_gather
@@ -220,15 +234,17 @@ class DistributedDotProductAttn(nn.Module):
                 qv = self._project_qv(queries, values)
                 q, k = qv[..., :Hg * dk], self._proj(self.keys, keys)
                 if self.rope is not None:  # at width dk, before the zero padding
-                    off = self.rope.resolve(comm.rank, k.shape[1])
+                    off = self.rope.resolve(comm.rank, k.shape[1], comm.world_size, lay)
                     q, k = _rope(q, Hg, self.rope, offset=off), _rope(k, H, self.rope, offset=off)
                 # (the Hg gathered heads and the H row heads are padded separately)
                 qv = torch.cat([pa.pad_heads(q, Hg, dk, Dp), pa.pad_heads(qv[..., Hg * dk:], Hg, dv, Dp)], dim=-1)
                 k = pa.pad_heads(k, H, dk, Dp)
-                o = seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm, gathered_heads=gh)
+                o = seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm, gathered_heads=gh, layout=lay)
                 return self._proj(self.composition, pa.unpad_heads(o, H, dv, Dp))
-            if isinstance(attn_mask, Tensor) and attn_mask.is_cuda and attn_mask.dim() == 3 and FLAGS.mask_async:
-                # pack the mask on a side stream while the projection GEMMs run
+            if isinstance(attn_mask, Tensor) and attn_mask.is_cuda and attn_mask.dim() == 3 and FLAGS.mask_async \
+                    and (lay == "contiguous" or comm.world_size == 1):
+                # pack the mask on a side stream while the projection GEMMs run (its columns as they
+                # are: the gathered side's order only under the contiguous layout)
                 from ..ops import flash
 
                 attn_mask = flash.prepare_mask_async(attn_mask.to(torch.bool), attn_mask.shape[0],
@@ -252,12 +268,12 @@ class DistributedDotProductAttn(nn.Module):
                     sync = (gs, id(self))
                 return AttnBlockFn.apply(keys, queries, attn_mask, self.keys.weight, self.keys.bias, wq, bq, wv, bv,
                                          self.composition.weight, self.composition.bias, self.num_heads, scale, comm,
-                                         self.chunk_plan, sync, torch.is_grad_enabled(), self.rope, gh)
+                                         self.chunk_plan, sync, torch.is_grad_enabled(), self.rope, gh, lay)
             # gathered side first: its all-gather runs while the row-side GEMM computes
             qv = self._project_qv(queries, values)
             pre = False
             if self.rope is not None:  # q rotated before the gather is issued
-                off = self.rope.resolve(comm.rank, qv.shape[1])
+                off = self.rope.resolve(comm.rank, qv.shape[1], comm.world_size, lay)
                 qv = rope_packed(qv, Hg * dk, Hg, self.rope, off)
             pending = start_gather(qv, comm, chunks=self.chunk_plan)
             k = self._proj(self.keys, keys)
@@ -267,7 +283,7 @@ class DistributedDotProductAttn(nn.Module):
                 pre = pa.prescale_wanted(k, qv, H, gh)
                 k = rope_packed(k, H * dk, H, self.rope, off, alpha=scale * _LOG2E if pre else 1.0, bwd_alpha=1.0)
             o = seq_parallel_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm, pending=pending,
-                                              k_prescaled=pre, gathered_heads=gh)
+                                              k_prescaled=pre, gathered_heads=gh, layout=lay)
             return self._proj(self.composition, o)
         if self._pick_impl(keys) == "ring":
             from ..parallel.ring import ring_attention_packed
@@ -276,19 +292,19 @@ class DistributedDotProductAttn(nn.Module):
             qv = self._project_qv(queries, values)
             k = self._proj(self.keys, keys)
             if self.rope is not None:
-                off = self.rope.resolve(comm.rank, k.shape[1])
+                off = self.rope.resolve(comm.rank, k.shape[1], comm.world_size, lay)
                 qv = rope_packed(qv, self.num_gathered_heads * self.dim, self.num_gathered_heads, self.rope, off)
                 k = rope_packed(k, k.shape[-1], self.num_heads, self.rope, off)
             o = ring_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm,
                                       gathered_heads=None if self.num_gathered_heads == self.num_heads
-                                      else self.num_gathered_heads)
+                                      else self.num_gathered_heads, layout=lay)
             return self._proj(self.composition, o)
         k = self._proj(self.keys, keys)
         q = self._proj(self.queries, queries)
         v = self._proj(self.values, values)
         if self.rope is not None:
-            rank = (self.comm or _comm.get_comm()).rank if self.distributed else 0
-            off = self.rope.resolve(rank, k.shape[1])
+            c = (self.comm or _comm.get_comm()) if self.distributed else _comm.LocalComm()
+            off = self.rope.resolve(c.rank, k.shape[1], c.world_size, lay)
             k = _rope(k, self.num_heads, self.rope, offset=off)
             q = _rope(q, self.num_gathered_heads, self.rope, offset=off)
         return self._proj(self.composition, self._materialized(k, q, v, attn_mask, scale))
@@ -325,10 +341,14 @@ class DistributedDotProductAttn(nn.Module):
             s = RightTransposeMultiplication.apply(k, q, self.offset, comm)
         else:
             s = torch.matmul(k, q.transpose(-1, -2))
-        if isinstance(attn_mask, StructuredMask):
-            # the softmax kernel takes a dense mask: the (B, R, T) tensor is built here, once
-            rank = comm.rank if self.distributed else 0
-            attn_mask = attn_mask.dense(B, R, s.shape[-1], rank * R, s.device)
+        if attn_mask is not None:
+            # the softmax kernel takes a dense mask: a StructuredMask's (B, R, T) tensor is built
+            # here, once; the scores' columns are in rank-major gathered order, which under a
+            # layout is not the global order a dense tensor's columns come in
+            from ..ops.mask import resolve as resolve_mask
+
+            attn_mask = resolve_mask(attn_mask, B, R, s.shape[-1], comm.rank if self.distributed else 0, False,
+                                     s.device, self.layout if self.distributed else "contiguous")
         p = scale_mask_softmax(s, attn_mask, scale)
         if self.distributed:
             o = FullMultiplication.apply(p, v, self.offset, comm)
@@ -343,4 +363,5 @@ class DistributedDotProductAttn(nn.Module):
                 f"offset={self.offset}, distributed={self.distributed}, impl={self.impl}, backend={self.backend}, "
                 f"dtype={self.compute_dtype}, chunk_plan={self.chunk_plan}"
                 + (f", rope={self.rope!r}" if self.rope is not None else "")
-                + (f", num_gathered_heads={self.num_gathered_heads}" if self.num_gathered_heads != self.num_heads else ""))
+                + (f", num_gathered_heads={self.num_gathered_heads}" if self.num_gathered_heads != self.num_heads else "")
+                + (f", layout={self.layout}" if self.layout != "contiguous" else ""))

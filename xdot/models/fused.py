@@ -78,8 +78,9 @@ class AttnBlockFn(torch.autograd.Function):
     @staticmethod
     @_ext.pinned
     def forward(ctx, xk, xqv, mask, wk, bk, wq, bq, wv, bv, wc, bc, H, scale, comm, chunk_plan, sync=None,
-                grad_on=True, rope=None, Hg=None):
+                grad_on=True, rope=None, Hg=None, layout="contiguous"):
         # Hg: gathered heads when fewer than H (grouped-query attention): wq / wv hold Hg heads
+        # layout: the row sharding (xdot.parallel.layout): the rotary positions and the mask follow it
         wqv = _rows(wq, wv)
         bqv = _rows(bq, bv) if bq is not None else None
         n = comm.world_size
@@ -100,7 +101,7 @@ class AttnBlockFn(torch.autograd.Function):
         if rope is not None:
             # q rotated at this rank's global positions, in place and BEFORE the gather is issued
             # (with the in-place gather this block is what the peers pull); v is untouched
-            tab = rope.table(R, nq // (Hg or H), rope.resolve(comm.rank, R), qv.device, _table_dtype(qv))
+            tab = rope.table(R, nq // (Hg or H), rope.resolve(comm.rank, R, n, layout), qv.device, _table_dtype(qv))
             rope_apply(qv[..., :nq], Hg or H, *tab, out=qv[..., :nq])
         pending = start_gather(qv, comm, chunks=chunk_plan, out=gbuf)  # in flight under the row-side GEMM
         # the row side's pre-scale (scale * log2 e) folded into the k projection: one rounding, no
@@ -113,7 +114,8 @@ class AttnBlockFn(torch.autograd.Function):
             rope_apply(k, H, *tab, out=k)
         actx = _Ctx()
         actx.needs_input_grad = (any(ctx.needs_input_grad),) * 2  # a backward can run (score buffers)
-        o = SeqParallelAttention.forward(actx, k, qv, mask, H, scale, comm, pending, pre, grad_on, Hg)  # k_prescaled
+        o = SeqParallelAttention.forward(actx, k, qv, mask, H, scale, comm, pending, pre, grad_on, Hg,  # k_prescaled
+                                         layout)
         out = proj(o, wc, bc)
         ctx.actx = actx
         ctx.sync = sync  # (GradSync, module key) or None
@@ -219,4 +221,5 @@ class AttnBlockFn(torch.autograd.Function):
         # the attention's tensors were only borrowed from ctx.saved_tensors (rebuilt from there by
         # every backward): do not keep them alive through the node after this backward
         ctx.actx._saved = None
-        return (dxk, dxqv, None, dwk, dbk, dwq, dbq, dwv, dbv, dwc, dbc, None, None, None, None, None, None, None, None)
+        return (dxk, dxqv, None, dwk, dbk, dwq, dbq, dwv, dbv, dwc, dbc, None, None, None, None, None, None, None, None,
+                None)

@@ -17,7 +17,7 @@ import torch
 
 from .. import _ext
 from ..utils.env import FLAGS
-from .mask import StructuredMask, segments_of
+from .mask import GatheredColumns, StructuredMask, segments_of
 
 
 class PackedMask:
@@ -46,7 +46,7 @@ def prepare_mask(mask: Optional[torch.Tensor], B: int, R: int, T: int) -> Option
 
 
 def generate_mask(spec: StructuredMask, B: int, R: int, T: int, row_offset: Optional[int] = None, segments=None,
-                  device=None) -> PackedMask:
+                  device=None, row_segments=None) -> PackedMask:
     """The packed form of ``spec`` for ``R`` local rows starting at global row ``row_offset`` and
     ``T`` packed columns, generated on the GPU (``mask_gen`` in ``csrc/mask_pack.hip``): bitwise
     what :func:`prepare_mask` gives for ``spec.dense(...)``, with nothing R x T sized allocated.
@@ -55,9 +55,25 @@ def generate_mask(spec: StructuredMask, B: int, R: int, T: int, row_offset: Opti
     consecutive global columns (``global_start = -1``: a run that is always masked); None: the
     identity, packed column = global column.  ``row_offset`` is used where ``spec`` has none;
     ``device``: default the device of ``spec.lengths`` (else of ``spec.doc_starts``) when on a
-    GPU, else the current one."""
+    GPU, else the current one.
+
+    ``row_segments``: the local rows as runs ``(local_start, length, global_start)`` of consecutive
+    global rows (:func:`xdot.parallel.layout.row_runs`) in place of ``row_offset``; they must tile
+    the ``R`` rows exactly.  One run starting at local row 0 is the ``row_offset`` call."""
     spec.check(B)
-    ro = spec.row_offset if spec.row_offset is not None else row_offset
+    rows = None
+    if row_segments is not None:
+        rows = [tuple(int(x) for x in rn) for rn in row_segments]
+        if R > 0 and sorted((a, a + n) for a, n, _g in rows if n > 0) != _tiling(rows, R):
+            raise ValueError(f"generate_mask: the row segments must tile the {R} rows exactly, got {rows}")
+        if any(g < 0 or g + n > 2**31 - 1 for _a, n, g in rows):
+            raise ValueError(f"generate_mask: the row segments' global rows must lie in [0, 2^31), got {rows}")
+        if spec.row_offset is not None:
+            raise ValueError("generate_mask: row_segments contradict the mask's explicit row_offset")
+        rows = [rn for rn in rows if rn[1] > 0]
+        if len(rows) <= 1:  # consecutive rows: the row_offset launch
+            row_offset, rows = (rows[0][2] if rows else 0), None
+    ro = 0 if rows is not None else (spec.row_offset if spec.row_offset is not None else row_offset)
     if ro is None:
         raise ValueError("generate_mask: row_offset is not set")
     if device is None:
@@ -68,8 +84,11 @@ def generate_mask(spec: StructuredMask, B: int, R: int, T: int, row_offset: Opti
         raise ValueError(f"generate_mask: the segments must tile the {T} packed columns exactly, got {segs}")
     table = torch.tensor(segs or [(0, 0, 0)], dtype=torch.int32).reshape(-1, 3).to(device, non_blocking=True)
     ds = spec.device_doc_starts(device)
+    # (trailing arguments only when set: an extension built before they existed takes every other call)
+    tail = (() if ds is None else (ds,)) if rows is None else (
+        ds, torch.tensor(rows, dtype=torch.int32).reshape(-1, 3).to(device, non_blocking=True))
     bits, flags, bits_t = _ext.ops().mask_gen(int(B), int(R), int(T), spec.causal, int(spec.window or 0), int(ro),
-                                              spec.device_lengths(device), table, *(() if ds is None else (ds,)))
+                                              spec.device_lengths(device), table, *tail)
     return PackedMask(bits, flags, bits_t, (B, R, T))
 
 
@@ -162,7 +181,14 @@ def prepare_mask_cached(mask: Optional[torch.Tensor], B: int, R: int, T: int, ta
         if mask._T is None:
             raise ValueError("prepare_mask_cached: bind() the StructuredMask first (row offset, global columns)")
         # (one description serves any batch / row count, unlike a tensor: the shape is part of the key)
-        return MASK_CACHE.get(mask, (tag, B, R, T), lambda: generate_mask(mask, B, R, T, segments=segments_of(view, mask._T)))
+        return MASK_CACHE.get(mask, (tag, B, R, T),
+                              lambda: generate_mask(mask, B, R, T, segments=segments_of(view, mask._T, mask._cols),
+                                                    row_segments=mask._rows))
+    if isinstance(mask, GatheredColumns):
+        # a dense tensor with global columns under a layout: its columns go into gathered order
+        # first (one R x T byte copy per miss, as a chunk permutation makes), then the launch's view
+        sel = mask.select if view is None else (lambda m: view(mask.select(m)))
+        return MASK_CACHE.get(mask.tensor, ("cols", mask.key, tag), lambda: prepare_mask(sel(mask.tensor), B, R, T))
     return MASK_CACHE.get(mask, tag, lambda: prepare_mask(mask if view is None else view(mask), B, R, T))
 
 

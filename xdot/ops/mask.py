@@ -43,14 +43,17 @@ class StructuredMask:
 
     ``lengths``: a ``(B,)`` integer tensor (kept by reference: a device tensor is read by the
     kernel with no host synchronisation, and an in-place edit re-generates the cached packed
-    mask) or a sequence of ints.  ``row_offset=None``: this rank's first row, ``rank * R``,
-    resolved by the attention entry points from the communicator.
+    mask) or a sequence of ints.  ``row_offset=None``: this rank's rows, resolved by the attention
+    entry points from the communicator and their ``layout`` (``rank * R`` onward for the contiguous
+    one, the rank's two chunks for ``"zigzag"``: :mod:`xdot.parallel.layout`).  An explicit
+    ``row_offset`` says the rows are consecutive, so it contradicts ``layout="zigzag"``.
 
     The object is immutable and is not a tensor; pass it where a mask tensor goes
     (``attn_mask`` of :class:`xdot.DistributedDotProductAttn`, ``mask`` of
     :func:`xdot.seq_parallel_attention` / the ring ops)."""
 
-    __slots__ = ("causal", "window", "lengths", "row_offset", "doc_starts", "_T", "_bound", "__weakref__")
+    __slots__ = ("causal", "window", "lengths", "row_offset", "doc_starts", "_T", "_rows", "_cols", "_bound",
+                 "__weakref__")
 
     def __init__(self, causal: bool = False, window: Optional[int] = None,
                  lengths: Union[None, torch.Tensor, Sequence[int]] = None, row_offset: Optional[int] = None,
@@ -78,6 +81,8 @@ class StructuredMask:
         s(self, "row_offset", row_offset)
         s(self, "doc_starts", doc_starts)
         s(self, "_T", None)      # global column count, set on the copies bind() hands out
+        s(self, "_rows", None)   # there too: the row runs when the rows are not one run from row_offset
+        s(self, "_cols", None)   # and the global index of every gathered column when not the identity
         s(self, "_bound", {})
 
     def __setattr__(self, name, value):
@@ -114,18 +119,33 @@ class StructuredMask:
         if self.doc_starts is not None and self.doc_starts.dim() == 2 and self.doc_starts.size(0) != B:
             raise ValueError(f"StructuredMask: doc_starts has {self.doc_starts.size(0)} rows, the batch is {B}")
 
-    def bind(self, row_offset: int, T: int) -> "StructuredMask":
-        """The description with its row offset resolved (``row_offset`` is used only where the
-        object has none) and the global column count ``T`` noted: the object the cached packed
-        masks are keyed on.  The same arguments give the same object back."""
-        ro = int(row_offset) if self.row_offset is None else self.row_offset
-        key = (ro, int(T))
+    def bind(self, rows, T: int, cols=None) -> "StructuredMask":
+        """The description with its rows resolved and the global column count ``T`` noted: the
+        object the cached packed masks are keyed on.  ``rows``: this rank's first row (used only
+        where the object has no ``row_offset``) or its row runs ``[(local_start, length,
+        global_start)]``; one run is the same as its ``global_start``.  ``cols``: ``(key, index)``,
+        the global index of every gathered column (int ``(T,)``) and a hashable name for it, when
+        the gathered side is not in global order (None).  The same arguments give the same object
+        back."""
+        runs = None
+        if isinstance(rows, (list, tuple)):
+            runs = tuple((int(a), int(b), int(c)) for a, b, c in rows)
+            if len(runs) == 1 and runs[0][0] == 0:
+                rows, runs = runs[0][2], None
+            elif self.row_offset is not None:
+                raise ValueError(f"StructuredMask: row_offset={self.row_offset} says the rows are consecutive, "
+                                 f"the layout gives the runs {list(runs)}")
+        ro = None if runs is not None else (int(rows) if self.row_offset is None else self.row_offset)
+        key = (ro if runs is None else runs, int(T)) + (() if cols is None else (cols[0],))
         b = self._bound.get(key)
         if b is None:
             if len(self._bound) >= 8:
                 self._bound.pop(next(iter(self._bound)))
             b = StructuredMask(self.causal, self.window, self.lengths, ro, self.doc_starts)
             object.__setattr__(b, "_T", int(T))
+            object.__setattr__(b, "_rows", runs)
+            if cols is not None:
+                object.__setattr__(b, "_cols", cols[1].reshape(-1).to("cpu", torch.int32))
             self._bound[key] = b
         return b
 
@@ -149,12 +169,23 @@ class StructuredMask:
     def dense(self, B: int, R: int, T: int, row_offset: Optional[int] = None, device=None) -> torch.Tensor:
         """The equivalent ``(B, R, T)`` boolean tensor, built with plain torch ops (it allocates
         ``B * R * T`` bytes).  ``row_offset`` is used where the object has none."""
-        self.check(B)
         ro = self.row_offset if self.row_offset is not None else row_offset
         if ro is None:
+            self.check(B)
             raise ValueError("StructuredMask.dense: row_offset is not set")
-        gr = (int(ro) + torch.arange(R, device=device, dtype=torch.int64)).view(R, 1)
-        gc = torch.arange(T, device=device, dtype=torch.int64).view(1, T)
+        return self.dense_at(B, int(ro) + torch.arange(R, device=device, dtype=torch.int64),
+                             torch.arange(T, device=device, dtype=torch.int64), device)
+
+    def dense_at(self, B: int, row_index, col_index, device=None) -> torch.Tensor:
+        """The dense oracle at arbitrary positions: the ``(B, R, T)`` boolean tensor whose element
+        ``(b, r, t)`` is the mask of global row ``row_index[r]`` against global column
+        ``col_index[t]`` (integer tensors or sequences; a negative column is masked in every
+        row).  ``row_offset`` plays no part.  Plain torch ops; allocates ``B * R * T`` bytes."""
+        self.check(B)
+        gr = torch.as_tensor(row_index).to(device=device, dtype=torch.int64).reshape(-1)
+        gc = torch.as_tensor(col_index).to(device=device, dtype=torch.int64).reshape(-1)
+        R, T = gr.numel(), gc.numel()
+        gr, gc = gr.view(R, 1), gc.view(1, T)
         m = torch.zeros(R, T, dtype=torch.bool, device=device)
         if self.causal:
             m |= gc > gr
@@ -162,6 +193,7 @@ class StructuredMask:
             m |= gc < gr - (self.window - 1)
             if not self.causal:
                 m |= gc > gr + (self.window - 1)
+        m |= gc < 0
         m = m.unsqueeze(0).expand(B, R, T)
         if self.lengths is not None:
             m = m | (gc.view(1, 1, T) >= self.lengths.to(device=device, dtype=torch.int64).view(B, 1, 1))
@@ -172,6 +204,21 @@ class StructuredMask:
             doc_c = torch.searchsorted(ds, gc.view(T).expand(*lead, T).contiguous(), right=True)
             m = m | (doc_r.unsqueeze(-1) != doc_c.unsqueeze(-2))
         return m.contiguous()
+
+
+class GatheredColumns:
+    """A dense ``(B, R, T)`` mask tensor whose columns are in GLOBAL order while the gathered side
+    is not (``layout="zigzag"``): what the kernel paths carry in place of the tensor.
+    :func:`xdot.ops.flash.prepare_mask_cached` selects ``cols`` (the global index of every gathered
+    column) before the launch's own column view, and caches the packed result on the tensor."""
+
+    __slots__ = ("tensor", "cols", "key")
+
+    def __init__(self, tensor: torch.Tensor, cols: torch.Tensor, key):
+        self.tensor, self.cols, self.key = tensor, cols, key
+
+    def select(self, m: torch.Tensor) -> torch.Tensor:
+        return m.index_select(-1, self.cols.to(m.device))
 
 
 def _check_doc_starts(x, what: str = "doc_starts", order: bool = True) -> torch.Tensor:
@@ -197,17 +244,35 @@ def _check_doc_starts(x, what: str = "doc_starts", order: bool = True) -> torch.
     return x
 
 
-def resolve(mask, B: int, R: int, T: int, rank: int, packed: bool, device):
-    """What an attention entry point does with its mask argument: a :class:`StructuredMask` is
-    checked against the batch and bound to ``row_offset = rank * R`` (``packed``: a path that
-    generates the packed mask from it), or turned into its dense tensor once (every other
-    path); anything else passes through."""
-    if not isinstance(mask, StructuredMask):
-        return mask
+def resolve(mask, B: int, R: int, T: int, rank: int, packed: bool, device, layout: str = "contiguous"):
+    """What an attention entry point does with its mask argument.  A :class:`StructuredMask` is
+    checked against the batch and bound to this rank's rows and to the gathered side's column
+    order under ``layout`` (``packed``: a path that generates the packed mask from it), or turned
+    into its dense tensor once (every other path), columns in rank-major gathered order.  A dense
+    tensor has local rows and GLOBAL columns: under a layout whose gathered side is not in global
+    order its columns are selected into that order, here (not ``packed``) or per kernel launch
+    (:class:`GatheredColumns`).  None passes through."""
+    from ..parallel import layout as L  # (xdot.parallel imports this module)
+
+    L.check_layout(layout)
+    spec = isinstance(mask, StructuredMask)
+    if layout != "contiguous" and spec and mask.row_offset is not None:
+        raise ValueError(f"StructuredMask: row_offset={mask.row_offset} says this rank's rows are consecutive, "
+                         f"which contradicts layout={layout!r}")
+    n = T // R if R else 1
+    if n <= 1:
+        layout = "contiguous"  # a world of one: the identity
+    if not spec:
+        if mask is None or layout == "contiguous":
+            return mask
+        cols = L.gathered_cols(layout, n, R)
+        return GatheredColumns(mask, cols, (layout, n, R)) if packed else mask.index_select(-1, cols.to(mask.device))
     mask.check(B)
+    if layout == "contiguous":
+        return mask.bind(rank * R, T) if packed else mask.dense(B, R, T, rank * R, device)
     if packed:
-        return mask.bind(rank * R, T)
-    return mask.dense(B, R, T, rank * R, device)
+        return mask.bind(L.row_runs(layout, rank, n, R), T, ((layout, n, R), L.gathered_cols(layout, n, R)))
+    return mask.dense_at(B, L.global_rows(layout, rank, n, R), L.gathered_cols(layout, n, R), device)
 
 
 def run_lengths(idx: torch.Tensor) -> List[Segment]:
@@ -224,11 +289,13 @@ def run_lengths(idx: torch.Tensor) -> List[Segment]:
     return [(int(s), int(e - s), int(x) if x >= 0 else -1) for s, e, x in zip(starts.tolist(), ends.tolist(), g.tolist())]
 
 
-def segments_of(view, T: int) -> List[Segment]:
+def segments_of(view, T: int, cols: Optional[torch.Tensor] = None) -> List[Segment]:
     """The segment table of ``view`` (a function of a ``(B, R, T)`` mask giving the columns a
     kernel launch sees, or None for all of them in order): the same function applied to a
-    ``(1, 1, T)`` row of column indices, run-length encoded."""
-    idx = torch.arange(T, dtype=torch.int32).view(1, 1, T)
+    ``(1, 1, T)`` row of column indices, run-length encoded.  ``cols``: the global index of every
+    column the view starts from (the gathered side's order under a layout; None: the identity),
+    so every view composes with the layout unchanged."""
+    idx = (torch.arange(T, dtype=torch.int32) if cols is None else cols.to("cpu", torch.int32).reshape(-1)).view(1, 1, T)
     return run_lengths(idx if view is None else view(idx))
 
 

@@ -4,7 +4,9 @@ The rotation is a pass of its own between the projections and the attention
 (``csrc/rope.hip``): the flash kernels, :class:`xdot.parallel.attention.SeqParallelAttention`
 and the ring know nothing about positions.  Under sequence parallelism rank ``r`` holds rows
 ``[rR, (r+1)R)`` and rotates them at their GLOBAL positions before the all-gather: the same
-``rank * R`` convention as ``StructuredMask(row_offset=None)``.
+``rank * R`` convention as ``StructuredMask(row_offset=None)``.  Under ``layout="zigzag"``
+(:mod:`xdot.parallel.layout`) a rank's rows are two runs of global positions; the table is then
+built per run and concatenated, the apply kernel reads a per-row table either way.
 
 Convention: half-split pairs.  In a head of width ``D`` element ``i`` pairs with ``i + D/2``
 (``i < D/2``), the angle at position ``p`` is ``θ(p, i) = p · base^(−2i/D)`` and
@@ -32,8 +34,10 @@ _MAX_POS = 2**31 - 1
 class Rotary:
     """``Rotary(base=10000.0, offset=None)``: a description, like :class:`xdot.StructuredMask`.
 
-    ``offset`` is the global position of this rank's first row; ``None`` resolves to
-    ``rank * R`` at the call (0 with ``distributed=False``).  Pass it as ``rope=`` to
+    ``offset`` is the global position of this rank's first row; ``None`` resolves to this rank's
+    rows under the entry point's ``layout`` at the call (``rank * R`` onward for the contiguous one,
+    the rank's two chunks for ``"zigzag"``, which an explicit ``offset`` therefore contradicts; 0
+    with ``distributed=False``).  Pass it as ``rope=`` to
     :class:`xdot.DistributedDotProductAttn` / :func:`xdot.seq_parallel_attention`, or to
     :func:`xdot.rope`.  The ``(cos, sin)`` tables are cached on the object."""
 
@@ -54,8 +58,21 @@ class Rotary:
     def __repr__(self):
         return f"Rotary(base={self.base:g}, offset={self.offset})"
 
-    def resolve(self, rank: int, R: int) -> int:
-        """This rank's first global position: ``offset``, or ``rank * R`` where it is None."""
+    def resolve(self, rank: int, R: int, world_size: Optional[int] = None, layout: str = "contiguous"):
+        """This rank's global positions: ``offset``, or where it is None ``rank * R`` -- under a
+        ``layout`` whose rank holds several runs of rows (``"zigzag"`` with ``world_size > 1``) the
+        tuple of its row runs ``(local_start, length, global_start)``, which :meth:`table`,
+        :func:`rope` and :func:`rope_packed` take in place of an offset."""
+        if layout != "contiguous":
+            from ..parallel import layout as L  # (xdot.parallel imports this module)
+
+            L.check_layout(layout)
+            if self.offset is not None:
+                raise ValueError(f"Rotary: offset={self.offset} says this rank's rows are consecutive, which "
+                                 f"contradicts layout={layout!r}")
+            if world_size is not None and int(world_size) > 1:
+                runs = L.row_runs(layout, rank, world_size, R)
+                return runs[0][2] if len(runs) == 1 else tuple(runs)
         return int(rank) * int(R) if self.offset is None else self.offset
 
     def inv_freq(self, D: int) -> list:
@@ -63,31 +80,57 @@ class Rotary:
         the GPU table multiply the positions with."""
         return [self.base ** (-2.0 * i / D) for i in range(D // 2)]
 
-    def table(self, R: int, D: int, offset: int, device, dtype: torch.dtype = torch.float32) -> Tuple[Tensor, Tensor]:
+    def table(self, R: int, D: int, offset, device, dtype: torch.dtype = torch.float32) -> Tuple[Tensor, Tensor]:
         """``(cos, sin)``, each ``(R, D/2)``, of the angles ``(offset + row) * inv_freq[i]``:
         product and sin / cos in fp64, rounded once to ``dtype`` (fp32 for the kernels; fp64
         tensors rotate with the unrounded table).  Cached on the object, keyed on
         ``(device, R, D, offset)`` and the dtype.  GPU: ``rope_table`` (``csrc/rope.hip``);
-        CPU, or ``backend='torch'``: torch fp64."""
-        R, D, offset = int(R), int(D), int(offset)
+        CPU, or ``backend='torch'``: torch fp64.
+
+        ``offset`` may be row runs ``[(local_start, length, global_start)]`` tiling the ``R`` rows
+        in local order (:func:`xdot.parallel.layout.row_runs`): the table is built per run, the
+        same way, and concatenated; one run is its ``global_start``."""
+        R, D = int(R), int(D)
+        runs = None
+        if isinstance(offset, (list, tuple)):
+            runs = tuple((int(a), int(b), int(c)) for a, b, c in offset if int(b) > 0)
+            at = 0
+            for a, b, _c in runs:
+                if a != at:
+                    break
+                at = a + b
+            if at != R:
+                raise ValueError(f"Rotary: the row runs must tile the {R} rows in order, got {list(offset)}")
+            if len(runs) <= 1:
+                offset, runs = (runs[0][2] if runs else 0), None
+        if runs is None:
+            offset = int(offset)
         if D < 2 or D % 2:
             raise ValueError(f"Rotary: the head dim must be even, got {D}")
-        if offset < 0 or offset + R > _MAX_POS:
-            raise ValueError(f"Rotary: positions must stay below 2^31 (offset {offset} + {R} rows)")
+        for off, ln in ([(offset, R)] if runs is None else [(c, b) for _a, b, c in runs]):
+            if off < 0 or off + ln > _MAX_POS:
+                raise ValueError(f"Rotary: positions must stay below 2^31 (offset {off} + {ln} rows)")
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        key = (device, R, D, offset, dtype)
+        key = (device, R, D, offset if runs is None else runs, dtype)
         tab = self._tables.get(key)
         if tab is None:
             if len(self._tables) >= 8:
                 self._tables.pop(next(iter(self._tables)))
             inv = torch.tensor(self.inv_freq(D), dtype=torch.float64).to(device)
-            if dtype == torch.float32 and _ext.use_hip(inv):
-                tab = tuple(_ext.ops().rope_table(R, D, offset, inv))
+
+            def build(ln, off):
+                if dtype == torch.float32 and _ext.use_hip(inv):
+                    return tuple(_ext.ops().rope_table(ln, D, off, inv))
+                ang = torch.arange(off, off + ln, dtype=torch.float64, device=device).view(ln, 1) * inv.view(1, -1)
+                return torch.cos(ang).to(dtype), torch.sin(ang).to(dtype)
+
+            if runs is None:
+                tab = build(R, offset)
             else:
-                ang = torch.arange(offset, offset + R, dtype=torch.float64, device=device).view(R, 1) * inv.view(1, -1)
-                tab = (torch.cos(ang).to(dtype), torch.sin(ang).to(dtype))
+                parts = [build(b, c) for _a, b, c in runs]
+                tab = (torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]))
             self._tables[key] = tab
         return tab
 
@@ -173,10 +216,11 @@ class _RopeFn(torch.autograd.Function):
         return gx, None, None, None, None, None, None, None, None, None
 
 
-def rope(x: Tensor, num_heads: int, rotary: Rotary, *, offset: Optional[int] = None, inverse: bool = False,
+def rope(x: Tensor, num_heads: int, rotary: Rotary, *, offset=None, inverse: bool = False,
          alpha: float = 1.0, out: Optional[Tensor] = None) -> Tensor:
     """``alpha * rotate(x)`` for ``x`` ``(B, R, H*D)`` whose row ``r`` sits at position
-    ``offset + r`` (``offset=None``: ``rotary.offset``, else 0).  Autograd-aware: the backward is
+    ``offset + r`` (``offset=None``: ``rotary.offset``, else 0; row runs ``[(local_start, length,
+    global_start)]`` place each run of rows at its own positions).  Autograd-aware: the backward is
     the inverse rotation of the incoming gradient times ``alpha``.  ``x`` may be a strided view
     with unit last stride (the ``q`` half of a packed ``[q | v]`` buffer, a rank slot of a gather
     buffer); ``out=x`` rotates in place."""
@@ -197,9 +241,10 @@ def rope(x: Tensor, num_heads: int, rotary: Rotary, *, offset: Optional[int] = N
                          float(alpha), mode)
 
 
-def rope_packed(qv: Tensor, ncols: int, num_heads: int, rotary: Rotary, offset: int, alpha: float = 1.0,
+def rope_packed(qv: Tensor, ncols: int, num_heads: int, rotary: Rotary, offset, alpha: float = 1.0,
                 bwd_alpha: Optional[float] = None) -> Tensor:
-    """A copy of ``qv`` with its first ``ncols`` features rotated (the ``q`` half of a packed
+    """A copy of ``qv`` with its first ``ncols`` features rotated at ``offset`` (an int, or row runs
+    as :meth:`Rotary.table` takes them) (the ``q`` half of a packed
     ``[q | v]``; all of a ``k``), as one autograd node: the per-op graph's form (a projection's
     output may be a view, which autograd does not let a later node overwrite; the one-node module
     of :mod:`xdot.models.fused` rotates in place).  ``bwd_alpha``: the factor of the backward

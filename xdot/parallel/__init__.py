@@ -6,3 +6,4 @@ from .autograd import RightTransposeMultiplication, FullMultiplication, LeftTran
 from .attention import seq_parallel_attention, SeqParallelAttention  # noqa: F401
 from .data_parallel import broadcast_parameters, allreduce_gradients, GradSync  # noqa: F401
 from .schedule import plan_chunks, auto_offset  # noqa: F401
+from .layout import shard_rows, unshard_rows  # noqa: F401

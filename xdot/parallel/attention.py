@@ -4,7 +4,9 @@ The reference materialises the (B, H, T/N, T) score block per rank and runs six 
 distributed products per fwd+bwd (2x nt, 2x all, 2x tn), re-gathering the
 same K/V data in backward.  This path keeps the reference's sharding (rank r owns rows
 [rR, (r+1)R) of every sequence tensor; ``keys`` is the row side, ``queries``/``values`` the
-gathered side) and its exact math, but restructures the work for HBM3E + MFMA + xGMI:
+gathered side; ``layout="zigzag"`` gives rank r chunks r and 2N-1-r of 2N instead, which only the
+mask and the rotary positions see: :mod:`xdot.parallel.layout`) and its exact math, but
+restructures the work for HBM3E + MFMA + xGMI:
 
 forward
   1. all-gather the gathered-side projections ``q`` and ``v`` ONCE (two RCCL all-gathers on
@@ -39,6 +41,7 @@ from ..utils.checks import check_consistent
 from ..utils.env import FLAGS
 from ..utils.streams import _on_stream, _prep_event, _side_stream
 from . import _ref
+from .layout import check_layout
 
 __all__ = ["seq_parallel_attention", "seq_parallel_attention_packed", "start_gather", "flash_supported",
            "SeqParallelAttention"]
@@ -661,13 +664,15 @@ class SeqParallelAttention(torch.autograd.Function):
 
     @staticmethod
     @_ext.pinned
-    def forward(ctx, k, qv, mask, H, scale, comm, pending=None, k_prescaled=False, grad_on=True, Hg=None):
+    def forward(ctx, k, qv, mask, H, scale, comm, pending=None, k_prescaled=False, grad_on=True, Hg=None,
+                layout="contiguous"):
         """``k_prescaled``: ``k`` already holds ``rows * scale * log2 e`` (:func:`prescale_wanted`;
         the fused module folds it into the k projection's epilogue).  ``grad_on``: grad mode at the
         call (inside ``forward`` it is always off, and ``needs_input_grad`` ignores it).  ``Hg``:
         gathered heads when fewer than ``H`` (:func:`gathered_heads_arg`); ``qv`` is ``[q | v]`` with
-        ``Hg`` heads each."""
-        check_consistent(comm, "seq_parallel_attention", k, qv, H, Hg or H)
+        ``Hg`` heads each.  ``layout``: which global rows this rank's rows are
+        (:mod:`xdot.parallel.layout`); only the mask depends on it."""
+        check_consistent(comm, "seq_parallel_attention", k, qv, H, Hg or H, layout)
         B, R, C = k.shape
         n, rank = comm.world_size, comm.rank
         T = n * qv.shape[1]
@@ -689,13 +694,15 @@ class SeqParallelAttention(torch.autograd.Function):
             if prescaled and not k_prescaled:
                 k = flash.prescale(k, scale)
             if isinstance(mask, flash.PendingMask):
-                if len(chunks) == 1:
+                # (packed ahead in the tensor's own column order: the gathered side's only when
+                # that is the global order)
+                if len(chunks) == 1 and (layout == "contiguous" or n == 1):
                     packed_full = mask.get()
                 mask = mask.raw
         mask = getattr(mask, "raw", mask)
         # a StructuredMask: bound to this rank's rows for the kernels' generated packed masks; the
         # torch path below gets its dense tensor, built once here
-        mask = resolve_mask(mask, B, R, T, rank, use_hip, k.device)
+        mask = resolve_mask(mask, B, R, T, rank, use_hip, k.device, layout)
         segmented = n > 1 and (FLAGS.local_first or len(chunks) > 1)
         sbuf = dsbuf = None
         # a backward can run on this forward (grad mode is off inside Function.forward: autograd's
@@ -738,7 +745,7 @@ class SeqParallelAttention(torch.autograd.Function):
             dk, dqv = _backward_hip(ctx, do, k, o, lse, bufs, sbt)
         else:
             dk, dqv = _backward_torch(ctx, do, k, o, lse, bufs[0])
-        return dk.to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None, None, None
+        return dk.to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None, None, None, None
 
 
 def gather_plan(qv_shape, qv: Tensor, comm: _comm.Communicator, chunks: Optional[int] = None):
@@ -777,13 +784,20 @@ def _checked_mask(mask, k: Tensor, T: int):
 def seq_parallel_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
                                   comm: Optional[_comm.Communicator] = None,
                                   pending: Optional["_PendingGather"] = None, k_prescaled: bool = False, *,
-                                  gathered_heads: Optional[int] = None) -> Tensor:
+                                  gathered_heads: Optional[int] = None, layout: str = "contiguous") -> Tensor:
     """Fused sequence-parallel attention with a packed gathered side ``qv = [q | v]`` (B, R, 2C).
 
     ``gathered_heads``: heads of ``q`` and of ``v`` when fewer than ``num_heads`` (grouped-query
     attention: gathered head ``h // G`` serves row head ``h``, ``G = num_heads // gathered_heads``);
     ``q`` is then the first ``gathered_heads * (C // num_heads)`` columns of ``qv``.  Everything that
     crosses the wire or stays resident for the backward is that much narrower.
+
+    ``layout``: the row sharding, ``"contiguous"`` (rank ``r`` holds the global rows ``[rR, (r+1)R)``)
+    or ``"zigzag"`` (chunks ``r`` and ``2N-1-r`` of ``2N``, which balances a causal mask across ranks:
+    :mod:`xdot.parallel.layout`; ``xdot.shard_rows`` / ``xdot.unshard_rows`` split and rebuild a
+    sequence).  It decides which global row a local row is for a :class:`xdot.StructuredMask` and
+    the global order of the gathered columns; a dense mask keeps local rows and GLOBAL columns.
+    Every rank must pass the same one (``XDOT_CHECK`` compares it).
 
     ``pending``: the handle of :func:`start_gather` on this ``qv`` (the gather is issued here
     otherwise).  ``k_prescaled``: ``k`` already holds ``rows * scale * log2 e`` (only where
@@ -798,12 +812,12 @@ def seq_parallel_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor],
                          f"divide into {Hg} gathered heads")
     mask = _checked_mask(mask, k, qv.shape[1] * comm.world_size)
     return SeqParallelAttention.apply(k, qv, mask, num_heads, float(scale), comm, pending, bool(k_prescaled),
-                                      torch.is_grad_enabled(), Hg)
+                                      torch.is_grad_enabled(), Hg, check_layout(layout))
 
 
 def seq_parallel_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tensor], num_heads: int,
                            scale: float, comm: Optional[_comm.Communicator] = None, rope=None, *,
-                           gathered_heads: Optional[int] = None) -> Tensor:
+                           gathered_heads: Optional[int] = None, layout: str = "contiguous") -> Tensor:
     """Fused sequence-parallel attention on projected, head-interleaved (B, R, H*d) tensors
     (``q`` / ``v``: ``gathered_heads * d`` columns when given, grouped-query attention).
 
@@ -812,6 +826,7 @@ def seq_parallel_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tenso
     packed form is generated on the GPU, the torch path builds its dense tensor), or None.
     ``rope``: an :class:`xdot.Rotary`; ``k`` and ``q`` are rotated at this rank's global positions
     (``rank * R`` unless the object carries an offset) before the attention, ``v`` is not.
+    ``layout``: the row sharding, as :func:`seq_parallel_attention_packed` (the rotation follows it).
     Returns (B, R, H*dv) in ``k``'s dtype.
     """
     if k.dim() != 3 or q.dim() != 3 or v.dim() != 3:
@@ -819,8 +834,9 @@ def seq_parallel_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tenso
     if rope is not None:
         from ..ops.rope import rope as _rope
 
-        off = rope.resolve((comm or _comm.get_comm()).rank, k.shape[1])
+        c = comm or _comm.get_comm()
+        off = rope.resolve(c.rank, k.shape[1], c.world_size, check_layout(layout))
         k = _rope(k, num_heads, rope, offset=off)
         q = _rope(q, gathered_heads_arg(num_heads, gathered_heads) or num_heads, rope, offset=off)
     return seq_parallel_attention_packed(k, torch.cat([q, v], dim=-1), mask, num_heads, scale, comm,
-                                         gathered_heads=gathered_heads)
+                                         gathered_heads=gathered_heads, layout=layout)

@@ -47,6 +47,7 @@ from ..utils.checks import check_consistent
 from ..utils.env import FLAGS
 from ..utils.streams import _on_stream, _side_stream
 from . import _ref
+from .layout import check_layout
 from .attention import (WIDE_F32_NEEDS_SCORES, _checked_mask, _expand_heads, _fold_heads, _hip_ok, _native_gqa,
                         _prescale_rows, _q_width, gathered_heads_arg)
 
@@ -302,8 +303,8 @@ class RingAttention(torch.autograd.Function):
 
     @staticmethod
     @_ext.pinned
-    def forward(ctx, k, qv, mask, H, scale, comm, Hg=None):
-        check_consistent(comm, "ring_attention", k, qv, H, Hg or H)
+    def forward(ctx, k, qv, mask, H, scale, comm, Hg=None, layout="contiguous"):
+        check_consistent(comm, "ring_attention", k, qv, H, Hg or H, layout)
         B, R, C = k.shape
         n = comm.world_size
         # (the ring has no score buffer: exact fp32 heads past 256 run the torch path)
@@ -311,7 +312,7 @@ class RingAttention(torch.autograd.Function):
         expand = bool(Hg) and use_hip and not _native_gqa(k, H)
         # a StructuredMask: bound to this rank's rows (packed masks generated per block), or its
         # dense tensor, built once, for the torch path
-        mask = resolve_mask(mask, B, R, n * R, comm.rank, use_hip, k.device)
+        mask = resolve_mask(mask, B, R, n * R, comm.rank, use_hip, k.device, layout)
         qv = qv.contiguous()
         rings = _Rings(comm, qv, _bidir())
         prescaled, fm = False, 0
@@ -362,28 +363,31 @@ class RingAttention(torch.autograd.Function):
             acc_h.wait()
             accs = acc_in
         dqv = accs[0] if len(accs) == 1 else torch.cat(accs, dim=1)
-        return dk().to(k.dtype), dqv.to(k.dtype), None, None, None, None, None
+        return dk().to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None
 
 
 def ring_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
-                          comm: Optional[_comm.Communicator] = None, *, gathered_heads: Optional[int] = None) -> Tensor:
+                          comm: Optional[_comm.Communicator] = None, *, gathered_heads: Optional[int] = None,
+                          layout: str = "contiguous") -> Tensor:
     """Ring sequence-parallel attention with a packed gathered side ``qv = [q | v]`` (B, R, Cq + Cv);
     ``mask``: bool (B, R, T) (True = masked), a :class:`xdot.StructuredMask`, or None.  Returns (B, R, Cv) in ``k``'s dtype.
     ``gathered_heads``: heads of ``q`` / ``v`` when fewer than ``num_heads`` (grouped-query attention,
     as :func:`xdot.parallel.attention.seq_parallel_attention_packed`): the ring blocks and the
-    gradient accumulators that ride the ring are that much narrower."""
+    gradient accumulators that ride the ring are that much narrower.  ``layout``: the row sharding
+    (``"contiguous"`` | ``"zigzag"``), as :func:`xdot.parallel.attention.seq_parallel_attention_packed`."""
     comm = comm or _comm.get_comm()
     Hg = gathered_heads_arg(num_heads, gathered_heads)
     if k.dim() != 3 or qv.dim() != 3 or k.shape[-1] % num_heads or qv.shape[-1] <= _q_width(k, num_heads, Hg) \
             or qv.shape[:2] != k.shape[:2]:
         raise ValueError("ring_attention expects k (B, R, C) and qv (B, R, Cq + Cv) with equal R")
     mask = _checked_mask(mask, k, qv.shape[1] * comm.world_size)
-    return RingAttention.apply(k, qv, mask, num_heads, float(scale), comm, Hg)
+    return RingAttention.apply(k, qv, mask, num_heads, float(scale), comm, Hg, check_layout(layout))
 
 
 def ring_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
-                   comm: Optional[_comm.Communicator] = None, *, gathered_heads: Optional[int] = None) -> Tensor:
+                   comm: Optional[_comm.Communicator] = None, *, gathered_heads: Optional[int] = None,
+                   layout: str = "contiguous") -> Tensor:
     """:func:`ring_attention_packed` on separate head-interleaved (B, R, H*d) ``k``, ``q``, ``v``
     (``q`` / ``v``: ``gathered_heads * d`` columns when given)."""
     return ring_attention_packed(k, torch.cat([q, v], dim=-1), mask, num_heads, scale, comm,
-                                 gathered_heads=gathered_heads)
+                                 gathered_heads=gathered_heads, layout=layout)
