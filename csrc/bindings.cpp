@@ -448,6 +448,11 @@ TORCH_LIBRARY(xdot, m) {
   m.def("flash_prescale(Tensor x, float scale) -> Tensor");
   m.def("rope_table(int R, int D, int offset, Tensor inv_freq) -> (Tensor, Tensor)");
   m.def("rope_apply(Tensor x, Tensor cos, Tensor sin, int H, bool inverse, float alpha, Tensor(a!) out) -> ()");
+  m.def("headnorm_plan(int B, int R, int H, int D, ScalarType dtype) -> int[]");
+  m.def("headnorm_fwd(Tensor x, Tensor weight, Tensor? cos, Tensor? sin, int H, float eps, float alpha, Tensor(a!) out, "
+        "bool save) -> (Tensor, Tensor)");
+  m.def("headnorm_bwd(Tensor g, Tensor x, Tensor rstd, Tensor weight, Tensor? cos, Tensor? sin, int H, float alpha, "
+        "Tensor(a!) dx, bool need_dw) -> Tensor");
   m.def("mse_fwd(Tensor y, Tensor t) -> (Tensor, Tensor)");
   m.def("proj(Tensor x, Tensor w, Tensor? bias, bool nn, Tensor(a!)? out=None, int force=0, float alpha=1.0) -> Tensor");
   m.def("wgrad(Tensor dy, Tensor x, ScalarType out_dtype, int splits=0) -> Tensor");

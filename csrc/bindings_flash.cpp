@@ -477,6 +477,161 @@ void rope_apply(const at::Tensor& x, const at::Tensor& cosb, const at::Tensor& s
   launched(xdot_rope_apply_launch(&a, dt_code(x.scalar_type()), mode, cur_stream(x)), "rope_apply", "shape");
 }
 
+// ---- per-head RMSNorm fused with the rotation (csrc/headnorm.hip) ----
+// the (B, R, C) views of one headnorm call: unit inner stride, any non-negative row / batch strides,
+// inside their storage (as rope_apply).  Returns batch / row strides per view and whether every
+// view is on the 16-byte grid
+struct HnViews { int64_t st[3][2]; bool vec; };
+
+HnViews hn_views(std::initializer_list<const at::Tensor*> ts, int64_t B, int64_t R, int64_t C, const char* op) {
+  HnViews v{};
+  v.vec = true;
+  const at::Tensor& first = **ts.begin();
+  const int64_t V = 16 / (int64_t)first.element_size();
+  int k = 0;
+  for (const at::Tensor* t : ts) {
+    TORCH_CHECK(t->is_cuda() && t->device() == first.device(), "xdot.", op, ": tensors of one GPU required");
+    TORCH_CHECK(t->dim() == 3 && t->size(0) == B && t->size(1) == R && t->size(2) == C &&
+                    t->scalar_type() == first.scalar_type(),
+                "xdot.", op, ": the views must be (B, R, H*D) of one dtype");
+    TORCH_CHECK(t->stride(2) == 1 || C == 1, "xdot.", op, ": the last dimension must have stride 1");
+    const int64_t sb = B > 1 ? t->stride(0) : 0, sr = R > 1 ? t->stride(1) : 0;
+    TORCH_CHECK(sb >= 0 && sr >= 0, "xdot.", op, ": negative strides");
+    TORCH_CHECK((B - 1) * sb + (R - 1) * sr + C <= avail_elems(*t), "xdot.", op, ": view out of bounds");
+    v.vec = v.vec && aligned16(t->data_ptr()) && sb % V == 0 && sr % V == 0;
+    v.st[k][0] = sb;
+    v.st[k][1] = sr;
+    ++k;
+  }
+  return v;
+}
+
+// `dst` is written while `src` is read: the same view (in place) or disjoint memory
+void hn_no_overlap(const at::Tensor& src, const int64_t* ss, const at::Tensor& dst, const int64_t* ds, int64_t B,
+                   int64_t R, int64_t C, const char* op) {
+  if (src.data_ptr() == dst.data_ptr()) {
+    TORCH_CHECK(ss[0] == ds[0] && ss[1] == ds[1], "xdot.", op, ": an in-place output must be the same view as its input");
+    return;
+  }
+  const char* sb = static_cast<const char*>(src.data_ptr());
+  const char* db = static_cast<const char*>(dst.data_ptr());
+  const int64_t es = (int64_t)src.element_size();
+  const int64_t se = ((B - 1) * ss[0] + (R - 1) * ss[1] + C) * es, de = ((B - 1) * ds[0] + (R - 1) * ds[1] + C) * es;
+  TORCH_CHECK(sb + se <= db || db + de <= sb, "xdot.", op, ": input and output overlap");
+}
+
+// weight (D,) in x's dtype or fp32; cos / sin both or neither, contiguous fp32 (R, D/2)
+void hn_params(const at::Tensor& x, const at::Tensor& weight, const OptT& cosb, const OptT& sinb, int64_t R, int64_t D,
+               const char* op) {
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf || x.scalar_type() == at::kFloat,
+              "xdot.", op, ": bf16/fp16/fp32 only");
+  TORCH_CHECK(weight.is_cuda() && weight.device() == x.device() && weight.dim() == 1 && weight.size(0) == D &&
+                  weight.is_contiguous() &&
+                  (weight.scalar_type() == x.scalar_type() || weight.scalar_type() == at::kFloat),
+              "xdot.", op, ": weight must be a contiguous (D,) = (", D, ",) tensor of x's dtype or fp32");
+  const bool hc = cosb.has_value() && cosb->defined(), hs = sinb.has_value() && sinb->defined();
+  TORCH_CHECK(hc == hs, "xdot.", op, ": cos and sin go together");
+  if (hc) {
+    TORCH_CHECK(D % 2 == 0, "xdot.", op, ": the rotation needs an even head dim, got ", D);
+    TORCH_CHECK(cosb->is_cuda() && sinb->is_cuda() && cosb->device() == x.device() && sinb->device() == x.device() &&
+                    cosb->scalar_type() == at::kFloat && sinb->scalar_type() == at::kFloat && cosb->is_contiguous() &&
+                    sinb->is_contiguous() && cosb->dim() == 2 && cosb->size(0) == R && cosb->size(1) == D / 2 &&
+                    sinb->sizes() == cosb->sizes(),
+                "xdot.", op, ": cos / sin must be contiguous fp32 (R, D/2)");
+  }
+}
+
+xdot::HeadNormPlan hn_plan(int64_t B, int64_t R, int64_t H, int64_t D, int64_t esize, const char* op) {
+  xdot::HeadNormPlan p{};
+  TORCH_CHECK(B < (1LL << 31) && R < (1LL << 31) && H * D < (1LL << 31) && B * H < (1LL << 31), "xdot.", op, ": too large");
+  TORCH_CHECK(xdot_headnorm_plan((int)B, (int)R, (int)H, (int)D, (int)esize, &p) == 0, "xdot.", op,
+              ": head dim ", D, " is too wide (one wave reduces a head row: D <= ", 64 * 2 * (16 / esize), ")");
+  return p;
+}
+
+// [G, rows per workgroup, forward grid x, y, backward grid x, y] of a headnorm launch (no launch)
+std::vector<int64_t> headnorm_plan(int64_t B, int64_t R, int64_t H, int64_t D, at::ScalarType dtype) {
+  TORCH_CHECK(B > 0 && R > 0 && H > 0 && D > 0, "xdot.headnorm_plan: shape");
+  const auto p = hn_plan(B, R, H, D, (int64_t)c10::elementSize(dtype), "headnorm_plan");
+  return {p.G, p.rows_per_wg, p.fwd_gx, p.fwd_gy, p.bwd_gx, p.bwd_gy};
+}
+
+// out = alpha * rotate(x * rstd * weight) per head of x (B, R, H*D) (rotation with a table only);
+// returns rstd (B, R, H) fp32 and, with save, a contiguous bit copy of x (else an empty tensor).
+// out may be x itself (the same view)
+std::tuple<at::Tensor, at::Tensor> headnorm_fwd(const at::Tensor& x, const at::Tensor& weight, const OptT& cosb,
+                                                const OptT& sinb, int64_t H, double eps, double alpha, at::Tensor& out,
+                                                bool save) {
+  Range rr_("xdot.headnorm_fwd");
+  TORCH_CHECK(x.is_cuda() && x.dim() == 3, "xdot.headnorm_fwd: x must be a (B, R, H*D) GPU tensor");
+  const int64_t B = x.size(0), R = x.size(1), C = x.size(2);
+  TORCH_CHECK(H > 0 && C > 0 && C % H == 0, "xdot.headnorm_fwd: H*D features, got C=", C, " H=", H);
+  TORCH_CHECK(eps > 0.0, "xdot.headnorm_fwd: eps must be positive");
+  const int64_t D = C / H;
+  hn_params(x, weight, cosb, sinb, R, D, "headnorm_fwd");
+  const HnViews v = hn_views({&x, static_cast<const at::Tensor*>(&out)}, B, R, C, "headnorm_fwd");
+  hn_no_overlap(x, v.st[0], out, v.st[1], B, R, C, "headnorm_fwd");
+  auto rstd = at::empty({B, R, H}, x.options().dtype(at::kFloat));
+  auto saved = save ? at::empty({B, R, C}, x.options()) : at::empty({0}, x.options());
+  if (x.numel() == 0) return {rstd, saved};
+  hn_plan(B, R, H, D, (int64_t)x.element_size(), "headnorm_fwd");
+  const bool rot = cosb.has_value() && cosb->defined();
+  xdot::HeadNormArgs a{};
+  a.x = x.data_ptr(); a.out = out.data_ptr(); a.save = save ? saved.data_ptr() : nullptr;
+  a.rstd = rstd.data_ptr<float>(); a.w = weight.data_ptr(); a.w_f32 = weight.scalar_type() == at::kFloat;
+  a.cos = rot ? cosb->data_ptr<float>() : nullptr; a.sin = rot ? sinb->data_ptr<float>() : nullptr;
+  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D;
+  a.xs_b = v.st[0][0]; a.xs_r = v.st[0][1]; a.os_b = v.st[1][0]; a.os_r = v.st[1][1];
+  a.alpha = (float)alpha; a.eps = (float)eps; a.inv_d = 1.0f / (float)D;
+  c10::DeviceGuard guard(x.device());
+  launched(xdot_headnorm_fwd_launch(&a, dt_code(x.scalar_type()), v.vec ? 1 : 0, cur_stream(x)), "headnorm_fwd", "shape");
+  return {rstd, saved};
+}
+
+// dx = rstd * (gw - xh * mean(gw . xh)) with gy = alpha * rotate^-1(g), xh = x * rstd, gw = gy * weight,
+// written to dx (may be g itself); returns dw = sum gy . xh in weight's dtype (need_dw), else empty.
+// Two launches: the pass, which leaves one fp32 (D,) partial per workgroup, and their ordered sum
+at::Tensor headnorm_bwd(const at::Tensor& g, const at::Tensor& x, const at::Tensor& rstd, const at::Tensor& weight,
+                        const OptT& cosb, const OptT& sinb, int64_t H, double alpha, at::Tensor& dx, bool need_dw) {
+  Range rr_("xdot.headnorm_bwd");
+  TORCH_CHECK(g.is_cuda() && g.dim() == 3, "xdot.headnorm_bwd: g must be a (B, R, H*D) GPU tensor");
+  const int64_t B = g.size(0), R = g.size(1), C = g.size(2);
+  TORCH_CHECK(H > 0 && C > 0 && C % H == 0, "xdot.headnorm_bwd: H*D features, got C=", C, " H=", H);
+  const int64_t D = C / H;
+  hn_params(g, weight, cosb, sinb, R, D, "headnorm_bwd");
+  const HnViews v = hn_views({&g, &x, static_cast<const at::Tensor*>(&dx)}, B, R, C, "headnorm_bwd");
+  hn_no_overlap(g, v.st[0], dx, v.st[2], B, R, C, "headnorm_bwd");
+  hn_no_overlap(x, v.st[1], dx, v.st[2], B, R, C, "headnorm_bwd");
+  TORCH_CHECK(x.data_ptr() != dx.data_ptr() || x.numel() == 0, "xdot.headnorm_bwd: dx may overwrite g, not x");
+  TORCH_CHECK(rstd.is_cuda() && rstd.device() == g.device() && rstd.scalar_type() == at::kFloat && rstd.is_contiguous() &&
+                  rstd.dim() == 3 && rstd.size(0) == B && rstd.size(1) == R && rstd.size(2) == H,
+              "xdot.headnorm_bwd: rstd must be contiguous fp32 (B, R, H)");
+  auto dw = need_dw ? at::empty({D}, weight.options()) : at::empty({0}, weight.options());
+  if (g.numel() == 0) {
+    if (need_dw) dw.zero_();
+    return dw;
+  }
+  const auto p = hn_plan(B, R, H, D, (int64_t)g.element_size(), "headnorm_bwd");
+  const int64_t nparts = (int64_t)p.bwd_gx * p.bwd_gy;
+  auto part = at::empty({nparts, D}, g.options().dtype(at::kFloat));
+  const bool rot = cosb.has_value() && cosb->defined();
+  xdot::HeadNormArgs a{};
+  a.x = x.data_ptr(); a.g = g.data_ptr(); a.out = dx.data_ptr(); a.rstd = rstd.data_ptr<float>();
+  a.w = weight.data_ptr(); a.w_f32 = weight.scalar_type() == at::kFloat; a.part = part.data_ptr<float>();
+  a.cos = rot ? cosb->data_ptr<float>() : nullptr; a.sin = rot ? sinb->data_ptr<float>() : nullptr;
+  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D;
+  a.gs_b = v.st[0][0]; a.gs_r = v.st[0][1]; a.xs_b = v.st[1][0]; a.xs_r = v.st[1][1];
+  a.os_b = v.st[2][0]; a.os_r = v.st[2][1];
+  a.alpha = (float)alpha; a.inv_d = 1.0f / (float)D;
+  c10::DeviceGuard guard(g.device());
+  launched(xdot_headnorm_bwd_launch(&a, dt_code(g.scalar_type()), v.vec ? 1 : 0, cur_stream(g)), "headnorm_bwd", "shape");
+  if (need_dw)
+    launched(xdot_headnorm_dw_launch(part.data_ptr<float>(), dw.data_ptr(), (int)nparts, (int)D, dt_code(weight.scalar_type()),
+                                     cur_stream(g)),
+             "headnorm_dw", "shape");
+  return dw;
+}
+
 // δ = rowsum(dO ⊙ O) per (b, h, row), fp32 (B, H, R)
 at::Tensor flash_bwd_delta(const at::Tensor& dout, const at::Tensor& out, int64_t H) {
   Range rr_("xdot.flash_bwd_delta");
@@ -622,6 +777,7 @@ TORCH_LIBRARY_IMPL(xdot, CompositeExplicitAutograd, m) {
   m.impl("flash_splits", &flash_splits);
   m.impl("flash_fwd_plan", &flash_fwd_plan);
   m.impl("flash_cols_plan", &flash_cols_plan);
+  m.impl("headnorm_plan", &headnorm_plan);
 }
 
 TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
@@ -635,6 +791,8 @@ TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("flash_prescale", &flash_prescale);
   m.impl("rope_table", &rope_table);
   m.impl("rope_apply", &rope_apply);
+  m.impl("headnorm_fwd", &headnorm_fwd);
+  m.impl("headnorm_bwd", &headnorm_bwd);
   m.impl("flash_fwd_partial", &flash_fwd_partial);
   m.impl("flash_fwd_combine", &flash_fwd_combine);
   m.impl("flash_fwd_merge", &flash_fwd_merge);

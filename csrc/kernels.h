@@ -189,6 +189,36 @@ struct RopeArgs {
   float alpha;             // out = alpha * rotate(x)
   int inverse;             // 1: rotate by -theta
 };
+// per-head RMSNorm of x (B, R, H*D) with a (D,) gain, fused with the rotation (csrc/headnorm.hip).
+// Forward: x -> out (may be x), rstd, and (save != nullptr) a bit copy of x.  Backward: g (the
+// gradient w.r.t. out), x (the pre-norm input), rstd -> out (dx, may be g) and fp32 (D,) partials.
+struct HeadNormArgs {
+  const void* x;           // forward: the input view; backward: the saved pre-norm x
+  const void* g;           // backward only: gradient w.r.t. the forward's out
+  void* out;               // forward: out; backward: dx
+  void* save;              // forward only: contiguous (B, R, H*D) copy of x, or nullptr
+  float* rstd;             // (B, R, H) fp32: written by the forward, read by the backward
+  const void* w;           // (D,) gain, x's dtype or fp32 (w_f32)
+  const float* cos;        // (R, D/2) fp32 table, or nullptr: no rotation
+  const float* sin;
+  float* part;             // backward only: (nparts, D) fp32, one row per workgroup
+  int B, R, H, D;
+  int w_f32;
+  int64_t xs_b, xs_r;      // strides in elements of x, g, out (unit inner stride)
+  int64_t gs_b, gs_r;
+  int64_t os_b, os_r;
+  float alpha;             // forward: out = alpha * rotate(y); backward: gy = alpha * rotate^-1(g)
+  float eps;
+  float inv_d;             // 1 / D rounded to fp32
+};
+// how a (B, R, H, D) problem of esize-byte elements is laid on the GPU: lanes per head row (a power
+// of two), head rows per workgroup, and the forward's and backward's grids; the backward writes
+// bwd_gx * bwd_gy partials
+struct HeadNormPlan {
+  int G, rows_per_wg;
+  int fwd_gx, fwd_gy;
+  int bwd_gx, bwd_gy;
+};
 namespace ipc {
 constexpr int MAXR = 8;     // ranks of one node
 constexpr int MAXG = 256;   // workgroups (byte ranges) per collective
@@ -280,6 +310,14 @@ int xdot_rope_table_launch(float* cos, float* sin, const double* inv_freq, int R
 // mode 1: 16-byte vectors (D/2 a multiple of the vector width, pointers and strides 16-byte
 // aligned), 2: unaligned vectors plus a scalar tail (D/2 not a multiple), 0: scalar
 int xdot_rope_apply_launch(const xdot::RopeArgs* a, int dt, int mode, hipStream_t st);
+// per-head RMSNorm (csrc/headnorm.hip).  plan: -1 when the head dim needs more than one wave per
+// head row (D/2 > 64 vectors of 16 bytes).  vec 1: 16-byte vectors where a lane's chunk is whole,
+// 0: scalar loads and stores (the same chunks and the same order of operations: bitwise equal)
+int xdot_headnorm_plan(int B, int R, int H, int D, int esize, xdot::HeadNormPlan* p);
+int xdot_headnorm_fwd_launch(const xdot::HeadNormArgs* a, int dt, int vec, hipStream_t st);
+int xdot_headnorm_bwd_launch(const xdot::HeadNormArgs* a, int dt, int vec, hipStream_t st);
+// dw (D elements of dtype dto) = the nparts rows of part summed in a fixed order
+int xdot_headnorm_dw_launch(const float* part, void* dw, int nparts, int D, int dto, hipStream_t st);
 // rows per workgroup of the forward kernel (128)
 int xdot_flash_fwd_rows_per_wg();
 // one AdamW step over a->nt tensors of dtype dt (params/grads), fp32 moments

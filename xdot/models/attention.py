@@ -61,6 +61,13 @@ Keyword-only knobs (each mirrors an environment flag, the argument
                 contradicts ``'zigzag'``), a dense ``attn_mask`` keeps local rows and GLOBAL columns.
                 Communication, gather chunks and kernels are layout-blind; ``distributed=False``
                 ignores it (a world of one is the identity).
+``qk_norm``     ``True``: QK-norm, an RMSNorm over each head's ``key_dim // num_heads`` features of
+                the projected ``k`` (its ``num_heads`` heads) and ``q`` (its ``num_gathered_heads``
+                heads) with a learnable gain each: two :class:`xdot.HeadRMSNorm` submodules,
+                ``keys_norm`` and ``queries_norm`` (two more ``state_dict`` keys).  Order: projection
+                -> norm -> rope -> attention, on every path; ``v`` is untouched.  On the GPU the norm
+                and the rotation are ONE pass (:mod:`xdot.ops.headnorm`).  ``False`` (default): no
+                submodules, no launch; ``qk_norm_eps`` is the ``eps`` under the square root.
 """
 from __future__ import annotations
 
@@ -74,6 +81,7 @@ from torch import Tensor
 from .. import _ext
 from ..ops.linear import linear
 from ..ops.mask import StructuredMask
+from ..ops.headnorm import HeadRMSNorm, head_rms_norm, norm_packed
 from ..ops.rope import Rotary, rope as _rope, rope_packed
 from ..ops.softmax import scale_mask_softmax
 from ..parallel.autograd import FullMultiplication, RightTransposeMultiplication
@@ -135,7 +143,8 @@ class DistributedDotProductAttn(nn.Module):
                  distributed: bool = True, *, impl: str = "auto", fused: Optional[bool] = None,
                  backend: str = "auto", dtype: Optional[torch.dtype] = None, chunk_plan: Optional[int] = None,
                  comm: Optional[_comm.Communicator] = None, rope: Optional[Rotary] = None,
-                 num_gathered_heads: Optional[int] = None, layout: str = "contiguous"):
+                 num_gathered_heads: Optional[int] = None, layout: str = "contiguous", qk_norm: bool = False,
+                 qk_norm_eps: float = 1e-6):
         super().__init__()
         check_layout(layout)
         if fused is not None:
@@ -165,6 +174,8 @@ class DistributedDotProductAttn(nn.Module):
                 raise TypeError(f"rope must be an xdot.Rotary or None, got {type(rope).__name__}")
             if (key_dim // num_heads) % 2:
                 raise ValueError(f"rope needs an even head dim, got {key_dim // num_heads}")
+        if not float(qk_norm_eps) > 0.0:
+            raise ValueError(f"qk_norm_eps must be positive, got {qk_norm_eps!r}")
         self.num_heads = num_heads
         self.num_gathered_heads = int(num_gathered_heads)
         self.value_dim = value_dim
@@ -183,6 +194,11 @@ class DistributedDotProductAttn(nn.Module):
         self.queries = nn.Linear(query_dim, self.num_gathered_heads * self.dim, bias=add_bias)
         self.values = nn.Linear(value_dim, self.num_gathered_heads * (value_dim // num_heads), bias=add_bias)
         self.composition = nn.Linear(value_dim, value_dim, bias=add_bias)
+        self.qk_norm = bool(qk_norm)
+        self.qk_norm_eps = float(qk_norm_eps)
+        if self.qk_norm:  # (no submodule without it: reference checkpoints keep loading)
+            self.keys_norm = HeadRMSNorm(self.dim, self.qk_norm_eps)
+            self.queries_norm = HeadRMSNorm(self.dim, self.qk_norm_eps)
         # weakref to an attached xdot.parallel.GradSync (set by it): the fused node hands it the
         # parameter gradients as they are computed (early all-reduce)
         self._xdot_grad_sync = None
@@ -233,9 +249,9 @@ class DistributedDotProductAttn(nn.Module):
                 # zero-padded to the next kernel dim, same scale 1/sqrt(dk)
                 qv = self._project_qv(queries, values)
                 q, k = qv[..., :Hg * dk], self._proj(self.keys, keys)
-                if self.rope is not None:  # at width dk, before the zero padding
-                    off = self.rope.resolve(comm.rank, k.shape[1], comm.world_size, lay)
-                    q, k = _rope(q, Hg, self.rope, offset=off), _rope(k, H, self.rope, offset=off)
+                if self.rope is not None or self.qk_norm:  # at width dk, before the zero padding
+                    off = self._rope_offset(comm, k.shape[1], lay)
+                    q, k = self._norm_rope(q, Hg, False, off), self._norm_rope(k, H, True, off)
                 # (the Hg gathered heads and the H row heads are padded separately)
                 qv = torch.cat([pa.pad_heads(q, Hg, dk, Dp), pa.pad_heads(qv[..., Hg * dk:], Hg, dv, Dp)], dim=-1)
                 k = pa.pad_heads(k, H, dk, Dp)
@@ -268,20 +284,29 @@ class DistributedDotProductAttn(nn.Module):
                     sync = (gs, id(self))
                 return AttnBlockFn.apply(keys, queries, attn_mask, self.keys.weight, self.keys.bias, wq, bq, wv, bv,
                                          self.composition.weight, self.composition.bias, self.num_heads, scale, comm,
-                                         self.chunk_plan, sync, torch.is_grad_enabled(), self.rope, gh, lay)
+                                         self.chunk_plan, sync, torch.is_grad_enabled(), self.rope, gh, lay,
+                                         *((self.keys_norm.weight, self.queries_norm.weight, self.qk_norm_eps)
+                                           if self.qk_norm else ()))
             # gathered side first: its all-gather runs while the row-side GEMM computes
             qv = self._project_qv(queries, values)
             pre = False
-            if self.rope is not None:  # q rotated before the gather is issued
-                off = self.rope.resolve(comm.rank, qv.shape[1], comm.world_size, lay)
+            off = self._rope_offset(comm, qv.shape[1], lay)
+            if self.qk_norm:  # q normalised and rotated, in one pass, before the gather is issued
+                qv = norm_packed(qv, Hg * dk, Hg, self.queries_norm.weight, self.qk_norm_eps, self.rope, off)
+            elif self.rope is not None:  # q rotated before the gather is issued
                 qv = rope_packed(qv, Hg * dk, Hg, self.rope, off)
             pending = start_gather(qv, comm, chunks=self.chunk_plan)
             k = self._proj(self.keys, keys)
-            if self.rope is not None:
-                # the row side's pre-scale rides in the rotation pass (its gradient comes back
+            if self.rope is not None or self.qk_norm:
+                # the row side's pre-scale rides in the rotation / norm pass (its gradient comes back
                 # w.r.t. the unscaled rows: no factor in the backward)
                 pre = pa.prescale_wanted(k, qv, H, gh)
-                k = rope_packed(k, H * dk, H, self.rope, off, alpha=scale * _LOG2E if pre else 1.0, bwd_alpha=1.0)
+                al = scale * _LOG2E if pre else 1.0
+                if self.qk_norm:
+                    k = norm_packed(k, H * dk, H, self.keys_norm.weight, self.qk_norm_eps, self.rope, off, alpha=al,
+                                    bwd_alpha=1.0)
+                else:
+                    k = rope_packed(k, H * dk, H, self.rope, off, alpha=al, bwd_alpha=1.0)
             o = seq_parallel_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm, pending=pending,
                                               k_prescaled=pre, gathered_heads=gh, layout=lay)
             return self._proj(self.composition, o)
@@ -291,8 +316,12 @@ class DistributedDotProductAttn(nn.Module):
             comm = (self.comm or _comm.get_comm()) if self.distributed else _comm.LocalComm()
             qv = self._project_qv(queries, values)
             k = self._proj(self.keys, keys)
-            if self.rope is not None:
-                off = self.rope.resolve(comm.rank, k.shape[1], comm.world_size, lay)
+            off = self._rope_offset(comm, k.shape[1], lay)
+            if self.qk_norm:
+                qv = norm_packed(qv, self.num_gathered_heads * self.dim, self.num_gathered_heads,
+                                 self.queries_norm.weight, self.qk_norm_eps, self.rope, off)
+                k = norm_packed(k, k.shape[-1], self.num_heads, self.keys_norm.weight, self.qk_norm_eps, self.rope, off)
+            elif self.rope is not None:
                 qv = rope_packed(qv, self.num_gathered_heads * self.dim, self.num_gathered_heads, self.rope, off)
                 k = rope_packed(k, k.shape[-1], self.num_heads, self.rope, off)
             o = ring_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm,
@@ -302,12 +331,24 @@ class DistributedDotProductAttn(nn.Module):
         k = self._proj(self.keys, keys)
         q = self._proj(self.queries, queries)
         v = self._proj(self.values, values)
-        if self.rope is not None:
+        if self.rope is not None or self.qk_norm:
             c = (self.comm or _comm.get_comm()) if self.distributed else _comm.LocalComm()
-            off = self.rope.resolve(c.rank, k.shape[1], c.world_size, lay)
-            k = _rope(k, self.num_heads, self.rope, offset=off)
-            q = _rope(q, self.num_gathered_heads, self.rope, offset=off)
+            off = self._rope_offset(c, k.shape[1], lay)
+            k = self._norm_rope(k, self.num_heads, True, off)
+            q = self._norm_rope(q, self.num_gathered_heads, False, off)
         return self._proj(self.composition, self._materialized(k, q, v, attn_mask, scale))
+
+    def _rope_offset(self, comm, R: int, lay: str):
+        """This rank's rotary positions (None without ``rope``)."""
+        return None if self.rope is None else self.rope.resolve(comm.rank, R, comm.world_size, lay)
+
+    def _norm_rope(self, t: Tensor, heads: int, row_side: bool, off) -> Tensor:
+        """projection -> norm -> rope of one operand as a tensor of its own (the paths that do not
+        pack ``[q | v]``): one pass where both are set."""
+        if not self.qk_norm:
+            return _rope(t, heads, self.rope, offset=off)
+        norm = self.keys_norm if row_side else self.queries_norm
+        return head_rms_norm(t, heads, norm.weight, self.qk_norm_eps, rotary=self.rope, offset=off)
 
     def _proj(self, layer: nn.Linear, x: Tensor) -> Tensor:
         """``layer(x)`` (compute dtype) with the split-K MFMA weight gradient (:mod:`xdot.ops.linear`)."""
@@ -364,4 +405,5 @@ class DistributedDotProductAttn(nn.Module):
                 f"dtype={self.compute_dtype}, chunk_plan={self.chunk_plan}"
                 + (f", rope={self.rope!r}" if self.rope is not None else "")
                 + (f", num_gathered_heads={self.num_gathered_heads}" if self.num_gathered_heads != self.num_heads else "")
-                + (f", layout={self.layout}" if self.layout != "contiguous" else ""))
+                + (f", layout={self.layout}" if self.layout != "contiguous" else "")
+                + (f", qk_norm=True, qk_norm_eps={self.qk_norm_eps:g}" if self.qk_norm else ""))

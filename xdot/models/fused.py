@@ -21,6 +21,10 @@ restores it), and hands back the eight parameter gradients and the input gradien
 With ``rope`` (an :class:`xdot.Rotary`) q is rotated in place in ``[q|v]`` before the gather is
 issued and k after its projection; the backward inverse-rotates ``dk`` and ``dq`` in place before
 the projections' gradients read them (``csrc/rope.hip``: two launches each way).
+With QK-norm (``norm``: the two gains and ``eps``) the same two spots run the norm and the rotation
+as one pass (``csrc/headnorm.hip``): the forward's passes also leave ``rstd`` and a bit copy of the
+pre-norm ``k`` / ``q`` (both are overwritten in place), the backward's passes run in place on ``dk``
+and the ``q`` part of ``d[q|v]`` and return the two gain gradients.
 """
 from __future__ import annotations
 
@@ -28,6 +32,7 @@ import torch
 
 from .. import _ext
 from ..ops.linear import linear_backward, native_wgrad, proj, weight_grad_pair
+from ..ops.headnorm import head_rms_norm_apply, head_rms_norm_backward
 from ..ops.rope import _table_dtype, rope_apply
 from ..utils.env import FLAGS
 from ..utils.streams import _on_stream, _side_stream
@@ -78,9 +83,10 @@ class AttnBlockFn(torch.autograd.Function):
     @staticmethod
     @_ext.pinned
     def forward(ctx, xk, xqv, mask, wk, bk, wq, bq, wv, bv, wc, bc, H, scale, comm, chunk_plan, sync=None,
-                grad_on=True, rope=None, Hg=None, layout="contiguous"):
+                grad_on=True, rope=None, Hg=None, layout="contiguous", wkn=None, wqn=None, norm_eps=1e-6):
         # Hg: gathered heads when fewer than H (grouped-query attention): wq / wv hold Hg heads
         # layout: the row sharding (xdot.parallel.layout): the rotary positions and the mask follow it
+        # wkn / wqn: the (D,) gains of QK-norm on k / q (both or neither), norm_eps its eps
         wqv = _rows(wq, wv)
         bqv = _rows(bq, bv) if bq is not None else None
         n = comm.world_size
@@ -102,16 +108,32 @@ class AttnBlockFn(torch.autograd.Function):
             # q rotated at this rank's global positions, in place and BEFORE the gather is issued
             # (with the in-place gather this block is what the peers pull); v is untouched
             tab = rope.table(R, nq // (Hg or H), rope.resolve(comm.rank, R, n, layout), qv.device, _table_dtype(qv))
-            rope_apply(qv[..., :nq], Hg or H, *tab, out=qv[..., :nq])
+            if wqn is None:
+                rope_apply(qv[..., :nq], Hg or H, *tab, out=qv[..., :nq])
+        nsaved = ()
+        keep = any(ctx.needs_input_grad)  # a backward can run: the norm passes keep their inputs
+        if wqn is not None:
+            # q normalised and rotated in ONE pass, in place in the gather slot, before the gather
+            _, rstd_q, q0 = head_rms_norm_apply(qv[..., :nq], Hg or H, wqn, norm_eps, *(tab or (None, None)),
+                                                out=qv[..., :nq], save=keep)
         pending = start_gather(qv, comm, chunks=chunk_plan, out=gbuf)  # in flight under the row-side GEMM
         # the row side's pre-scale (scale * log2 e) folded into the k projection: one rounding, no
         # separate pass (the attention backward's dk is w.r.t. the unscaled k either way)
         # (the probe reads shape, dtype and device only: a stride-0 view shaped like k)
         k_like = qv[..., :wk.shape[0]] if Hg is None else qv[..., :1].expand(B, R, wk.shape[0])
         pre = xk.shape[-1] == wk.shape[1] and prescale_wanted(k_like, qv, H, Hg)
-        k = proj(xk, wk, bk, alpha=scale * _LOG2E if pre else 1.0)
-        if tab is not None:  # the pre-scale sits in the projection: a rotation commutes with a scalar
-            rope_apply(k, H, *tab, out=k)
+        if wkn is not None:
+            # RMSNorm cancels a scalar: the projection runs unscaled and the norm pass carries the
+            # pre-scale (and the rotation)
+            k = proj(xk, wk, bk)
+            _, rstd_k, k0 = head_rms_norm_apply(k, H, wkn, norm_eps, *(tab or (None, None)),
+                                                alpha=scale * _LOG2E if pre else 1.0, out=k, save=keep)
+            if keep:
+                nsaved = (k0, rstd_k, wkn, q0, rstd_q, wqn)
+        else:
+            k = proj(xk, wk, bk, alpha=scale * _LOG2E if pre else 1.0)
+            if tab is not None:  # the pre-scale sits in the projection: a rotation commutes with a scalar
+                rope_apply(k, H, *tab, out=k)
         actx = _Ctx()
         actx.needs_input_grad = (any(ctx.needs_input_grad),) * 2  # a backward can run (score buffers)
         o = SeqParallelAttention.forward(actx, k, qv, mask, H, scale, comm, pending, pre, grad_on, Hg,  # k_prescaled
@@ -126,13 +148,15 @@ class AttnBlockFn(torch.autograd.Function):
         # the attention's tensors go through save_for_backward too (version checks, and a graph
         # retained for a second backward keeps them)
         asaved, actx._saved = actx._saved, None
-        ctx.save_for_backward(xk, xqv, wk, wqv, wc, o, *asaved)
+        ctx.nnorm = len(nsaved)
+        ctx.save_for_backward(xk, xqv, wk, wqv, wc, o, *nsaved, *asaved)
         return out
 
     @staticmethod
     @_ext.pinned
     def backward(ctx, dout):
         xk, xqv, wk, wqv, wc, o, *asaved = ctx.saved_tensors
+        nsaved, asaved = asaved[:ctx.nnorm], asaved[ctx.nnorm:]
         ctx.actx._saved = tuple(asaved)
         ng = ctx.needs_input_grad
         hk, hq, hc = ctx.has_b
@@ -164,7 +188,25 @@ class AttnBlockFn(torch.autograd.Function):
             sync.deliver([(wc_, dwc), (bc_, dbc)], stream=side)
             dwc = dbc = None
         dk, dqv = SeqParallelAttention.backward(ctx.actx, do)[:2]
-        if ctx.rope_tab is not None:
+        dwkn = dwqn = None
+        if nsaved:
+            # QK-norm: gradients w.r.t. the normalised, rotated k / q -> w.r.t. the projections'
+            # outputs, in place, the inverse rotation folded in; on the streams the inverse rotation
+            # alone runs on (below).  The gain gradients are ordered sums (csrc/headnorm.hip)
+            k0, rstd_k, wkn, q0, rstd_q, wqn = nsaved
+            tab = ctx.rope_tab or (None, None)
+            _, dwkn = head_rms_norm_backward(dk, k0, rstd_k, ctx.H, wkn, *tab, out=dk, need_dw=ng[20])
+            dq, on = dqv[..., :ctx.nq], getattr(dqv, "_xdot_ready_on", None)
+            if on is None:
+                _, dwqn = head_rms_norm_backward(dq, q0, rstd_q, ctx.Hg, wqn, *tab, out=dq, need_dw=ng[21])
+            else:
+                here = torch.cuda.current_stream(dqv.device)
+                with _on_stream(on, here):
+                    _, dwqn = head_rms_norm_backward(dq, q0, rstd_q, ctx.Hg, wqn, *tab, out=dq, need_dw=ng[21])
+                here.wait_stream(on)
+                if dwqn is not None:
+                    dwqn.record_stream(here)
+        elif ctx.rope_tab is not None:
             # gradients w.r.t. the rotated k / q -> w.r.t. the projections' outputs: the inverse
             # rotation, in place, before anything below reads them.  d[q|v] may be handed on with
             # ``_xdot_ready_on`` (its weight gradient then runs on that stream without waiting for
@@ -221,5 +263,6 @@ class AttnBlockFn(torch.autograd.Function):
         # the attention's tensors were only borrowed from ctx.saved_tensors (rebuilt from there by
         # every backward): do not keep them alive through the node after this backward
         ctx.actx._saved = None
-        return (dxk, dxqv, None, dwk, dbk, dwq, dbq, dwv, dbv, dwc, dbc, None, None, None, None, None, None, None, None,
-                None)
+        grads = (dxk, dxqv, None, dwk, dbk, dwq, dbq, dwv, dbv, dwc, dbc, None, None, None, None, None, None, None, None,
+                 None)
+        return grads + (dwkn, dwqn, None) if len(ng) > len(grads) else grads

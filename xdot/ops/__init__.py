@@ -7,3 +7,4 @@ from .optim import FusedAdamW  # noqa: F401
 from .loss import mse_loss, MSELoss  # noqa: F401
 from .mask import StructuredMask  # noqa: F401
 from .rope import Rotary, rope  # noqa: F401
+from .headnorm import HeadRMSNorm, head_rms_norm  # noqa: F401
