@@ -453,6 +453,8 @@ TORCH_LIBRARY(xdot, m) {
         "bool save) -> (Tensor, Tensor)");
   m.def("headnorm_bwd(Tensor g, Tensor x, Tensor rstd, Tensor weight, Tensor? cos, Tensor? sin, int H, float alpha, "
         "Tensor(a!) dx, bool need_dw) -> Tensor");
+  m.def("sink_fold(Tensor(a!) out, Tensor(b!) lse, Tensor sinks, int H) -> ()");
+  m.def("sink_grad(Tensor delta, Tensor lse, Tensor sinks) -> Tensor");
   m.def("mse_fwd(Tensor y, Tensor t) -> (Tensor, Tensor)");
   m.def("proj(Tensor x, Tensor w, Tensor? bias, bool nn, Tensor(a!)? out=None, int force=0, float alpha=1.0) -> Tensor");
   m.def("wgrad(Tensor dy, Tensor x, ScalarType out_dtype, int splits=0) -> Tensor");

@@ -632,6 +632,78 @@ at::Tensor headnorm_bwd(const at::Tensor& g, const at::Tensor& x, const at::Tens
   return dw;
 }
 
+// ---- attention sinks (csrc/sink.hip) ----
+// sinks (H,): fp32, bf16 or fp16 on the launch's device (an fp32 master parameter beside 16-bit tensors)
+void sink_param(const at::Tensor& sinks, int64_t H, const at::Device& dev, const char* op) {
+  TORCH_CHECK(sinks.is_cuda() && sinks.device() == dev && sinks.dim() == 1 && sinks.size(0) == H && sinks.is_contiguous() &&
+                  (sinks.scalar_type() == at::kFloat || sinks.scalar_type() == at::kBFloat16 ||
+                   sinks.scalar_type() == at::kHalf),
+              "xdot.", op, ": sinks must be a contiguous (H,) = (", H, ",) fp32 / bf16 / fp16 tensor on the same GPU");
+}
+
+// the fold of one sink logit per head into a finished forward, in place: lse' = logaddexp(lse, s_h),
+// out' = sigmoid(lse - s_h) * out.  out: (B, R, H*D) with unit inner stride and 16-byte aligned
+// rows (row / batch strides allowed), lse: contiguous fp32 (B, H, R)
+void sink_fold(at::Tensor& out, at::Tensor& lse, const at::Tensor& sinks, int64_t H) {
+  Range rr_("xdot.sink_fold");
+  TORCH_CHECK(out.is_cuda() && out.dim() == 3, "xdot.sink_fold: out must be a (B, R, H*D) GPU tensor");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kHalf || out.scalar_type() == at::kFloat,
+              "xdot.sink_fold: bf16/fp16/fp32 only");
+  const int64_t B = out.size(0), R = out.size(1), C = out.size(2);
+  TORCH_CHECK(H > 0 && C > 0 && C % H == 0, "xdot.sink_fold: H*D features, got C=", C, " H=", H);
+  const int64_t D = C / H;
+  TORCH_CHECK(D >= 32 && D <= 384 && D % 8 == 0,
+              "xdot.sink_fold: the head dim must be one the flash paths produce (32..384 in steps of 8), got ", D);
+  TORCH_CHECK(B < (1LL << 31) && R < (1LL << 31) && C < (1LL << 31), "xdot.sink_fold: too large");
+  sink_param(sinks, H, out.device(), "sink_fold");
+  TORCH_CHECK(lse.dim() == 3 && lse.size(0) == B && lse.size(1) == H && lse.size(2) == R,
+              "xdot.sink_fold: lse must be (B, H, R) = (", B, ", ", H, ", ", R, ")");
+  check_bhr(lse, B, H, R, out.device(), "xdot.sink_fold: lse must be a contiguous fp32 tensor on the same GPU");
+  if (out.numel() == 0) return;
+  const int64_t V = 16 / (int64_t)out.element_size();
+  TORCH_CHECK(out.stride(2) == 1, "xdot.sink_fold: the last dimension must have stride 1");
+  const int64_t sb = B > 1 ? out.stride(0) : 0, sr = R > 1 ? out.stride(1) : 0;
+  TORCH_CHECK(sb >= 0 && sr >= 0, "xdot.sink_fold: negative strides");
+  // (every (b, row) is written: two of them may not share memory)
+  TORCH_CHECK((R == 1 || sr >= C) && (B == 1 || sb >= (R - 1) * sr + C), "xdot.sink_fold: the rows of out overlap");
+  TORCH_CHECK((B - 1) * sb + (R - 1) * sr + C <= avail_elems(out), "xdot.sink_fold: view out of bounds");
+  TORCH_CHECK(aligned16(out.data_ptr()) && sb % V == 0 && sr % V == 0,
+              "xdot.sink_fold: out and its row / batch strides must be 16-byte aligned");
+  xdot::SinkArgs a{};
+  a.out = out.data_ptr(); a.lse = lse.data_ptr<float>(); a.sinks = sinks.data_ptr();
+  a.s_dt = dt_code(sinks.scalar_type());
+  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D;
+  a.os_b = sb; a.os_r = sr;
+  c10::DeviceGuard guard(out.device());
+  launched(xdot_sink_fold_launch(&a, dt_code(out.scalar_type()), cur_stream(out)), "sink_fold", "shape");
+}
+
+// ds (H,) fp32 = -sum_{b, r} exp(s_h - lse'[b, h, r]) * delta[b, h, r] from the folded lse' and the
+// delta of the folded output: per-workgroup partials, then their ordered sum (two launches, no atomics)
+at::Tensor sink_grad(const at::Tensor& delta, const at::Tensor& lse, const at::Tensor& sinks) {
+  Range rr_("xdot.sink_grad");
+  TORCH_CHECK(lse.is_cuda() && lse.dim() == 3 && delta.dim() == 3 && delta.sizes() == lse.sizes(),
+              "xdot.sink_grad: delta and lse must be (B, H, R) GPU tensors");
+  const int64_t B = lse.size(0), H = lse.size(1), R = lse.size(2);
+  TORCH_CHECK(H > 0 && H <= 65535 && B < (1LL << 31) && R < (1LL << 31), "xdot.sink_grad: shape");
+  check_bhr(lse, B, H, R, lse.device(), "xdot.sink_grad: lse must be contiguous fp32");
+  check_bhr(delta, B, H, R, lse.device(), "xdot.sink_grad: delta must be contiguous fp32 on the same GPU");
+  sink_param(sinks, H, lse.device(), "sink_grad");
+  auto ds = at::empty({H}, lse.options());
+  if (B * R == 0) return ds.zero_();
+  const int nparts = xdot_sink_grad_parts((int)B, (int)R);
+  TORCH_CHECK(nparts > 0, "xdot.sink_grad: too large");
+  auto part = at::empty({H, (int64_t)nparts}, lse.options());
+  xdot::SinkGradArgs a{};
+  a.delta = delta.data_ptr<float>(); a.lse = lse.data_ptr<float>(); a.sinks = sinks.data_ptr();
+  a.part = part.data_ptr<float>(); a.ds = ds.data_ptr<float>();
+  a.s_dt = dt_code(sinks.scalar_type());
+  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.nparts = nparts;
+  c10::DeviceGuard guard(lse.device());
+  launched(xdot_sink_grad_launch(&a, cur_stream(lse)), "sink_grad", "shape");
+  return ds;
+}
+
 // δ = rowsum(dO ⊙ O) per (b, h, row), fp32 (B, H, R)
 at::Tensor flash_bwd_delta(const at::Tensor& dout, const at::Tensor& out, int64_t H) {
   Range rr_("xdot.flash_bwd_delta");
@@ -793,6 +865,8 @@ TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("rope_apply", &rope_apply);
   m.impl("headnorm_fwd", &headnorm_fwd);
   m.impl("headnorm_bwd", &headnorm_bwd);
+  m.impl("sink_fold", &sink_fold);
+  m.impl("sink_grad", &sink_grad);
   m.impl("flash_fwd_partial", &flash_fwd_partial);
   m.impl("flash_fwd_combine", &flash_fwd_combine);
   m.impl("flash_fwd_merge", &flash_fwd_merge);

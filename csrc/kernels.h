@@ -219,6 +219,28 @@ struct HeadNormPlan {
   int fwd_gx, fwd_gy;
   int bwd_gx, bwd_gy;
 };
+// attention sink (csrc/sink.hip): one logit per head joins the softmax denominator after the flash
+// forward.  Fold, in place: lse' = logaddexp(lse, s_h), out' = sigmoid(lse - s_h) * out (a row with
+// lse = -inf: out' = 0, lse' = s_h; s_h = -inf: nothing is written)
+struct SinkArgs {
+  void* out;               // (B, R, H*D), unit inner stride, 16-byte aligned rows
+  float* lse;              // (B, H, R) fp32 natural log, contiguous
+  const void* sinks;       // (H,) of dtype s_dt, read as fp32
+  int s_dt;
+  int B, R, H, D;
+  int64_t os_b, os_r;      // out strides in elements
+};
+// ds_h = -sum_{b, r} exp(s_h - lse'[b, h, r]) * delta[b, h, r]: nparts partial sums per head in a
+// fixed order, then their ordered sum
+struct SinkGradArgs {
+  const float* delta;      // (B, H, R) fp32, contiguous
+  const float* lse;        // (B, H, R) fp32: the folded lse'
+  const void* sinks;       // (H,) of dtype s_dt
+  float* part;             // (H, nparts) fp32
+  float* ds;               // (H,) fp32
+  int s_dt;
+  int B, R, H, nparts;
+};
 namespace ipc {
 constexpr int MAXR = 8;     // ranks of one node
 constexpr int MAXG = 256;   // workgroups (byte ranges) per collective
@@ -318,6 +340,12 @@ int xdot_headnorm_fwd_launch(const xdot::HeadNormArgs* a, int dt, int vec, hipSt
 int xdot_headnorm_bwd_launch(const xdot::HeadNormArgs* a, int dt, int vec, hipStream_t st);
 // dw (D elements of dtype dto) = the nparts rows of part summed in a fixed order
 int xdot_headnorm_dw_launch(const float* part, void* dw, int nparts, int D, int dto, hipStream_t st);
+// attention sink (csrc/sink.hip).  fold: in place on a->out / a->lse; -1: a head dim that is no
+// multiple of the 16-byte vector, or a grid past 2^31.  grad: partials per head a 1024-element chunk
+// of (B, R) each (xdot_sink_grad_parts), then one ordered sum per head: two launches
+int xdot_sink_fold_launch(const xdot::SinkArgs* a, int dt, hipStream_t st);
+int xdot_sink_grad_parts(int B, int R);
+int xdot_sink_grad_launch(const xdot::SinkGradArgs* a, hipStream_t st);
 // rows per workgroup of the forward kernel (128)
 int xdot_flash_fwd_rows_per_wg();
 // one AdamW step over a->nt tensors of dtype dt (params/grads), fp32 moments

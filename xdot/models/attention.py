@@ -68,6 +68,17 @@ Keyword-only knobs (each mirrors an environment flag, the argument
                 -> norm -> rope -> attention, on every path; ``v`` is untouched.  On the GPU the norm
                 and the rotation are ONE pass (:mod:`xdot.ops.headnorm`).  ``False`` (default): no
                 submodules, no launch; ``qk_norm_eps`` is the ``eps`` under the square root.
+``sinks``       ``True``: attention sinks, one learnable logit per ROW head (``self.sinks``, a
+                ``(num_heads,)`` parameter, one more ``state_dict`` key; grouped heads do not change
+                it) that takes part in the softmax denominator and contributes no value:
+                ``P = softmax([S, s_h])[..., :T]``.  The logit is appended after mask and scale -- it
+                is NOT multiplied by ``1/sqrt(d)`` -- and starts at zero: "one extra key of score 0".
+                A row whose columns are all masked then gives 0 instead of NaN, on every path.  The
+                flash and ring kernels are untouched: one fold pass over the finished ``(o, lse)``
+                and one small ordered sum in the backward (``csrc/sink.hip``; a 16-bit output is
+                rounded once by the kernel and once by the fold).  The parameter is replicated: each
+                rank's gradient is the partial over its rows, which ``GradSync`` sums.  ``False``
+                (default): no parameter, no launch, the same result bit for bit.
 """
 from __future__ import annotations
 
@@ -144,7 +155,7 @@ class DistributedDotProductAttn(nn.Module):
                  backend: str = "auto", dtype: Optional[torch.dtype] = None, chunk_plan: Optional[int] = None,
                  comm: Optional[_comm.Communicator] = None, rope: Optional[Rotary] = None,
                  num_gathered_heads: Optional[int] = None, layout: str = "contiguous", qk_norm: bool = False,
-                 qk_norm_eps: float = 1e-6):
+                 qk_norm_eps: float = 1e-6, sinks: bool = False):
         super().__init__()
         check_layout(layout)
         if fused is not None:
@@ -199,6 +210,10 @@ class DistributedDotProductAttn(nn.Module):
         if self.qk_norm:  # (no submodule without it: reference checkpoints keep loading)
             self.keys_norm = HeadRMSNorm(self.dim, self.qk_norm_eps)
             self.queries_norm = HeadRMSNorm(self.dim, self.qk_norm_eps)
+        if sinks:  # (no parameter without it: reference checkpoints keep loading)
+            self.sinks = nn.Parameter(torch.zeros(num_heads))
+        else:
+            self.register_parameter("sinks", None)
         # weakref to an attached xdot.parallel.GradSync (set by it): the fused node hands it the
         # parameter gradients as they are computed (early all-reduce)
         self._xdot_grad_sync = None
@@ -255,7 +270,8 @@ class DistributedDotProductAttn(nn.Module):
                 # (the Hg gathered heads and the H row heads are padded separately)
                 qv = torch.cat([pa.pad_heads(q, Hg, dk, Dp), pa.pad_heads(qv[..., Hg * dk:], Hg, dv, Dp)], dim=-1)
                 k = pa.pad_heads(k, H, dk, Dp)
-                o = seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm, gathered_heads=gh, layout=lay)
+                o = seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm, gathered_heads=gh, layout=lay,
+                                                  sinks=self.sinks)
                 return self._proj(self.composition, pa.unpad_heads(o, H, dv, Dp))
             if isinstance(attn_mask, Tensor) and attn_mask.is_cuda and attn_mask.dim() == 3 and FLAGS.mask_async \
                     and (lay == "contiguous" or comm.world_size == 1):
@@ -286,7 +302,8 @@ class DistributedDotProductAttn(nn.Module):
                                          self.composition.weight, self.composition.bias, self.num_heads, scale, comm,
                                          self.chunk_plan, sync, torch.is_grad_enabled(), self.rope, gh, lay,
                                          *((self.keys_norm.weight, self.queries_norm.weight, self.qk_norm_eps)
-                                           if self.qk_norm else ()))
+                                           if self.qk_norm else ((None, None, 1e-6) if self.sinks is not None else ())),
+                                         *((self.sinks,) if self.sinks is not None else ()))
             # gathered side first: its all-gather runs while the row-side GEMM computes
             qv = self._project_qv(queries, values)
             pre = False
@@ -308,7 +325,7 @@ class DistributedDotProductAttn(nn.Module):
                 else:
                     k = rope_packed(k, H * dk, H, self.rope, off, alpha=al, bwd_alpha=1.0)
             o = seq_parallel_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm, pending=pending,
-                                              k_prescaled=pre, gathered_heads=gh, layout=lay)
+                                              k_prescaled=pre, gathered_heads=gh, layout=lay, sinks=self.sinks)
             return self._proj(self.composition, o)
         if self._pick_impl(keys) == "ring":
             from ..parallel.ring import ring_attention_packed
@@ -326,7 +343,7 @@ class DistributedDotProductAttn(nn.Module):
                 k = rope_packed(k, k.shape[-1], self.num_heads, self.rope, off)
             o = ring_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm,
                                       gathered_heads=None if self.num_gathered_heads == self.num_heads
-                                      else self.num_gathered_heads, layout=lay)
+                                      else self.num_gathered_heads, layout=lay, sinks=self.sinks)
             return self._proj(self.composition, o)
         k = self._proj(self.keys, keys)
         q = self._proj(self.queries, queries)
@@ -390,7 +407,10 @@ class DistributedDotProductAttn(nn.Module):
 
             attn_mask = resolve_mask(attn_mask, B, R, s.shape[-1], comm.rank if self.distributed else 0, False,
                                      s.device, self.layout if self.distributed else "contiguous")
-        p = scale_mask_softmax(s, attn_mask, scale)
+        if self.sinks is not None:
+            p = self._sink_softmax(s, attn_mask, scale)
+        else:
+            p = scale_mask_softmax(s, attn_mask, scale)
         if self.distributed:
             o = FullMultiplication.apply(p, v, self.offset, comm)
         else:
@@ -399,6 +419,18 @@ class DistributedDotProductAttn(nn.Module):
             o = o.transpose(1, 2).reshape(B, R, self.value_dim)
         return o
 
+    def _sink_softmax(self, s: Tensor, mask: Optional[Tensor], scale: float) -> Tensor:
+        """``softmax([s * scale (masked), sinks])[..., :T]`` in torch (the reference-structured path):
+        the row log-sum-exp of the masked, scaled scores joined with the unscaled sink logit, and the
+        probabilities taken against it -- ``exp(-inf - lse')`` is 0, so a fully masked row gives 0."""
+        x = s.float() * scale if s.dtype != torch.float64 else s * scale
+        if mask is not None:
+            x = x.masked_fill(mask.unsqueeze(1) if x.dim() == 4 else mask, -float("inf"))
+        sk = self.sinks.to(x.dtype)
+        sk = sk.view(1, -1, 1) if x.dim() == 4 else sk.view(1, 1)
+        lse = torch.logaddexp(torch.logsumexp(x, dim=-1), sk)
+        return torch.exp(x - lse.unsqueeze(-1)).to(s.dtype)
+
     def extra_repr(self) -> str:
         return (f"heads={self.num_heads}, head_dim={self.dim}, value_dim={self.value_dim}, "
                 f"offset={self.offset}, distributed={self.distributed}, impl={self.impl}, backend={self.backend}, "
@@ -406,4 +438,5 @@ class DistributedDotProductAttn(nn.Module):
                 + (f", rope={self.rope!r}" if self.rope is not None else "")
                 + (f", num_gathered_heads={self.num_gathered_heads}" if self.num_gathered_heads != self.num_heads else "")
                 + (f", layout={self.layout}" if self.layout != "contiguous" else "")
-                + (f", qk_norm=True, qk_norm_eps={self.qk_norm_eps:g}" if self.qk_norm else ""))
+                + (f", qk_norm=True, qk_norm_eps={self.qk_norm_eps:g}" if self.qk_norm else "")
+                + (", sinks=True" if self.sinks is not None else ""))

@@ -25,6 +25,8 @@ With QK-norm (``norm``: the two gains and ``eps``) the same two spots run the no
 as one pass (``csrc/headnorm.hip``): the forward's passes also leave ``rstd`` and a bit copy of the
 pre-norm ``k`` / ``q`` (both are overwritten in place), the backward's passes run in place on ``dk``
 and the ``q`` part of ``d[q|v]`` and return the two gain gradients.
+With attention sinks (``sinks``: the (H,) logits) the attention folds them into its finished forward
+and its backward hands back their gradient, which goes to ``GradSync`` like every replicated parameter's.
 """
 from __future__ import annotations
 
@@ -83,10 +85,11 @@ class AttnBlockFn(torch.autograd.Function):
     @staticmethod
     @_ext.pinned
     def forward(ctx, xk, xqv, mask, wk, bk, wq, bq, wv, bv, wc, bc, H, scale, comm, chunk_plan, sync=None,
-                grad_on=True, rope=None, Hg=None, layout="contiguous", wkn=None, wqn=None, norm_eps=1e-6):
+                grad_on=True, rope=None, Hg=None, layout="contiguous", wkn=None, wqn=None, norm_eps=1e-6, sinks=None):
         # Hg: gathered heads when fewer than H (grouped-query attention): wq / wv hold Hg heads
         # layout: the row sharding (xdot.parallel.layout): the rotary positions and the mask follow it
         # wkn / wqn: the (D,) gains of QK-norm on k / q (both or neither), norm_eps its eps
+        # sinks: the (H,) attention-sink logits (a replicated parameter) or None
         wqv = _rows(wq, wv)
         bqv = _rows(bq, bv) if bq is not None else None
         n = comm.world_size
@@ -137,11 +140,12 @@ class AttnBlockFn(torch.autograd.Function):
         actx = _Ctx()
         actx.needs_input_grad = (any(ctx.needs_input_grad),) * 2  # a backward can run (score buffers)
         o = SeqParallelAttention.forward(actx, k, qv, mask, H, scale, comm, pending, pre, grad_on, Hg,  # k_prescaled
-                                         layout)
+                                         layout, sinks)
         out = proj(o, wc, bc)
         ctx.actx = actx
         ctx.sync = sync  # (GradSync, module key) or None
         ctx.params = (wk, bk, wq, bq, wv, bv, wc, bc)
+        ctx.sinks = sinks
         ctx.nq = nq
         ctx.rope_tab, ctx.H, ctx.Hg = tab, H, Hg or H
         ctx.has_b = (bk is not None, bq is not None, bc is not None)
@@ -187,7 +191,13 @@ class AttnBlockFn(torch.autograd.Function):
             # all-reduce runs under the attention backward (stream None: the current one)
             sync.deliver([(wc_, dwc), (bc_, dbc)], stream=side)
             dwc = dbc = None
-        dk, dqv = SeqParallelAttention.backward(ctx.actx, do)[:2]
+        agrads = SeqParallelAttention.backward(ctx.actx, do)
+        dk, dqv, dsk = agrads[0], agrads[1], agrads[-1]  # (dsk: this rank's rows' share of the sinks' gradient)
+        if dsk is not None and not ng[23]:
+            dsk = None
+        if dsk is not None and sync is not None:  # a replicated parameter like the others: summed by GradSync
+            sync.deliver([(ctx.sinks, dsk)])
+            dsk = None
         dwkn = dwqn = None
         if nsaved:
             # QK-norm: gradients w.r.t. the normalised, rotated k / q -> w.r.t. the projections'
@@ -265,4 +275,4 @@ class AttnBlockFn(torch.autograd.Function):
         ctx.actx._saved = None
         grads = (dxk, dxqv, None, dwk, dbk, dwq, dbq, dwv, dbv, dwc, dbc, None, None, None, None, None, None, None, None,
                  None)
-        return grads + (dwkn, dwqn, None) if len(ng) > len(grads) else grads
+        return (grads + (dwkn, dwqn, None, dsk))[:len(ng)]

@@ -436,6 +436,30 @@ def bwd(dout: torch.Tensor, rows: torch.Tensor, kc: torch.Tensor, vc: torch.Tens
     return drows, dkv[..., :Cg], dkv[..., Cg:]
 
 
+# ---- attention sinks (csrc/sink.hip) -------------------------------------------------------------
+def _sinks(sinks: torch.Tensor) -> torch.Tensor:
+    """The logits as the kernels read them: contiguous fp32 / bf16 / fp16 (anything else -> fp32)."""
+    s = sinks.detach()
+    if s.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        s = s.float()
+    return s.contiguous()
+
+
+def sink_fold(out: torch.Tensor, lse: torch.Tensor, sinks: torch.Tensor, H: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Fold one sink logit per head (``sinks`` (H,), fp32 / bf16 / fp16, not scaled by ``1/sqrt(d)``)
+    into a finished forward, IN PLACE -> the same ``(out, lse)``: ``lse' = logaddexp(lse, s_h)``,
+    ``out' = sigmoid(lse - s_h) * out``.  A fully masked row (``lse = -inf``, NaN in ``out``) comes
+    out 0 with ``lse' = s_h``; ``s_h = -inf`` leaves the head as it is, bit for bit.  One launch."""
+    _ext.ops().sink_fold(out, lse, _sinks(sinks), int(H))
+    return out, lse
+
+
+def sink_grad(delta: torch.Tensor, lse: torch.Tensor, sinks: torch.Tensor) -> torch.Tensor:
+    """``ds`` (H,) fp32 ``= -sum_{b,r} exp(s_h - lse') * delta`` from the folded ``lse'`` and the δ of
+    the folded output (both fp32 (B, H, R)): an ordered sum, bitwise reproducible.  Two launches."""
+    return _ext.ops().sink_grad(delta.contiguous(), lse.contiguous(), _sinks(sinks))
+
+
 # ---- launches into partial slots (gather chunks, ring blocks) ------------------------------------
 def splits(B: int, R: int, T: int, H: int, rows_kernel: bool = False) -> int:
     """Partial slots one :func:`fwd_partial` (``rows_kernel``: :func:`bwd_rows_partial`) launch over

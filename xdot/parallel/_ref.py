@@ -73,6 +73,29 @@ def combine(parts, dtype):
     return o.to(dtype), lse
 
 
+def sink_fold(o, lse, sinks, H: int):
+    """One sink logit per head (``sinks`` (H,), not scaled) folded into a finished forward ->
+    (o' in o's dtype, lse'): ``lse' = logaddexp(lse, s_h)``, ``o' = exp(lse - lse') * o``; a fully
+    masked row (``lse = -inf``, NaN in ``o``) gives 0 and ``lse' = s_h``.  ``s_h = -inf`` is the
+    identity (a fully masked row stays NaN / -inf)."""
+    cdt = lse.dtype
+    s = sinks.detach().to(cdt).view(1, H, 1)
+    new = torch.logaddexp(lse, s)
+    g = torch.where(s > -float("inf"), torch.exp(lse - new), torch.ones_like(new))  # -inf - -inf: weight 1
+    oh = heads(o, H, cdt)
+    dead = ((lse == -float("inf")) & (s > -float("inf"))).unsqueeze(-1)
+    oh = torch.where(dead, torch.zeros_like(oh), oh * g.unsqueeze(-1))  # selected, not multiplied: o is NaN there
+    return _merge(oh).to(o.dtype), new
+
+
+def sink_grad(delta, lse, sinks):
+    """``ds`` (H,) ``= -sum_{b,r} exp(s_h - lse') * delta`` from the folded ``lse'`` and the δ of the
+    folded output, compute dtype; 0 for ``s_h = -inf``."""
+    s = sinks.detach().to(lse.dtype).view(1, -1, 1)
+    w = torch.where(s > -float("inf"), torch.exp(s - lse), torch.zeros_like(lse))
+    return -torch.where(w == 0, torch.zeros_like(delta), w * delta).sum(dim=(0, 2))
+
+
 def block_bwd(do, k, kc, vc, lse, delta, mask, H: int, scale: float, Hg=None):
     """Gradients of one column segment given the whole row's ``lse`` and ``delta`` (B, H, R) ->
     (dk (B, R, H*dh), dq (B, T, Hg*dh), dv (B, T, Hg*dv)), compute dtype; dq / dv summed over each

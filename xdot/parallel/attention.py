@@ -23,7 +23,20 @@ backward (recompute, no stored probabilities)
 
 The gathered q/v are reused from forward (saved, T x (dh+dv) per head: 77 MB bf16 at
 T=25000) instead of the reference's second round of gathers.  A fully masked row yields NaN
-like the reference.  CPU tensors (and GPU dtypes the kernels do not take) run the same
+like the reference.
+
+attention sinks (``sinks``: one logit ``s_h`` per row head that joins the softmax denominator and
+carries no value; appended after mask and scale, so NOT multiplied by ``scale``; zeros are "one extra
+key of score 0")
+  need no change to any kernel: every forward branch ends in a normalised ``o`` and a natural-log
+  ``lse``, and the sink is the fold ``lse' = logaddexp(lse, s_h)``, ``o' = exp(lse - lse') o``
+  (``csrc/sink.hip``, once, after whichever branch ran; the folded pair is what is saved).  Steps
+  3-5 on ``(o', lse')`` give dk, dq, dv exactly, and ``ds_h = -sum exp(s_h - lse') δ`` is a small
+  ordered sum over the δ of step 3.  With sinks a fully masked row gives 0, not NaN; without
+  (``sinks=None``) nothing is launched and the result is bit for bit what it was.  On 16-bit tensors
+  the one-launch forward's output is rounded twice (by the kernel, by the fold).
+
+CPU tensors (and GPU dtypes the kernels do not take) run the same
 schedule with a torch reference implementation of steps 2-5.
 """
 from __future__ import annotations
@@ -111,6 +124,21 @@ def gathered_heads_arg(H: int, gathered_heads: Optional[int]) -> Optional[int]:
     if Hg < 1 or H % Hg:
         raise ValueError(f"num_heads {H} must be a multiple of gathered_heads {gathered_heads}")
     return Hg
+
+
+def sinks_arg(sinks, H: int, like: Tensor):
+    """The ``sinks`` argument validated -> None or a float ``(H,)`` tensor on ``like``'s device: one
+    logit per ROW head (grouped-query attention does not change it)."""
+    if sinks is None:
+        return None
+    if not isinstance(sinks, Tensor) or not sinks.is_floating_point():
+        raise TypeError(f"sinks must be a floating-point tensor of one logit per head or None, got "
+                        f"{sinks.dtype if isinstance(sinks, Tensor) else type(sinks).__name__}")
+    if sinks.dim() != 1 or sinks.shape[0] != H:
+        raise ValueError(f"sinks must be (num_heads,) = ({H},), got {tuple(sinks.shape)}")
+    if sinks.device != like.device:
+        raise ValueError(f"sinks must be on the tensors' device {like.device}, got {sinks.device}")
+    return sinks
 
 
 def _native_gqa(k: Tensor, H: int) -> bool:
@@ -285,11 +313,12 @@ def _segmented_forward_torch(k, qv, mask, H, scale, pending, n, rank, Hg=None):
     return o, lse, [torch.cat(gs, dim=2) if len(gs) > 1 else gs[0]]
 
 
-def _backward_torch(ctx, do, k, o, lse, qvg):
-    """-> (dk, d[q|v] of this rank's rows) from the rank-major gathered ``qvg`` (N, B, R, Cq + Cv)."""
+def _backward_torch(ctx, do, k, o, lse, qvg, sinks=None):
+    """-> (dk, d[q|v] of this rank's rows, ds or None) from the rank-major gathered ``qvg`` (N, B, R, Cq + Cv)."""
     C = _q_width(k, ctx.H, ctx.Hg)
     n, B, Rg = qvg.shape[:3]
     delta = _ref.delta(do, o, ctx.H, lse.dtype)
+    ds = None if sinks is None else _ref.sink_grad(delta, lse, sinks)
     dk, dq, dv = _ref.block_bwd(do, k, _as_global(qvg[..., :C]), _as_global(qvg[..., C:]), lse, delta, ctx.mask,
                                 ctx.H, ctx.scale, ctx.Hg)
     parts = torch.cat([dq, dv], dim=-1).view(B, n, Rg, -1).permute(1, 0, 2, 3).contiguous()  # rank-major
@@ -298,7 +327,7 @@ def _backward_torch(ctx, do, k, o, lse, qvg):
     h, dqv = _reduce_async(ctx.comm, parts)
     if h is not None:
         h.wait()
-    return dk, dqv
+    return dk, dqv, ds
 
 
 def _reduce_async(comm, parts, out=None):
@@ -573,7 +602,7 @@ def _rows_hip(ctx, do, k, lse, delta, bufs, mks, sbuf, dsbuf, cur):
     return flash.bwd_rows_sum(dpart, H, k)
 
 
-def _backward_hip(ctx, do, k, o, lse, bufs, sbt):
+def _backward_hip(ctx, do, k, o, lse, bufs, sbt, sinks=None):
     """δ, then two independent streams: 1) gathered-side grads on a HIGH-priority stream,
     followed there by their reduce-scatter(s), and 2) the row-side dk on the current
     stream.  2) fills the partly occupied last workgroup rounds of 1) and hides the
@@ -637,6 +666,8 @@ def _backward_hip(ctx, do, k, o, lse, bufs, sbt):
     cur.wait_event(ev if ev_cols is None else ev_cols)
     delta.record_stream(cur)
     dk = _rows_hip(ctx, do, k, lse, delta, bufs, mks, sbuf, dsbuf, cur)
+    # the sink's gradient from the delta both kernels read: a small ordered sum behind the row kernel
+    ds = None if sinks is None else flash.sink_grad(delta, lse, sinks)
     with _on_stream(hi, cur):  # the gathered-side grads complete on the priority stream
         for h in handles:
             if h is not None:
@@ -652,7 +683,7 @@ def _backward_hip(ctx, do, k, o, lse, bufs, sbt):
     # reduce-scatter lands, under the row-side kernel still running on `cur`
     if FLAGS.wgrad_side and dqv.dtype == k.dtype:
         dqv._xdot_ready_on = hi
-    return dk, dqv
+    return dk, dqv, ds
 
 
 # ----------------------------------------------------------------------------------------
@@ -665,14 +696,16 @@ class SeqParallelAttention(torch.autograd.Function):
     @staticmethod
     @_ext.pinned
     def forward(ctx, k, qv, mask, H, scale, comm, pending=None, k_prescaled=False, grad_on=True, Hg=None,
-                layout="contiguous"):
+                layout="contiguous", sinks=None):
         """``k_prescaled``: ``k`` already holds ``rows * scale * log2 e`` (:func:`prescale_wanted`;
         the fused module folds it into the k projection's epilogue).  ``grad_on``: grad mode at the
         call (inside ``forward`` it is always off, and ``needs_input_grad`` ignores it).  ``Hg``:
         gathered heads when fewer than ``H`` (:func:`gathered_heads_arg`); ``qv`` is ``[q | v]`` with
         ``Hg`` heads each.  ``layout``: which global rows this rank's rows are
-        (:mod:`xdot.parallel.layout`); only the mask depends on it."""
-        check_consistent(comm, "seq_parallel_attention", k, qv, H, Hg or H, layout)
+        (:mod:`xdot.parallel.layout`); only the mask depends on it.  ``sinks``: (H,) attention-sink
+        logits (:func:`sinks_arg`) or None: folded once into whichever branch's ``(o, lse)``, and the
+        folded pair is what is saved."""
+        check_consistent(comm, "seq_parallel_attention", k, qv, H, Hg or H, layout, sinks is not None)
         B, R, C = k.shape
         n, rank = comm.world_size, comm.rank
         T = n * qv.shape[1]
@@ -722,11 +755,16 @@ class SeqParallelAttention(torch.autograd.Function):
             qvg = pending.wait(0)                            # (N, B, R, 2C)
             o, lse = _forward_torch(k, qvg, mask, H, scale, Hg)
             bufs, mks = [qvg], [mask]
+        if sinks is not None:
+            # the sink logit joins the finished softmax: lse' = logaddexp(lse, s_h), o' = exp(lse - lse') o.
+            # The backward kernels run unchanged on the folded pair
+            o, lse = flash.sink_fold(o, lse, sinks, H) if use_hip else _ref.sink_fold(o, lse, sinks, H)
         # the score buffers travel as saved tensors: autograd frees them after the backward unless
         # the graph is retained (a ctx attribute would keep 20-40 GB alive as long as the graph is
         # referenced, e.g. through the previous step's loss)
         sbt = tuple(t for t in (sbuf, dsbuf) if t is not None)
-        ctx.save_for_backward(k, o, lse, *bufs, *sbt)
+        ctx.save_for_backward(k, o, lse, *bufs, *sbt, *(() if sinks is None else (sinks,)))
+        ctx.has_sinks = sinks is not None
         ctx.mks, ctx.mask, ctx.chunks, ctx.H, ctx.scale, ctx.comm, ctx.use_hip = mks, mask, chunks, H, scale, comm, use_hip
         ctx.prescaled, ctx.fp32_mode = prescaled, fm
         ctx.Hg, ctx.expand = Hg, expand
@@ -738,14 +776,17 @@ class SeqParallelAttention(torch.autograd.Function):
     @_ext.pinned
     def backward(ctx, do):
         k, o, lse, *bufs = ctx.saved_tensors
+        sinks = bufs.pop() if getattr(ctx, "has_sinks", False) else None
         nsb = sum(getattr(ctx, "sb_kind", (False, False)))
         bufs, sbt = bufs[:len(bufs) - nsb], bufs[len(bufs) - nsb:]
         do = do.contiguous()
         if ctx.use_hip:
-            dk, dqv = _backward_hip(ctx, do, k, o, lse, bufs, sbt)
+            dk, dqv, ds = _backward_hip(ctx, do, k, o, lse, bufs, sbt, sinks)
         else:
-            dk, dqv = _backward_torch(ctx, do, k, o, lse, bufs[0])
-        return dk.to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None, None, None, None
+            dk, dqv, ds = _backward_torch(ctx, do, k, o, lse, bufs[0], sinks)
+        if ds is not None:
+            ds = ds.to(sinks.dtype)
+        return dk.to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None, None, None, None, ds
 
 
 def gather_plan(qv_shape, qv: Tensor, comm: _comm.Communicator, chunks: Optional[int] = None):
@@ -784,7 +825,8 @@ def _checked_mask(mask, k: Tensor, T: int):
 def seq_parallel_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
                                   comm: Optional[_comm.Communicator] = None,
                                   pending: Optional["_PendingGather"] = None, k_prescaled: bool = False, *,
-                                  gathered_heads: Optional[int] = None, layout: str = "contiguous") -> Tensor:
+                                  gathered_heads: Optional[int] = None, layout: str = "contiguous",
+                                  sinks: Optional[Tensor] = None) -> Tensor:
     """Fused sequence-parallel attention with a packed gathered side ``qv = [q | v]`` (B, R, 2C).
 
     ``gathered_heads``: heads of ``q`` and of ``v`` when fewer than ``num_heads`` (grouped-query
@@ -801,8 +843,19 @@ def seq_parallel_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor],
 
     ``pending``: the handle of :func:`start_gather` on this ``qv`` (the gather is issued here
     otherwise).  ``k_prescaled``: ``k`` already holds ``rows * scale * log2 e`` (only where
-    :func:`prescale_wanted`; the gradient returned for it is w.r.t. the unscaled rows)."""
+    :func:`prescale_wanted`; the gradient returned for it is w.r.t. the unscaled rows).
+
+    ``sinks``: attention sinks, a float ``(num_heads,)`` tensor of one logit per ROW head that takes
+    part in the softmax denominator and contributes no value (StreamingLLM / gpt-oss): row ``r`` of
+    head ``h`` is ``softmax([scores_r, s_h])[:T] @ v``.  The logit is appended after mask and scale:
+    it is NOT multiplied by ``scale``; zeros mean "one extra key of score 0".  With sinks a fully
+    masked row gives 0 instead of NaN.  It is differentiable (each rank's gradient is the partial
+    over its rows: sum it across ranks, as :class:`xdot.parallel.GradSync` does).  The kernels are
+    untouched: one fold pass after the forward (``csrc/sink.hip``; a 16-bit output is rounded once by
+    the kernel and once by the fold) and one small ordered sum in the backward.  ``None``: no launch,
+    the result of the call without the argument bit for bit.  Every rank must pass sinks or none (``XDOT_CHECK`` compares it)."""
     comm = comm or _comm.get_comm()
+    sinks = sinks_arg(sinks, num_heads, k)
     Hg = gathered_heads_arg(num_heads, gathered_heads)
     if k.dim() != 3 or qv.dim() != 3 or k.shape[-1] % num_heads or qv.shape[-1] <= _q_width(k, num_heads, Hg):
         raise ValueError("seq_parallel_attention_packed expects k (B, R, C) and qv (B, R, Cq + Cv) with "
@@ -812,12 +865,13 @@ def seq_parallel_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor],
                          f"divide into {Hg} gathered heads")
     mask = _checked_mask(mask, k, qv.shape[1] * comm.world_size)
     return SeqParallelAttention.apply(k, qv, mask, num_heads, float(scale), comm, pending, bool(k_prescaled),
-                                      torch.is_grad_enabled(), Hg, check_layout(layout))
+                                      torch.is_grad_enabled(), Hg, check_layout(layout), sinks)
 
 
 def seq_parallel_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tensor], num_heads: int,
                            scale: float, comm: Optional[_comm.Communicator] = None, rope=None, *,
-                           gathered_heads: Optional[int] = None, layout: str = "contiguous") -> Tensor:
+                           gathered_heads: Optional[int] = None, layout: str = "contiguous",
+                           sinks: Optional[Tensor] = None) -> Tensor:
     """Fused sequence-parallel attention on projected, head-interleaved (B, R, H*d) tensors
     (``q`` / ``v``: ``gathered_heads * d`` columns when given, grouped-query attention).
 
@@ -827,6 +881,7 @@ def seq_parallel_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tenso
     ``rope``: an :class:`xdot.Rotary`; ``k`` and ``q`` are rotated at this rank's global positions
     (``rank * R`` unless the object carries an offset) before the attention, ``v`` is not.
     ``layout``: the row sharding, as :func:`seq_parallel_attention_packed` (the rotation follows it).
+    ``sinks``: (H,) attention-sink logits, as :func:`seq_parallel_attention_packed`.
     Returns (B, R, H*dv) in ``k``'s dtype.
     """
     if k.dim() != 3 or q.dim() != 3 or v.dim() != 3:
@@ -839,4 +894,4 @@ def seq_parallel_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tenso
         k = _rope(k, num_heads, rope, offset=off)
         q = _rope(q, gathered_heads_arg(num_heads, gathered_heads) or num_heads, rope, offset=off)
     return seq_parallel_attention_packed(k, torch.cat([q, v], dim=-1), mask, num_heads, scale, comm,
-                                         gathered_heads=gathered_heads, layout=layout)
+                                         gathered_heads=gathered_heads, layout=layout, sinks=sinks)

@@ -49,7 +49,7 @@ from ..utils.streams import _on_stream, _side_stream
 from . import _ref
 from .layout import check_layout
 from .attention import (WIDE_F32_NEEDS_SCORES, _checked_mask, _expand_heads, _fold_heads, _hip_ok, _native_gqa,
-                        _prescale_rows, _q_width, gathered_heads_arg)
+                        _prescale_rows, _q_width, gathered_heads_arg, sinks_arg)
 
 __all__ = ["RingAttention", "ring_attention", "ring_attention_packed"]
 
@@ -228,9 +228,9 @@ def _forward_torch(k, qv, rings, mask, H, scale, n, Hg=None):
     return acc.transpose(1, 2).reshape(B, R, -1).to(k.dtype), lse, mks
 
 
-def _backward_hip(ctx, do, k, o, lse, rings):
+def _backward_hip(ctx, do, k, o, lse, rings, sinks=None):
     """-> (step(s): the launches of ring step s -> the lanes' fp32 [dq | dv] contributions,
-    dk(): the row-side gradient after the last step)"""
+    dk(): the row-side gradient after the last step, ds: the sinks' gradient or None)"""
     H, scale, n = ctx.H, ctx.scale, ctx.comm.world_size
     B, R, C = k.shape
     Hg, expand = ctx.Hg, ctx.expand
@@ -241,6 +241,7 @@ def _backward_hip(ctx, do, k, o, lse, rings):
     two = ov not in ("0", "false", "off", "no") and (ov != "auto" or -(-R // 128) * B * H >= 1024)
     hi = _side_stream(do.device) if two else cur  # XDOT_RING_OVERLAP (utils/env.py)
     delta = flash.bwd_delta(do, o, H)
+    ds = None if sinks is None else flash.sink_grad(delta, lse, sinks)
     nsr = flash.splits(B, R, rings.width, H, True)
     # slot 0: running fp32 dk, then nsr column-split partial slots per launch
     dpart = torch.empty(1 + rings.launches * nsr, B, R, C, dtype=torch.float32, device=k.device)
@@ -276,14 +277,15 @@ def _backward_hip(ctx, do, k, o, lse, rings):
             c_.record_stream(cur)
         return contribs
 
-    return step, lambda: flash.bwd_rows_sum(dpart, H, k)
+    return step, (lambda: flash.bwd_rows_sum(dpart, H, k)), ds
 
 
-def _backward_torch(ctx, do, k, o, lse, rings):
+def _backward_torch(ctx, do, k, o, lse, rings, sinks=None):
     """As :func:`_backward_hip`, in torch."""
     C = _q_width(k, ctx.H, ctx.Hg)
     cdt = lse.dtype
     delta = _ref.delta(do, o, ctx.H, cdt)
+    ds = None if sinks is None else _ref.sink_grad(delta, lse, sinks)
     dk = torch.zeros(k.shape, dtype=cdt, device=k.device)
 
     def step(s):
@@ -295,7 +297,7 @@ def _backward_torch(ctx, do, k, o, lse, rings):
             contribs.append(torch.cat([dq, dv], dim=-1))
         return contribs
 
-    return step, lambda: dk
+    return step, (lambda: dk), ds
 
 
 class RingAttention(torch.autograd.Function):
@@ -303,8 +305,8 @@ class RingAttention(torch.autograd.Function):
 
     @staticmethod
     @_ext.pinned
-    def forward(ctx, k, qv, mask, H, scale, comm, Hg=None, layout="contiguous"):
-        check_consistent(comm, "ring_attention", k, qv, H, Hg or H, layout)
+    def forward(ctx, k, qv, mask, H, scale, comm, Hg=None, layout="contiguous", sinks=None):
+        check_consistent(comm, "ring_attention", k, qv, H, Hg or H, layout, sinks is not None)
         B, R, C = k.shape
         n = comm.world_size
         # (the ring has no score buffer: exact fp32 heads past 256 run the torch path)
@@ -320,7 +322,9 @@ class RingAttention(torch.autograd.Function):
             o, lse, k, mks, prescaled, fm = _forward_hip(k, rings, mask, H, scale, n, Hg, expand)
         else:
             o, lse, mks = _forward_torch(k, qv, rings, mask, H, scale, n, Hg)
-        ctx.save_for_backward(k, qv, o, lse)
+        if sinks is not None:  # folded after the last combine; the folded pair is what is saved
+            o, lse = flash.sink_fold(o, lse, sinks, H) if use_hip else _ref.sink_fold(o, lse, sinks, H)
+        ctx.save_for_backward(k, qv, o, lse, *(() if sinks is None else (sinks,)))
         ctx.mks, ctx.H, ctx.scale, ctx.comm, ctx.use_hip, ctx.prescaled = mks, H, scale, comm, use_hip, prescaled
         ctx.fp32_mode, ctx.bidir = fm, len(rings.lanes) > 1
         ctx.Hg, ctx.expand = Hg, expand
@@ -329,7 +333,8 @@ class RingAttention(torch.autograd.Function):
     @staticmethod
     @_ext.pinned
     def backward(ctx, do):
-        k, qv, o, lse = ctx.saved_tensors
+        k, qv, o, lse, *rest = ctx.saved_tensors
+        sinks = rest[0] if rest else None
         comm = ctx.comm
         n = comm.world_size
         B = k.shape[0]
@@ -345,7 +350,9 @@ class RingAttention(torch.autograd.Function):
             if n > 1 else None
         acc_h = None
         accs = None
-        step, dk = (_backward_hip if ctx.use_hip else _backward_torch)(ctx, do, k, o, lse, rings)
+        step, dk, ds = (_backward_hip if ctx.use_hip else _backward_torch)(ctx, do, k, o, lse, rings, sinks)
+        if ds is not None:
+            ds = ds.to(sinks.dtype)
         for s in range(n):
             rings.start(s)
             contribs = step(s)
@@ -363,31 +370,33 @@ class RingAttention(torch.autograd.Function):
             acc_h.wait()
             accs = acc_in
         dqv = accs[0] if len(accs) == 1 else torch.cat(accs, dim=1)
-        return dk().to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None
+        return dk().to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None, ds
 
 
 def ring_attention_packed(k: Tensor, qv: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
                           comm: Optional[_comm.Communicator] = None, *, gathered_heads: Optional[int] = None,
-                          layout: str = "contiguous") -> Tensor:
+                          layout: str = "contiguous", sinks: Optional[Tensor] = None) -> Tensor:
     """Ring sequence-parallel attention with a packed gathered side ``qv = [q | v]`` (B, R, Cq + Cv);
     ``mask``: bool (B, R, T) (True = masked), a :class:`xdot.StructuredMask`, or None.  Returns (B, R, Cv) in ``k``'s dtype.
     ``gathered_heads``: heads of ``q`` / ``v`` when fewer than ``num_heads`` (grouped-query attention,
     as :func:`xdot.parallel.attention.seq_parallel_attention_packed`): the ring blocks and the
     gradient accumulators that ride the ring are that much narrower.  ``layout``: the row sharding
-    (``"contiguous"`` | ``"zigzag"``), as :func:`xdot.parallel.attention.seq_parallel_attention_packed`."""
+    (``"contiguous"`` | ``"zigzag"``), as :func:`xdot.parallel.attention.seq_parallel_attention_packed`.
+    ``sinks``: (num_heads,) attention-sink logits, as there: folded after the last block's combine."""
     comm = comm or _comm.get_comm()
     Hg = gathered_heads_arg(num_heads, gathered_heads)
     if k.dim() != 3 or qv.dim() != 3 or k.shape[-1] % num_heads or qv.shape[-1] <= _q_width(k, num_heads, Hg) \
             or qv.shape[:2] != k.shape[:2]:
         raise ValueError("ring_attention expects k (B, R, C) and qv (B, R, Cq + Cv) with equal R")
     mask = _checked_mask(mask, k, qv.shape[1] * comm.world_size)
-    return RingAttention.apply(k, qv, mask, num_heads, float(scale), comm, Hg, check_layout(layout))
+    return RingAttention.apply(k, qv, mask, num_heads, float(scale), comm, Hg, check_layout(layout),
+                               sinks_arg(sinks, num_heads, k))
 
 
 def ring_attention(k: Tensor, q: Tensor, v: Tensor, mask: Optional[Tensor], num_heads: int, scale: float,
                    comm: Optional[_comm.Communicator] = None, *, gathered_heads: Optional[int] = None,
-                   layout: str = "contiguous") -> Tensor:
+                   layout: str = "contiguous", sinks: Optional[Tensor] = None) -> Tensor:
     """:func:`ring_attention_packed` on separate head-interleaved (B, R, H*d) ``k``, ``q``, ``v``
     (``q`` / ``v``: ``gathered_heads * d`` columns when given)."""
     return ring_attention_packed(k, torch.cat([q, v], dim=-1), mask, num_heads, scale, comm,
-                                 gathered_heads=gathered_heads, layout=layout)
+                                 gathered_heads=gathered_heads, layout=layout, sinks=sinks)
