@@ -455,6 +455,8 @@ TORCH_LIBRARY(xdot, m) {
         "Tensor(a!) dx, bool need_dw) -> Tensor");
   m.def("sink_fold(Tensor(a!) out, Tensor(b!) lse, Tensor sinks, int H) -> ()");
   m.def("sink_grad(Tensor delta, Tensor lse, Tensor sinks) -> Tensor");
+  m.def("gate_apply(Tensor o, Tensor g, int H, Tensor(a!) out, int mode=-1) -> ()");
+  m.def("gate_backward(Tensor dy, Tensor o, Tensor g, int H, Tensor(a!) dout, int mode=-1) -> Tensor");
   m.def("mse_fwd(Tensor y, Tensor t) -> (Tensor, Tensor)");
   m.def("proj(Tensor x, Tensor w, Tensor? bias, bool nn, Tensor(a!)? out=None, int force=0, float alpha=1.0) -> Tensor");
   m.def("wgrad(Tensor dy, Tensor x, ScalarType out_dtype, int splits=0) -> Tensor");

@@ -704,6 +704,113 @@ at::Tensor sink_grad(const at::Tensor& delta, const at::Tensor& lse, const at::T
   return ds;
 }
 
+// ---- gated attention (csrc/gate.hip) ----
+// one (B, R, C) operand of the gate kernels: unit inner stride, non-negative row / batch strides,
+// inside its storage; -> (batch stride, row stride) in elements, 0 for a dimension of size 1
+struct GateView { int64_t sb, sr; bool vec; };
+GateView gate_view(const at::Tensor& t, int64_t B, int64_t R, int64_t C, const at::Tensor& like, bool written,
+                   const char* op, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == like.scalar_type() && t.dim() == 3 &&
+                  t.size(0) == B && t.size(1) == R && t.size(2) == C,
+              "xdot.", op, ": ", name, " must be a (", B, ", ", R, ", ", C, ") tensor of o's dtype on the same GPU");
+  if (t.numel() == 0) return {0, 0, true};
+  TORCH_CHECK(C == 1 || t.stride(2) == 1, "xdot.", op, ": the last dimension of ", name, " must have stride 1");
+  const int64_t sb = B > 1 ? t.stride(0) : 0, sr = R > 1 ? t.stride(1) : 0;
+  TORCH_CHECK(sb >= 0 && sr >= 0, "xdot.", op, ": negative strides in ", name);
+  if (written)  // (every (b, row) is written: two of them may not share memory)
+    TORCH_CHECK((R == 1 || sr >= C) && (B == 1 || sb >= (R - 1) * sr + C), "xdot.", op, ": the rows of ", name, " overlap");
+  TORCH_CHECK((B - 1) * sb + (R - 1) * sr + C <= avail_elems(t), "xdot.", op, ": view ", name, " out of bounds");
+  const int64_t V = 16 / (int64_t)t.element_size();
+  return {sb, sr, aligned16(t.data_ptr()) && sb % V == 0 && sr % V == 0};
+}
+
+// the bytes [lo, hi) a (B, R, C) view with these strides spans
+struct GateSpan { uintptr_t lo, hi; };
+GateSpan gate_span(const at::Tensor& t, const GateView& v) {
+  const uintptr_t lo = reinterpret_cast<uintptr_t>(t.data_ptr());
+  if (t.numel() == 0) return {lo, lo};
+  const int64_t n = (t.size(0) - 1) * v.sb + (t.size(1) - 1) * v.sr + t.size(2);
+  return {lo, lo + (uintptr_t)n * t.element_size()};
+}
+bool gate_disjoint(const GateSpan& a, const GateSpan& b) { return a.hi <= b.lo || b.hi <= a.lo; }
+
+// 16-byte lane steps?  mode -1: where D, the pointers and the strides allow; 0: never (one element per
+// step); 1: asked for -- the views must be aligned (checked here), D % V is left to the launcher
+int gate_vec(int64_t mode, bool aligned, int64_t D, int64_t V, const char* op) {
+  TORCH_CHECK(mode >= -1 && mode <= 1, "xdot.", op, ": mode must be -1 (auto), 0 (scalar) or 1 (vector)");
+  if (mode == 0) return 0;
+  if (mode == 1) {
+    TORCH_CHECK(aligned, "xdot.", op, ": vector mode needs 16-byte aligned views and strides");
+    return 1;
+  }
+  return aligned && D % V == 0;
+}
+
+int64_t gate_dims(const at::Tensor& o, const at::Tensor& g, int64_t H, const char* op, bool& headwise) {
+  TORCH_CHECK(o.is_cuda() && o.dim() == 3, "xdot.", op, ": o must be a (B, R, H*D) GPU tensor");
+  TORCH_CHECK(o.scalar_type() == at::kBFloat16 || o.scalar_type() == at::kHalf || o.scalar_type() == at::kFloat,
+              "xdot.", op, ": bf16/fp16/fp32 only");
+  const int64_t C = o.size(2);
+  TORCH_CHECK(H > 0 && C > 0 && C % H == 0, "xdot.", op, ": H*D features, got C=", C, " H=", H);
+  TORCH_CHECK(o.size(0) < (1LL << 31) && o.size(1) < (1LL << 31) && C < (1LL << 31), "xdot.", op, ": too large");
+  TORCH_CHECK(g.dim() == 3 && (g.size(2) == C || g.size(2) == H), "xdot.", op, ": g must be (B, R, ", C, ") or (B, R, ", H, ")");
+  headwise = g.size(2) != C;  // (D = 1: both kinds are the same thing; elementwise it is)
+  return C / H;
+}
+
+// o' = o * sigmoid(g) into out (out of place: out may not share memory with o or g)
+void gate_apply(const at::Tensor& o, const at::Tensor& g, int64_t H, at::Tensor& out, int64_t mode) {
+  Range rr_("xdot.gate_apply");
+  bool hw = false;
+  const int64_t D = gate_dims(o, g, H, "gate_apply", hw);
+  const int64_t B = o.size(0), R = o.size(1), C = o.size(2);
+  const GateView vo = gate_view(o, B, R, C, o, false, "gate_apply", "o");
+  const GateView vg = gate_view(g, B, R, hw ? H : C, o, false, "gate_apply", "g");
+  const GateView vy = gate_view(out, B, R, C, o, true, "gate_apply", "out");
+  if (o.numel() == 0) return;
+  TORCH_CHECK(gate_disjoint(gate_span(out, vy), gate_span(o, vo)) && gate_disjoint(gate_span(out, vy), gate_span(g, vg)),
+              "xdot.gate_apply: out may not share memory with o or g (out of place)");
+  const int64_t V = 16 / (int64_t)o.element_size();
+  const int vec = gate_vec(mode, vo.vec && vy.vec && (hw || vg.vec), D, V, "gate_apply");
+  xdot::GateArgs a{};
+  a.o = o.data_ptr(); a.g = g.data_ptr(); a.y = out.data_ptr();
+  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D; a.headwise = hw ? 1 : 0;
+  a.os_b = vo.sb; a.os_r = vo.sr; a.gs_b = vg.sb; a.gs_r = vg.sr; a.ys_b = vy.sb; a.ys_r = vy.sr;
+  c10::DeviceGuard guard(o.device());
+  launched(xdot_gate_apply_launch(&a, dt_code(o.scalar_type()), vec, cur_stream(o)), "gate_apply", "shape");
+}
+
+// do = dy * sigmoid(g) into dout (which may be dy itself) and dg -> a new contiguous tensor shaped like g
+at::Tensor gate_backward(const at::Tensor& dy, const at::Tensor& o, const at::Tensor& g, int64_t H, at::Tensor& dout,
+                         int64_t mode) {
+  Range rr_("xdot.gate_backward");
+  bool hw = false;
+  const int64_t D = gate_dims(o, g, H, "gate_backward", hw);
+  const int64_t B = o.size(0), R = o.size(1), C = o.size(2);
+  const GateView vo = gate_view(o, B, R, C, o, false, "gate_backward", "o");
+  const GateView vg = gate_view(g, B, R, hw ? H : C, o, false, "gate_backward", "g");
+  const GateView vd = gate_view(dy, B, R, C, o, false, "gate_backward", "dy");
+  const GateView vy = gate_view(dout, B, R, C, o, true, "gate_backward", "dout");
+  auto dg = at::empty({B, R, hw ? H : C}, o.options());
+  if (o.numel() == 0) return dg;
+  TORCH_CHECK(gate_disjoint(gate_span(dout, vy), gate_span(o, vo)) && gate_disjoint(gate_span(dout, vy), gate_span(g, vg)),
+              "xdot.gate_backward: dout may not share memory with o or g");
+  // (every element of do is written by the lane that read that element of dy: dy itself, or apart)
+  TORCH_CHECK((dout.data_ptr() == dy.data_ptr() && vy.sb == vd.sb && vy.sr == vd.sr) ||
+                  gate_disjoint(gate_span(dout, vy), gate_span(dy, vd)),
+              "xdot.gate_backward: dout must be dy itself (same strides) or share no memory with it");
+  const int64_t V = 16 / (int64_t)o.element_size();
+  const int vec = gate_vec(mode, vo.vec && vy.vec && vd.vec && (hw || vg.vec), D, V, "gate_backward");
+  xdot::GateArgs a{};
+  a.o = o.data_ptr(); a.g = g.data_ptr(); a.dy = dy.data_ptr(); a.y = dout.data_ptr(); a.dg = dg.data_ptr();
+  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D; a.headwise = hw ? 1 : 0;
+  a.os_b = vo.sb; a.os_r = vo.sr; a.gs_b = vg.sb; a.gs_r = vg.sr; a.ys_b = vy.sb; a.ys_r = vy.sr;
+  a.ds_b = vd.sb; a.ds_r = vd.sr;
+  c10::DeviceGuard guard(o.device());
+  launched(xdot_gate_backward_launch(&a, dt_code(o.scalar_type()), vec, cur_stream(o)), "gate_backward", "shape");
+  return dg;
+}
+
 // δ = rowsum(dO ⊙ O) per (b, h, row), fp32 (B, H, R)
 at::Tensor flash_bwd_delta(const at::Tensor& dout, const at::Tensor& out, int64_t H) {
   Range rr_("xdot.flash_bwd_delta");
@@ -867,6 +974,8 @@ TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("headnorm_bwd", &headnorm_bwd);
   m.impl("sink_fold", &sink_fold);
   m.impl("sink_grad", &sink_grad);
+  m.impl("gate_apply", &gate_apply);
+  m.impl("gate_backward", &gate_backward);
   m.impl("flash_fwd_partial", &flash_fwd_partial);
   m.impl("flash_fwd_combine", &flash_fwd_combine);
   m.impl("flash_fwd_merge", &flash_fwd_merge);

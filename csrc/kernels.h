@@ -241,6 +241,19 @@ struct SinkGradArgs {
   int s_dt;
   int B, R, H, nparts;
 };
+// gated attention (csrc/gate.hip): o' = o * sigmoid(g) on the merged attention output.  apply reads
+// o, g and writes y = o'; backward reads dy = do', o, g and writes y = do = do' * sigmoid(g) (y may be
+// dy's memory) and dg.  Strides in elements; the last dimension has unit stride everywhere.
+struct GateArgs {
+  const void* o;           // (B, R, H*D)
+  const void* g;           // (B, R, H*D), or (B, R, H) with headwise
+  const void* dy;          // backward: do' (B, R, H*D)
+  void* y;                 // apply: o'; backward: do
+  void* dg;                // backward: contiguous (B, R, H*D) or (B, R, H)
+  int B, R, H, D;
+  int headwise;            // 0: one gate value per feature, 1: one per (row, head)
+  int64_t os_b, os_r, gs_b, gs_r, ys_b, ys_r, ds_b, ds_r;
+};
 namespace ipc {
 constexpr int MAXR = 8;     // ranks of one node
 constexpr int MAXG = 256;   // workgroups (byte ranges) per collective
@@ -346,6 +359,11 @@ int xdot_headnorm_dw_launch(const float* part, void* dw, int nparts, int D, int 
 int xdot_sink_fold_launch(const xdot::SinkArgs* a, int dt, hipStream_t st);
 int xdot_sink_grad_parts(int B, int R);
 int xdot_sink_grad_launch(const xdot::SinkGradArgs* a, hipStream_t st);
+// gated attention (csrc/gate.hip), one launch each.  vec: 16-byte lane steps (the caller checked
+// D, strides and pointers), else one element per step.  0 without a launch for an empty B or R; -1:
+// a bad shape or kind, a missing pointer, D no multiple of the vector, or a grid past 2^31
+int xdot_gate_apply_launch(const xdot::GateArgs* a, int dt, int vec, hipStream_t st);
+int xdot_gate_backward_launch(const xdot::GateArgs* a, int dt, int vec, hipStream_t st);
 // rows per workgroup of the forward kernel (128)
 int xdot_flash_fwd_rows_per_wg();
 // one AdamW step over a->nt tensors of dtype dt (params/grads), fp32 moments

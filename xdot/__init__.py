@@ -16,4 +16,4 @@ from .parallel import (distributed_matmul_nt, distributed_matmul_all, distribute
                        allreduce_gradients, GradSync, gather_sequence, shard_rows, unshard_rows)
 from .models import DistributedDotProductAttn  # noqa: E402,F401
 from .ops import (scale_mask_softmax, linear, FusedAdamW, MSELoss, mse_loss, StructuredMask,  # noqa: E402,F401
-                  Rotary, rope, HeadRMSNorm, head_rms_norm)
+                  Rotary, rope, HeadRMSNorm, head_rms_norm, sigmoid_gate)

@@ -79,6 +79,19 @@ Keyword-only knobs (each mirrors an environment flag, the argument
                 rounded once by the kernel and once by the fold).  The parameter is replicated: each
                 rank's gradient is the partial over its rows, which ``GradSync`` sums.  ``False``
                 (default): no parameter, no launch, the same result bit for bit.
+``gate``        ``'elementwise'`` | ``'headwise'``: gated attention (Qiu et al. 2025; Qwen3-Next), a
+                query-dependent sigmoid gate on the merged attention output before ``composition``:
+                ``g = gate(keys_input)``, ``o' = o * sigmoid(g)``, ``out = composition(o')``, with
+                ``self.gate`` an ``nn.Linear(key_dim, value_dim)`` (``'elementwise'``: one gate value
+                per output feature) or ``nn.Linear(key_dim, num_heads)`` (``'headwise'``: one per
+                (row, row head), broadcast over that head's features; grouped heads do not change
+                it), bias as ``add_bias``, ``nn.Linear``'s own initialisation: a zero pre-activation
+                HALVES the output.  The order on every path is attention (sinks included), gate,
+                ``composition``; the gate is row-local, so layout, gather chunks, ring hops and
+                grouped heads do not see it.  One pass each way (``csrc/gate.hip``,
+                :func:`xdot.sigmoid_gate`); no flash kernel changes.  The parameters are replicated
+                like the other projections'.  ``None`` (default): no submodule, no ``state_dict``
+                key, no launch, the same result bit for bit.
 """
 from __future__ import annotations
 
@@ -90,6 +103,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _ext
+from ..ops.gate import sigmoid_gate
 from ..ops.linear import linear
 from ..ops.mask import StructuredMask
 from ..ops.headnorm import HeadRMSNorm, head_rms_norm, norm_packed
@@ -155,7 +169,7 @@ class DistributedDotProductAttn(nn.Module):
                  backend: str = "auto", dtype: Optional[torch.dtype] = None, chunk_plan: Optional[int] = None,
                  comm: Optional[_comm.Communicator] = None, rope: Optional[Rotary] = None,
                  num_gathered_heads: Optional[int] = None, layout: str = "contiguous", qk_norm: bool = False,
-                 qk_norm_eps: float = 1e-6, sinks: bool = False):
+                 qk_norm_eps: float = 1e-6, sinks: bool = False, gate: Optional[str] = None):
         super().__init__()
         check_layout(layout)
         if fused is not None:
@@ -187,6 +201,8 @@ class DistributedDotProductAttn(nn.Module):
                 raise ValueError(f"rope needs an even head dim, got {key_dim // num_heads}")
         if not float(qk_norm_eps) > 0.0:
             raise ValueError(f"qk_norm_eps must be positive, got {qk_norm_eps!r}")
+        if gate is not None and gate not in ("headwise", "elementwise"):
+            raise ValueError(f"gate must be None, 'headwise' or 'elementwise', got {gate!r}")
         self.num_heads = num_heads
         self.num_gathered_heads = int(num_gathered_heads)
         self.value_dim = value_dim
@@ -214,6 +230,10 @@ class DistributedDotProductAttn(nn.Module):
             self.sinks = nn.Parameter(torch.zeros(num_heads))
         else:
             self.register_parameter("sinks", None)
+        self.gate_kind = gate
+        if gate is not None:  # (no submodule without it: reference checkpoints keep loading)
+            # a zero pre-activation halves the output: sigmoid(0) = 1/2
+            self.gate = nn.Linear(key_dim, value_dim if gate == "elementwise" else num_heads, bias=add_bias)
         # weakref to an attached xdot.parallel.GradSync (set by it): the fused node hands it the
         # parameter gradients as they are computed (early all-reduce)
         self._xdot_grad_sync = None
@@ -248,6 +268,16 @@ class DistributedDotProductAttn(nn.Module):
         return t.to(self.compute_dtype)
 
     def _forward(self, keys: Tensor, queries: Tensor, values: Tensor, attn_mask: Optional[Tensor]) -> Tensor:
+        if FLAGS.check and self.distributed:
+            # ranks that disagree on the gate would hang in GradSync (one more pair of gradients): the
+            # kind rides in the fingerprints of the distributed ops below (XDOT_CHECK)
+            from ..utils.checks import fingerprint_extra
+
+            with fingerprint_extra("gate", self.gate_kind):
+                return self._forward_impl(keys, queries, values, attn_mask)
+        return self._forward_impl(keys, queries, values, attn_mask)
+
+    def _forward_impl(self, keys: Tensor, queries: Tensor, values: Tensor, attn_mask: Optional[Tensor]) -> Tensor:
         scale = 1.0 / math.sqrt(self.dim)
         lay = self.layout if self.distributed else "contiguous"  # (a world of one: the identity)
         if self._pick_impl(keys) == "flash":
@@ -272,7 +302,7 @@ class DistributedDotProductAttn(nn.Module):
                 k = pa.pad_heads(k, H, dk, Dp)
                 o = seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm, gathered_heads=gh, layout=lay,
                                                   sinks=self.sinks)
-                return self._proj(self.composition, pa.unpad_heads(o, H, dv, Dp))
+                return self._proj(self.composition, self._gated(pa.unpad_heads(o, H, dv, Dp), keys))
             if isinstance(attn_mask, Tensor) and attn_mask.is_cuda and attn_mask.dim() == 3 and FLAGS.mask_async \
                     and (lay == "contiguous" or comm.world_size == 1):
                 # pack the mask on a side stream while the projection GEMMs run (its columns as they
@@ -295,6 +325,7 @@ class DistributedDotProductAttn(nn.Module):
                         _stacked_rows(bq, bv)
                 gs = self._xdot_grad_sync() if self._xdot_grad_sync is not None else None
                 sync = None
+                has_gate = self.gate_kind is not None
                 if gs is not None and torch.is_grad_enabled():
                     gs.note_use(id(self))
                     sync = (gs, id(self))
@@ -302,8 +333,10 @@ class DistributedDotProductAttn(nn.Module):
                                          self.composition.weight, self.composition.bias, self.num_heads, scale, comm,
                                          self.chunk_plan, sync, torch.is_grad_enabled(), self.rope, gh, lay,
                                          *((self.keys_norm.weight, self.queries_norm.weight, self.qk_norm_eps)
-                                           if self.qk_norm else ((None, None, 1e-6) if self.sinks is not None else ())),
-                                         *((self.sinks,) if self.sinks is not None else ()))
+                                           if self.qk_norm else ((None, None, 1e-6) if self.sinks is not None or has_gate
+                                                                 else ())),
+                                         *((self.sinks,) if self.sinks is not None or has_gate else ()),
+                                         *((self.gate.weight, self.gate.bias) if has_gate else ()))
             # gathered side first: its all-gather runs while the row-side GEMM computes
             qv = self._project_qv(queries, values)
             pre = False
@@ -326,7 +359,7 @@ class DistributedDotProductAttn(nn.Module):
                     k = rope_packed(k, H * dk, H, self.rope, off, alpha=al, bwd_alpha=1.0)
             o = seq_parallel_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm, pending=pending,
                                               k_prescaled=pre, gathered_heads=gh, layout=lay, sinks=self.sinks)
-            return self._proj(self.composition, o)
+            return self._proj(self.composition, self._gated(o, keys))
         if self._pick_impl(keys) == "ring":
             from ..parallel.ring import ring_attention_packed
 
@@ -344,7 +377,7 @@ class DistributedDotProductAttn(nn.Module):
             o = ring_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm,
                                       gathered_heads=None if self.num_gathered_heads == self.num_heads
                                       else self.num_gathered_heads, layout=lay, sinks=self.sinks)
-            return self._proj(self.composition, o)
+            return self._proj(self.composition, self._gated(o, keys))
         k = self._proj(self.keys, keys)
         q = self._proj(self.queries, queries)
         v = self._proj(self.values, values)
@@ -353,7 +386,14 @@ class DistributedDotProductAttn(nn.Module):
             off = self._rope_offset(c, k.shape[1], lay)
             k = self._norm_rope(k, self.num_heads, True, off)
             q = self._norm_rope(q, self.num_gathered_heads, False, off)
-        return self._proj(self.composition, self._materialized(k, q, v, attn_mask, scale))
+        return self._proj(self.composition, self._gated(self._materialized(k, q, v, attn_mask, scale), keys))
+
+    def _gated(self, o: Tensor, keys: Tensor) -> Tensor:
+        """``o * sigmoid(gate(keys))`` (``o`` itself without a gate): after the attention, sink fold
+        included, and before ``composition``."""
+        if self.gate_kind is None:
+            return o
+        return sigmoid_gate(o, self._proj(self.gate, keys), self.num_heads)
 
     def _rope_offset(self, comm, R: int, lay: str):
         """This rank's rotary positions (None without ``rope``)."""
@@ -439,4 +479,5 @@ class DistributedDotProductAttn(nn.Module):
                 + (f", num_gathered_heads={self.num_gathered_heads}" if self.num_gathered_heads != self.num_heads else "")
                 + (f", layout={self.layout}" if self.layout != "contiguous" else "")
                 + (f", qk_norm=True, qk_norm_eps={self.qk_norm_eps:g}" if self.qk_norm else "")
-                + (", sinks=True" if self.sinks is not None else ""))
+                + (", sinks=True" if self.sinks is not None else "")
+                + (f", gate={self.gate_kind}" if self.gate_kind is not None else ""))

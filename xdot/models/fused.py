@@ -27,6 +27,13 @@ pre-norm ``k`` / ``q`` (both are overwritten in place), the backward's passes ru
 and the ``q`` part of ``d[q|v]`` and return the two gain gradients.
 With attention sinks (``sinks``: the (H,) logits) the attention folds them into its finished forward
 and its backward hands back their gradient, which goes to ``GradSync`` like every replicated parameter's.
+With a gate (``wg`` / ``bg``: the gate projection, ``xdot.ops.gate``) ``g = x_k Wgᵀ (+b)`` is issued beside
+the ``k`` projection, under the all-gather; ``o' = o ⊙ σ(g)`` (``csrc/gate.hip``, one launch) runs between
+the attention and the output projection, which reads ``o'``.  Kept for the backward: ``o'`` (the output
+projection's weight gradient) and ``g``; the ungated ``o`` is the tensor the attention saves anyway.  The
+backward runs the output projection's ``linear_backward`` on ``(dout, o')``, one ``gate_backward`` launch
+(``do`` in place over ``do'``), the unchanged attention backward on ``do``, then the gate projection's
+gradients; its input gradient is ADDED to ``dx_k`` (one add pass).
 """
 from __future__ import annotations
 
@@ -34,6 +41,7 @@ import torch
 
 from .. import _ext
 from ..ops.linear import linear_backward, native_wgrad, proj, weight_grad_pair
+from ..ops.gate import gate_apply, gate_backward
 from ..ops.headnorm import head_rms_norm_apply, head_rms_norm_backward
 from ..ops.rope import _table_dtype, rope_apply
 from ..utils.env import FLAGS
@@ -85,11 +93,13 @@ class AttnBlockFn(torch.autograd.Function):
     @staticmethod
     @_ext.pinned
     def forward(ctx, xk, xqv, mask, wk, bk, wq, bq, wv, bv, wc, bc, H, scale, comm, chunk_plan, sync=None,
-                grad_on=True, rope=None, Hg=None, layout="contiguous", wkn=None, wqn=None, norm_eps=1e-6, sinks=None):
+                grad_on=True, rope=None, Hg=None, layout="contiguous", wkn=None, wqn=None, norm_eps=1e-6, sinks=None,
+                wg=None, bg=None):
         # Hg: gathered heads when fewer than H (grouped-query attention): wq / wv hold Hg heads
         # layout: the row sharding (xdot.parallel.layout): the rotary positions and the mask follow it
         # wkn / wqn: the (D,) gains of QK-norm on k / q (both or neither), norm_eps its eps
         # sinks: the (H,) attention-sink logits (a replicated parameter) or None
+        # wg / bg: the gate projection ((C, C): one gate value per feature, (H, C): one per head) or None
         wqv = _rows(wq, wv)
         bqv = _rows(bq, bv) if bq is not None else None
         n = comm.world_size
@@ -137,15 +147,20 @@ class AttnBlockFn(torch.autograd.Function):
             k = proj(xk, wk, bk, alpha=scale * _LOG2E if pre else 1.0)
             if tab is not None:  # the pre-scale sits in the projection: a rotation commutes with a scalar
                 rope_apply(k, H, *tab, out=k)
+        # the gate projection beside the k projection: under the all-gather too
+        g = proj(xk, wg, bg) if wg is not None else None
         actx = _Ctx()
         actx.needs_input_grad = (any(ctx.needs_input_grad),) * 2  # a backward can run (score buffers)
         o = SeqParallelAttention.forward(actx, k, qv, mask, H, scale, comm, pending, pre, grad_on, Hg,  # k_prescaled
                                          layout, sinks)
-        out = proj(o, wc, bc)
+        # gated attention: o' = o * sigmoid(g), out of place (the attention keeps o for delta)
+        og = gate_apply(o, g, H) if g is not None else o
+        out = proj(og, wc, bc)
         ctx.actx = actx
         ctx.sync = sync  # (GradSync, module key) or None
         ctx.params = (wk, bk, wq, bq, wv, bv, wc, bc)
         ctx.sinks = sinks
+        ctx.gate = (wg, bg) if wg is not None else None
         ctx.nq = nq
         ctx.rope_tab, ctx.H, ctx.Hg = tab, H, Hg or H
         ctx.has_b = (bk is not None, bq is not None, bc is not None)
@@ -153,14 +168,18 @@ class AttnBlockFn(torch.autograd.Function):
         # retained for a second backward keeps them)
         asaved, actx._saved = actx._saved, None
         ctx.nnorm = len(nsaved)
-        ctx.save_for_backward(xk, xqv, wk, wqv, wc, o, *nsaved, *asaved)
+        gsaved = (og, g, wg) if g is not None and keep else ()
+        ctx.ngate = len(gsaved)
+        ctx.save_for_backward(xk, xqv, wk, wqv, wc, o, *gsaved, *nsaved, *asaved)
         return out
 
     @staticmethod
     @_ext.pinned
     def backward(ctx, dout):
         xk, xqv, wk, wqv, wc, o, *asaved = ctx.saved_tensors
+        gsaved, asaved = asaved[:ctx.ngate], asaved[ctx.ngate:]
         nsaved, asaved = asaved[:ctx.nnorm], asaved[ctx.nnorm:]
+        oc = gsaved[0] if gsaved else o  # what the output projection read: o' with a gate
         ctx.actx._saved = tuple(asaved)
         ng = ctx.needs_input_grad
         hk, hq, hc = ctx.has_b
@@ -180,17 +199,20 @@ class AttnBlockFn(torch.autograd.Function):
                else None) if sync is not None else (lambda *ps: None)
         side = _wgrad_stream(dout)
         if side is None:
-            do, dwc, dbc = linear_backward(dout, o, wc, True, ng[9], hc and ng[10], dw_dtype=wdt(wc_, bc_))
+            do, dwc, dbc = linear_backward(dout, oc, wc, True, ng[9], hc and ng[10], dw_dtype=wdt(wc_, bc_))
         else:
-            do, _, _ = linear_backward(dout, o, wc, True, False, False)
+            do, _, _ = linear_backward(dout, oc, wc, True, False, False)
             dout._xdot_ready_on = _ready_on(dout, side)
-            _, dwc, dbc = linear_backward(dout, o, wc, False, ng[9], hc and ng[10], join=False, dw_dtype=wdt(wc_, bc_))
+            _, dwc, dbc = linear_backward(dout, oc, wc, False, ng[9], hc and ng[10], join=False, dw_dtype=wdt(wc_, bc_))
         # the current stream is only looked up when a side stream is in play (host cost per call)
         cur = torch.cuda.current_stream(dout.device) if side is not None else None
         if sync is not None:  # hand the output projection's gradients to GradSync now: their
             # all-reduce runs under the attention backward (stream None: the current one)
             sync.deliver([(wc_, dwc), (bc_, dbc)], stream=side)
             dwc = dbc = None
+        dg = None
+        if gsaved:  # do' -> do in place, and dg: one launch
+            _, dg = gate_backward(do, o, gsaved[1], ctx.H, out=do)
         agrads = SeqParallelAttention.backward(ctx.actx, do)
         dk, dqv, dsk = agrads[0], agrads[1], agrads[-1]  # (dsk: this rank's rows' share of the sinks' gradient)
         if dsk is not None and not ng[23]:
@@ -249,6 +271,18 @@ class AttnBlockFn(torch.autograd.Function):
                 dxk, _, _ = linear_backward(dk, xk, wk, ng[0], False, False)
                 _, dwk, dbk = linear_backward(dk, xk, wk, False, need_wk, hk and ng[4], join=False, dw_dtype=kdt)
             dxqv, dwqv, dbqv = linear_backward(dqv, xqv, wqv, ng[1], need_wqv, hq and (ng[6] or ng[8]), dw_dtype=qvdt)
+        dwg = dbg = None
+        if dg is not None:
+            # the gate projection reads the row-side input too: its input gradient is added to dx_k
+            # (one add pass), its weight / bias gradients are this rank's partial over its rows
+            wg_, bg_ = ctx.gate
+            dxg, dwg, dbg = linear_backward(dg, xk, gsaved[2], ng[0], ng[24], bg_ is not None and ng[25],
+                                            dw_dtype=wdt(wg_, bg_))
+            if dxg is not None:
+                dxk = dxg if dxk is None else dxk.add_(dxg)
+            if sync is not None:
+                sync.deliver([(wg_, dwg), (bg_, dbg)])
+                dwg = dbg = None
         n = ctx.nq
         dwq = dwv = dbq = dbv = None
         # the packed products cover both halves; hand back only what is asked for (a frozen
@@ -275,4 +309,4 @@ class AttnBlockFn(torch.autograd.Function):
         ctx.actx._saved = None
         grads = (dxk, dxqv, None, dwk, dbk, dwq, dbq, dwv, dbv, dwc, dbc, None, None, None, None, None, None, None, None,
                  None)
-        return (grads + (dwkn, dwqn, None, dsk))[:len(ng)]
+        return (grads + (dwkn, dwqn, None, dsk, dwg, dbg))[:len(ng)]

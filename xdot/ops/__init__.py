@@ -8,3 +8,4 @@ from .loss import mse_loss, MSELoss  # noqa: F401
 from .mask import StructuredMask  # noqa: F401
 from .rope import Rotary, rope  # noqa: F401
 from .headnorm import HeadRMSNorm, head_rms_norm  # noqa: F401
+from .gate import sigmoid_gate  # noqa: F401

@@ -9,12 +9,32 @@ error on the first divergence instead of deadlocking inside RCCL.
 from __future__ import annotations
 
 import itertools
+import threading
 
 import torch
 
 from .env import FLAGS
 
 _counter = itertools.count()
+_tls = threading.local()
+
+
+class fingerprint_extra:
+    """``with fingerprint_extra("gate", kind):`` -- options of the calling module that the distributed
+    ops below it do not see themselves ride in THEIR fingerprints on this thread (no collective of
+    their own)."""
+
+    def __init__(self, *items):
+        self.items = tuple(items)
+
+    def __enter__(self):
+        self.prev = getattr(_tls, "extra", ())
+        _tls.extra = self.prev + self.items
+        return self
+
+    def __exit__(self, *exc):
+        _tls.extra = self.prev
+        return False
 
 
 class RankDivergenceError(RuntimeError):
@@ -34,7 +54,7 @@ def fingerprint(op: str, *items) -> tuple:
 def check_consistent(comm, op: str, *items, force: bool = False) -> None:
     if not (FLAGS.check or force) or comm.world_size == 1:
         return
-    fp = (next(_counter),) + fingerprint(op, *items)
+    fp = (next(_counter),) + fingerprint(op, *items, *getattr(_tls, "extra", ()))
     allfp = comm.all_gather_object(fp)
     if any(f[1:] != allfp[0][1:] for f in allfp):
         lines = "\n".join(f"  rank {r}: {f}" for r, f in enumerate(allfp))
