@@ -5,6 +5,7 @@
 // current HIP stream and calls the C-ABI launchers.  Every launch is bounds-checked on
 // the host against the tensors' storage so a bad stride can never turn into a GPU fault.
 // The flash-attention ops are implemented (and bound to their schemas below) in bindings_flash.cpp,
+// the row-wise ops around them (rope_*, headnorm_*, sink_*, gate_*) in bindings_rowops.cpp,
 // the GEMM ops (gemm, gemm_plan, proj, wgrad, wgrad2) in bindings_gemm.cpp.
 #include "bindings_common.h"
 

@@ -92,11 +92,6 @@ float* sbuf_ptr(const OptT& sbuf, const FlashGeom& g, int64_t H, const at::Tenso
   return t.data_ptr<float>();
 }
 
-// a contiguous fp32 (B, H, R) tensor (lse, lse2, delta) on the launch's device
-void check_bhr(const at::Tensor& t, int64_t B, int64_t H, int64_t R, const at::Device& dev, const char* what) {
-  TORCH_CHECK(t.is_contiguous() && t.scalar_type() == at::kFloat && t.numel() == B * H * R && t.device() == dev, what);
-}
-
 // ---- grid planning -----------------------------------------------------------------------
 // nsplit column splits of `blocks` row blocks; heavy: per XCD `whole` row blocks run unsplit, only the
 // last `rem` in nsplit pieces
@@ -404,413 +399,6 @@ at::Tensor flash_prescale(const at::Tensor& x, double scale) {
   return out;
 }
 
-// rotary table: cos / sin (R, D/2) fp32 of double(offset + row) * inv_freq[i] (csrc/rope.hip)
-std::tuple<at::Tensor, at::Tensor> rope_table(int64_t R, int64_t D, int64_t offset, const at::Tensor& inv_freq) {
-  Range rr_("xdot.rope_table");
-  TORCH_CHECK(D >= 2 && D % 2 == 0 && D < (1LL << 31), "xdot.rope_table: head dim must be even, got ", D);
-  TORCH_CHECK(R >= 0 && offset >= 0 && offset + R <= 2147483647LL, "xdot.rope_table: positions must stay below 2^31");
-  TORCH_CHECK(inv_freq.is_cuda() && inv_freq.scalar_type() == at::kDouble && inv_freq.is_contiguous() &&
-                  inv_freq.numel() == D / 2,
-              "xdot.rope_table: inv_freq must be a contiguous fp64 device tensor of D/2 entries");
-  auto cosb = at::empty({R, D / 2}, inv_freq.options().dtype(at::kFloat));
-  auto sinb = at::empty_like(cosb);
-  c10::DeviceGuard guard(inv_freq.device());
-  launched(xdot_rope_table_launch(cosb.data_ptr<float>(), sinb.data_ptr<float>(), inv_freq.data_ptr<double>(), (int)R,
-                                  (int)(D / 2), offset, cur_stream(inv_freq)),
-           "rope_table", "shape");
-  return {cosb, sinb};
-}
-
-// out = alpha * rotate(x): x, out (B, R, H*D) with unit inner stride and any row / batch strides
-// (the q half of a packed [q|v] buffer, a rank slot of the gather buffer); out may be x itself
-void rope_apply(const at::Tensor& x, const at::Tensor& cosb, const at::Tensor& sinb, int64_t H, bool inverse,
-                double alpha, at::Tensor& out) {
-  Range rr_("xdot.rope_apply");
-  TORCH_CHECK(x.is_cuda() && out.is_cuda() && cosb.is_cuda() && sinb.is_cuda() && out.device() == x.device() &&
-                  cosb.device() == x.device() && sinb.device() == x.device(),
-              "xdot.rope_apply: tensors of one GPU required");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf || x.scalar_type() == at::kFloat,
-              "xdot.rope_apply: bf16/fp16/fp32 only");
-  TORCH_CHECK(x.dim() == 3 && out.sizes() == x.sizes() && out.scalar_type() == x.scalar_type(),
-              "xdot.rope_apply: x and out must be (B, R, H*D) of one dtype");
-  const int64_t B = x.size(0), R = x.size(1), C = x.size(2);
-  TORCH_CHECK(H > 0 && C % H == 0 && (C / H) % 2 == 0, "xdot.rope_apply: H*D with an even head dim D, got C=", C, " H=", H);
-  TORCH_CHECK(B < (1LL << 31) && R < (1LL << 31) && C < (1LL << 31) && B * H < (1LL << 31), "xdot.rope_apply: too large");
-  const int64_t D = C / H;
-  TORCH_CHECK(cosb.scalar_type() == at::kFloat && sinb.scalar_type() == at::kFloat && cosb.is_contiguous() &&
-                  sinb.is_contiguous() && cosb.dim() == 2 && cosb.size(0) == R && cosb.size(1) == D / 2 &&
-                  sinb.sizes() == cosb.sizes(),
-              "xdot.rope_apply: cos / sin must be contiguous fp32 (R, D/2)");
-  if (x.numel() == 0) return;
-  const int64_t V = 16 / (int64_t)x.element_size();
-  int64_t st[4];  // x batch, x row, out batch, out row (a stride of a size-1 dim is never used)
-  bool vec = aligned16(x.data_ptr()) && aligned16(out.data_ptr()) && aligned16(cosb.data_ptr()) && aligned16(sinb.data_ptr());
-  int k = 0;
-  for (const at::Tensor* t : {&x, static_cast<const at::Tensor*>(&out)}) {
-    TORCH_CHECK(t->stride(2) == 1 || C == 1, "xdot.rope_apply: the last dimension must have stride 1");
-    const int64_t sb = B > 1 ? t->stride(0) : 0, sr = R > 1 ? t->stride(1) : 0;
-    TORCH_CHECK(sb >= 0 && sr >= 0, "xdot.rope_apply: negative strides");
-    TORCH_CHECK((B - 1) * sb + (R - 1) * sr + C <= avail_elems(*t), "xdot.rope_apply: view out of bounds");
-    vec = vec && sb % V == 0 && sr % V == 0;
-    st[k++] = sb;
-    st[k++] = sr;
-  }
-  // in place (the same view) or disjoint: a lane reads only the pairs it writes
-  if (x.data_ptr() == out.data_ptr()) {
-    TORCH_CHECK(st[0] == st[2] && st[1] == st[3], "xdot.rope_apply: an in-place out must be the same view as x");
-  } else {
-    const char* xb = static_cast<const char*>(x.data_ptr());
-    const char* ob = static_cast<const char*>(out.data_ptr());
-    const int64_t es = (int64_t)x.element_size();
-    const int64_t xe = ((B - 1) * st[0] + (R - 1) * st[1] + C) * es, oe = ((B - 1) * st[2] + (R - 1) * st[3] + C) * es;
-    TORCH_CHECK(xb + xe <= ob || ob + oe <= xb, "xdot.rope_apply: x and out overlap");
-  }
-  xdot::RopeArgs a{};
-  a.x = x.data_ptr(); a.out = out.data_ptr();
-  a.cos = cosb.data_ptr<float>(); a.sin = sinb.data_ptr<float>();
-  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D;
-  a.xs_b = st[0]; a.xs_r = st[1]; a.os_b = st[2]; a.os_r = st[3];
-  a.alpha = (float)alpha; a.inverse = inverse ? 1 : 0;
-  const int64_t half = D / 2;
-  const int mode = !vec ? 0 : (half % V == 0 ? 1 : (half > V ? 2 : 0));
-  c10::DeviceGuard guard(x.device());
-  launched(xdot_rope_apply_launch(&a, dt_code(x.scalar_type()), mode, cur_stream(x)), "rope_apply", "shape");
-}
-
-// ---- per-head RMSNorm fused with the rotation (csrc/headnorm.hip) ----
-// the (B, R, C) views of one headnorm call: unit inner stride, any non-negative row / batch strides,
-// inside their storage (as rope_apply).  Returns batch / row strides per view and whether every
-// view is on the 16-byte grid
-struct HnViews { int64_t st[3][2]; bool vec; };
-
-HnViews hn_views(std::initializer_list<const at::Tensor*> ts, int64_t B, int64_t R, int64_t C, const char* op) {
-  HnViews v{};
-  v.vec = true;
-  const at::Tensor& first = **ts.begin();
-  const int64_t V = 16 / (int64_t)first.element_size();
-  int k = 0;
-  for (const at::Tensor* t : ts) {
-    TORCH_CHECK(t->is_cuda() && t->device() == first.device(), "xdot.", op, ": tensors of one GPU required");
-    TORCH_CHECK(t->dim() == 3 && t->size(0) == B && t->size(1) == R && t->size(2) == C &&
-                    t->scalar_type() == first.scalar_type(),
-                "xdot.", op, ": the views must be (B, R, H*D) of one dtype");
-    TORCH_CHECK(t->stride(2) == 1 || C == 1, "xdot.", op, ": the last dimension must have stride 1");
-    const int64_t sb = B > 1 ? t->stride(0) : 0, sr = R > 1 ? t->stride(1) : 0;
-    TORCH_CHECK(sb >= 0 && sr >= 0, "xdot.", op, ": negative strides");
-    TORCH_CHECK((B - 1) * sb + (R - 1) * sr + C <= avail_elems(*t), "xdot.", op, ": view out of bounds");
-    v.vec = v.vec && aligned16(t->data_ptr()) && sb % V == 0 && sr % V == 0;
-    v.st[k][0] = sb;
-    v.st[k][1] = sr;
-    ++k;
-  }
-  return v;
-}
-
-// `dst` is written while `src` is read: the same view (in place) or disjoint memory
-void hn_no_overlap(const at::Tensor& src, const int64_t* ss, const at::Tensor& dst, const int64_t* ds, int64_t B,
-                   int64_t R, int64_t C, const char* op) {
-  if (src.data_ptr() == dst.data_ptr()) {
-    TORCH_CHECK(ss[0] == ds[0] && ss[1] == ds[1], "xdot.", op, ": an in-place output must be the same view as its input");
-    return;
-  }
-  const char* sb = static_cast<const char*>(src.data_ptr());
-  const char* db = static_cast<const char*>(dst.data_ptr());
-  const int64_t es = (int64_t)src.element_size();
-  const int64_t se = ((B - 1) * ss[0] + (R - 1) * ss[1] + C) * es, de = ((B - 1) * ds[0] + (R - 1) * ds[1] + C) * es;
-  TORCH_CHECK(sb + se <= db || db + de <= sb, "xdot.", op, ": input and output overlap");
-}
-
-// weight (D,) in x's dtype or fp32; cos / sin both or neither, contiguous fp32 (R, D/2)
-void hn_params(const at::Tensor& x, const at::Tensor& weight, const OptT& cosb, const OptT& sinb, int64_t R, int64_t D,
-               const char* op) {
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf || x.scalar_type() == at::kFloat,
-              "xdot.", op, ": bf16/fp16/fp32 only");
-  TORCH_CHECK(weight.is_cuda() && weight.device() == x.device() && weight.dim() == 1 && weight.size(0) == D &&
-                  weight.is_contiguous() &&
-                  (weight.scalar_type() == x.scalar_type() || weight.scalar_type() == at::kFloat),
-              "xdot.", op, ": weight must be a contiguous (D,) = (", D, ",) tensor of x's dtype or fp32");
-  const bool hc = cosb.has_value() && cosb->defined(), hs = sinb.has_value() && sinb->defined();
-  TORCH_CHECK(hc == hs, "xdot.", op, ": cos and sin go together");
-  if (hc) {
-    TORCH_CHECK(D % 2 == 0, "xdot.", op, ": the rotation needs an even head dim, got ", D);
-    TORCH_CHECK(cosb->is_cuda() && sinb->is_cuda() && cosb->device() == x.device() && sinb->device() == x.device() &&
-                    cosb->scalar_type() == at::kFloat && sinb->scalar_type() == at::kFloat && cosb->is_contiguous() &&
-                    sinb->is_contiguous() && cosb->dim() == 2 && cosb->size(0) == R && cosb->size(1) == D / 2 &&
-                    sinb->sizes() == cosb->sizes(),
-                "xdot.", op, ": cos / sin must be contiguous fp32 (R, D/2)");
-  }
-}
-
-xdot::HeadNormPlan hn_plan(int64_t B, int64_t R, int64_t H, int64_t D, int64_t esize, const char* op) {
-  xdot::HeadNormPlan p{};
-  TORCH_CHECK(B < (1LL << 31) && R < (1LL << 31) && H * D < (1LL << 31) && B * H < (1LL << 31), "xdot.", op, ": too large");
-  TORCH_CHECK(xdot_headnorm_plan((int)B, (int)R, (int)H, (int)D, (int)esize, &p) == 0, "xdot.", op,
-              ": head dim ", D, " is too wide (one wave reduces a head row: D <= ", 64 * 2 * (16 / esize), ")");
-  return p;
-}
-
-// [G, rows per workgroup, forward grid x, y, backward grid x, y] of a headnorm launch (no launch)
-std::vector<int64_t> headnorm_plan(int64_t B, int64_t R, int64_t H, int64_t D, at::ScalarType dtype) {
-  TORCH_CHECK(B > 0 && R > 0 && H > 0 && D > 0, "xdot.headnorm_plan: shape");
-  const auto p = hn_plan(B, R, H, D, (int64_t)c10::elementSize(dtype), "headnorm_plan");
-  return {p.G, p.rows_per_wg, p.fwd_gx, p.fwd_gy, p.bwd_gx, p.bwd_gy};
-}
-
-// out = alpha * rotate(x * rstd * weight) per head of x (B, R, H*D) (rotation with a table only);
-// returns rstd (B, R, H) fp32 and, with save, a contiguous bit copy of x (else an empty tensor).
-// out may be x itself (the same view)
-std::tuple<at::Tensor, at::Tensor> headnorm_fwd(const at::Tensor& x, const at::Tensor& weight, const OptT& cosb,
-                                                const OptT& sinb, int64_t H, double eps, double alpha, at::Tensor& out,
-                                                bool save) {
-  Range rr_("xdot.headnorm_fwd");
-  TORCH_CHECK(x.is_cuda() && x.dim() == 3, "xdot.headnorm_fwd: x must be a (B, R, H*D) GPU tensor");
-  const int64_t B = x.size(0), R = x.size(1), C = x.size(2);
-  TORCH_CHECK(H > 0 && C > 0 && C % H == 0, "xdot.headnorm_fwd: H*D features, got C=", C, " H=", H);
-  TORCH_CHECK(eps > 0.0, "xdot.headnorm_fwd: eps must be positive");
-  const int64_t D = C / H;
-  hn_params(x, weight, cosb, sinb, R, D, "headnorm_fwd");
-  const HnViews v = hn_views({&x, static_cast<const at::Tensor*>(&out)}, B, R, C, "headnorm_fwd");
-  hn_no_overlap(x, v.st[0], out, v.st[1], B, R, C, "headnorm_fwd");
-  auto rstd = at::empty({B, R, H}, x.options().dtype(at::kFloat));
-  auto saved = save ? at::empty({B, R, C}, x.options()) : at::empty({0}, x.options());
-  if (x.numel() == 0) return {rstd, saved};
-  hn_plan(B, R, H, D, (int64_t)x.element_size(), "headnorm_fwd");
-  const bool rot = cosb.has_value() && cosb->defined();
-  xdot::HeadNormArgs a{};
-  a.x = x.data_ptr(); a.out = out.data_ptr(); a.save = save ? saved.data_ptr() : nullptr;
-  a.rstd = rstd.data_ptr<float>(); a.w = weight.data_ptr(); a.w_f32 = weight.scalar_type() == at::kFloat;
-  a.cos = rot ? cosb->data_ptr<float>() : nullptr; a.sin = rot ? sinb->data_ptr<float>() : nullptr;
-  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D;
-  a.xs_b = v.st[0][0]; a.xs_r = v.st[0][1]; a.os_b = v.st[1][0]; a.os_r = v.st[1][1];
-  a.alpha = (float)alpha; a.eps = (float)eps; a.inv_d = 1.0f / (float)D;
-  c10::DeviceGuard guard(x.device());
-  launched(xdot_headnorm_fwd_launch(&a, dt_code(x.scalar_type()), v.vec ? 1 : 0, cur_stream(x)), "headnorm_fwd", "shape");
-  return {rstd, saved};
-}
-
-// dx = rstd * (gw - xh * mean(gw . xh)) with gy = alpha * rotate^-1(g), xh = x * rstd, gw = gy * weight,
-// written to dx (may be g itself); returns dw = sum gy . xh in weight's dtype (need_dw), else empty.
-// Two launches: the pass, which leaves one fp32 (D,) partial per workgroup, and their ordered sum
-at::Tensor headnorm_bwd(const at::Tensor& g, const at::Tensor& x, const at::Tensor& rstd, const at::Tensor& weight,
-                        const OptT& cosb, const OptT& sinb, int64_t H, double alpha, at::Tensor& dx, bool need_dw) {
-  Range rr_("xdot.headnorm_bwd");
-  TORCH_CHECK(g.is_cuda() && g.dim() == 3, "xdot.headnorm_bwd: g must be a (B, R, H*D) GPU tensor");
-  const int64_t B = g.size(0), R = g.size(1), C = g.size(2);
-  TORCH_CHECK(H > 0 && C > 0 && C % H == 0, "xdot.headnorm_bwd: H*D features, got C=", C, " H=", H);
-  const int64_t D = C / H;
-  hn_params(g, weight, cosb, sinb, R, D, "headnorm_bwd");
-  const HnViews v = hn_views({&g, &x, static_cast<const at::Tensor*>(&dx)}, B, R, C, "headnorm_bwd");
-  hn_no_overlap(g, v.st[0], dx, v.st[2], B, R, C, "headnorm_bwd");
-  hn_no_overlap(x, v.st[1], dx, v.st[2], B, R, C, "headnorm_bwd");
-  TORCH_CHECK(x.data_ptr() != dx.data_ptr() || x.numel() == 0, "xdot.headnorm_bwd: dx may overwrite g, not x");
-  TORCH_CHECK(rstd.is_cuda() && rstd.device() == g.device() && rstd.scalar_type() == at::kFloat && rstd.is_contiguous() &&
-                  rstd.dim() == 3 && rstd.size(0) == B && rstd.size(1) == R && rstd.size(2) == H,
-              "xdot.headnorm_bwd: rstd must be contiguous fp32 (B, R, H)");
-  auto dw = need_dw ? at::empty({D}, weight.options()) : at::empty({0}, weight.options());
-  if (g.numel() == 0) {
-    if (need_dw) dw.zero_();
-    return dw;
-  }
-  const auto p = hn_plan(B, R, H, D, (int64_t)g.element_size(), "headnorm_bwd");
-  const int64_t nparts = (int64_t)p.bwd_gx * p.bwd_gy;
-  auto part = at::empty({nparts, D}, g.options().dtype(at::kFloat));
-  const bool rot = cosb.has_value() && cosb->defined();
-  xdot::HeadNormArgs a{};
-  a.x = x.data_ptr(); a.g = g.data_ptr(); a.out = dx.data_ptr(); a.rstd = rstd.data_ptr<float>();
-  a.w = weight.data_ptr(); a.w_f32 = weight.scalar_type() == at::kFloat; a.part = part.data_ptr<float>();
-  a.cos = rot ? cosb->data_ptr<float>() : nullptr; a.sin = rot ? sinb->data_ptr<float>() : nullptr;
-  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D;
-  a.gs_b = v.st[0][0]; a.gs_r = v.st[0][1]; a.xs_b = v.st[1][0]; a.xs_r = v.st[1][1];
-  a.os_b = v.st[2][0]; a.os_r = v.st[2][1];
-  a.alpha = (float)alpha; a.inv_d = 1.0f / (float)D;
-  c10::DeviceGuard guard(g.device());
-  launched(xdot_headnorm_bwd_launch(&a, dt_code(g.scalar_type()), v.vec ? 1 : 0, cur_stream(g)), "headnorm_bwd", "shape");
-  if (need_dw)
-    launched(xdot_headnorm_dw_launch(part.data_ptr<float>(), dw.data_ptr(), (int)nparts, (int)D, dt_code(weight.scalar_type()),
-                                     cur_stream(g)),
-             "headnorm_dw", "shape");
-  return dw;
-}
-
-// ---- attention sinks (csrc/sink.hip) ----
-// sinks (H,): fp32, bf16 or fp16 on the launch's device (an fp32 master parameter beside 16-bit tensors)
-void sink_param(const at::Tensor& sinks, int64_t H, const at::Device& dev, const char* op) {
-  TORCH_CHECK(sinks.is_cuda() && sinks.device() == dev && sinks.dim() == 1 && sinks.size(0) == H && sinks.is_contiguous() &&
-                  (sinks.scalar_type() == at::kFloat || sinks.scalar_type() == at::kBFloat16 ||
-                   sinks.scalar_type() == at::kHalf),
-              "xdot.", op, ": sinks must be a contiguous (H,) = (", H, ",) fp32 / bf16 / fp16 tensor on the same GPU");
-}
-
-// the fold of one sink logit per head into a finished forward, in place: lse' = logaddexp(lse, s_h),
-// out' = sigmoid(lse - s_h) * out.  out: (B, R, H*D) with unit inner stride and 16-byte aligned
-// rows (row / batch strides allowed), lse: contiguous fp32 (B, H, R)
-void sink_fold(at::Tensor& out, at::Tensor& lse, const at::Tensor& sinks, int64_t H) {
-  Range rr_("xdot.sink_fold");
-  TORCH_CHECK(out.is_cuda() && out.dim() == 3, "xdot.sink_fold: out must be a (B, R, H*D) GPU tensor");
-  TORCH_CHECK(out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kHalf || out.scalar_type() == at::kFloat,
-              "xdot.sink_fold: bf16/fp16/fp32 only");
-  const int64_t B = out.size(0), R = out.size(1), C = out.size(2);
-  TORCH_CHECK(H > 0 && C > 0 && C % H == 0, "xdot.sink_fold: H*D features, got C=", C, " H=", H);
-  const int64_t D = C / H;
-  TORCH_CHECK(D >= 32 && D <= 384 && D % 8 == 0,
-              "xdot.sink_fold: the head dim must be one the flash paths produce (32..384 in steps of 8), got ", D);
-  TORCH_CHECK(B < (1LL << 31) && R < (1LL << 31) && C < (1LL << 31), "xdot.sink_fold: too large");
-  sink_param(sinks, H, out.device(), "sink_fold");
-  TORCH_CHECK(lse.dim() == 3 && lse.size(0) == B && lse.size(1) == H && lse.size(2) == R,
-              "xdot.sink_fold: lse must be (B, H, R) = (", B, ", ", H, ", ", R, ")");
-  check_bhr(lse, B, H, R, out.device(), "xdot.sink_fold: lse must be a contiguous fp32 tensor on the same GPU");
-  if (out.numel() == 0) return;
-  const int64_t V = 16 / (int64_t)out.element_size();
-  TORCH_CHECK(out.stride(2) == 1, "xdot.sink_fold: the last dimension must have stride 1");
-  const int64_t sb = B > 1 ? out.stride(0) : 0, sr = R > 1 ? out.stride(1) : 0;
-  TORCH_CHECK(sb >= 0 && sr >= 0, "xdot.sink_fold: negative strides");
-  // (every (b, row) is written: two of them may not share memory)
-  TORCH_CHECK((R == 1 || sr >= C) && (B == 1 || sb >= (R - 1) * sr + C), "xdot.sink_fold: the rows of out overlap");
-  TORCH_CHECK((B - 1) * sb + (R - 1) * sr + C <= avail_elems(out), "xdot.sink_fold: view out of bounds");
-  TORCH_CHECK(aligned16(out.data_ptr()) && sb % V == 0 && sr % V == 0,
-              "xdot.sink_fold: out and its row / batch strides must be 16-byte aligned");
-  xdot::SinkArgs a{};
-  a.out = out.data_ptr(); a.lse = lse.data_ptr<float>(); a.sinks = sinks.data_ptr();
-  a.s_dt = dt_code(sinks.scalar_type());
-  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D;
-  a.os_b = sb; a.os_r = sr;
-  c10::DeviceGuard guard(out.device());
-  launched(xdot_sink_fold_launch(&a, dt_code(out.scalar_type()), cur_stream(out)), "sink_fold", "shape");
-}
-
-// ds (H,) fp32 = -sum_{b, r} exp(s_h - lse'[b, h, r]) * delta[b, h, r] from the folded lse' and the
-// delta of the folded output: per-workgroup partials, then their ordered sum (two launches, no atomics)
-at::Tensor sink_grad(const at::Tensor& delta, const at::Tensor& lse, const at::Tensor& sinks) {
-  Range rr_("xdot.sink_grad");
-  TORCH_CHECK(lse.is_cuda() && lse.dim() == 3 && delta.dim() == 3 && delta.sizes() == lse.sizes(),
-              "xdot.sink_grad: delta and lse must be (B, H, R) GPU tensors");
-  const int64_t B = lse.size(0), H = lse.size(1), R = lse.size(2);
-  TORCH_CHECK(H > 0 && H <= 65535 && B < (1LL << 31) && R < (1LL << 31), "xdot.sink_grad: shape");
-  check_bhr(lse, B, H, R, lse.device(), "xdot.sink_grad: lse must be contiguous fp32");
-  check_bhr(delta, B, H, R, lse.device(), "xdot.sink_grad: delta must be contiguous fp32 on the same GPU");
-  sink_param(sinks, H, lse.device(), "sink_grad");
-  auto ds = at::empty({H}, lse.options());
-  if (B * R == 0) return ds.zero_();
-  const int nparts = xdot_sink_grad_parts((int)B, (int)R);
-  TORCH_CHECK(nparts > 0, "xdot.sink_grad: too large");
-  auto part = at::empty({H, (int64_t)nparts}, lse.options());
-  xdot::SinkGradArgs a{};
-  a.delta = delta.data_ptr<float>(); a.lse = lse.data_ptr<float>(); a.sinks = sinks.data_ptr();
-  a.part = part.data_ptr<float>(); a.ds = ds.data_ptr<float>();
-  a.s_dt = dt_code(sinks.scalar_type());
-  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.nparts = nparts;
-  c10::DeviceGuard guard(lse.device());
-  launched(xdot_sink_grad_launch(&a, cur_stream(lse)), "sink_grad", "shape");
-  return ds;
-}
-
-// ---- gated attention (csrc/gate.hip) ----
-// one (B, R, C) operand of the gate kernels: unit inner stride, non-negative row / batch strides,
-// inside its storage; -> (batch stride, row stride) in elements, 0 for a dimension of size 1
-struct GateView { int64_t sb, sr; bool vec; };
-GateView gate_view(const at::Tensor& t, int64_t B, int64_t R, int64_t C, const at::Tensor& like, bool written,
-                   const char* op, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == like.scalar_type() && t.dim() == 3 &&
-                  t.size(0) == B && t.size(1) == R && t.size(2) == C,
-              "xdot.", op, ": ", name, " must be a (", B, ", ", R, ", ", C, ") tensor of o's dtype on the same GPU");
-  if (t.numel() == 0) return {0, 0, true};
-  TORCH_CHECK(C == 1 || t.stride(2) == 1, "xdot.", op, ": the last dimension of ", name, " must have stride 1");
-  const int64_t sb = B > 1 ? t.stride(0) : 0, sr = R > 1 ? t.stride(1) : 0;
-  TORCH_CHECK(sb >= 0 && sr >= 0, "xdot.", op, ": negative strides in ", name);
-  if (written)  // (every (b, row) is written: two of them may not share memory)
-    TORCH_CHECK((R == 1 || sr >= C) && (B == 1 || sb >= (R - 1) * sr + C), "xdot.", op, ": the rows of ", name, " overlap");
-  TORCH_CHECK((B - 1) * sb + (R - 1) * sr + C <= avail_elems(t), "xdot.", op, ": view ", name, " out of bounds");
-  const int64_t V = 16 / (int64_t)t.element_size();
-  return {sb, sr, aligned16(t.data_ptr()) && sb % V == 0 && sr % V == 0};
-}
-
-// the bytes [lo, hi) a (B, R, C) view with these strides spans
-struct GateSpan { uintptr_t lo, hi; };
-GateSpan gate_span(const at::Tensor& t, const GateView& v) {
-  const uintptr_t lo = reinterpret_cast<uintptr_t>(t.data_ptr());
-  if (t.numel() == 0) return {lo, lo};
-  const int64_t n = (t.size(0) - 1) * v.sb + (t.size(1) - 1) * v.sr + t.size(2);
-  return {lo, lo + (uintptr_t)n * t.element_size()};
-}
-bool gate_disjoint(const GateSpan& a, const GateSpan& b) { return a.hi <= b.lo || b.hi <= a.lo; }
-
-// 16-byte lane steps?  mode -1: where D, the pointers and the strides allow; 0: never (one element per
-// step); 1: asked for -- the views must be aligned (checked here), D % V is left to the launcher
-int gate_vec(int64_t mode, bool aligned, int64_t D, int64_t V, const char* op) {
-  TORCH_CHECK(mode >= -1 && mode <= 1, "xdot.", op, ": mode must be -1 (auto), 0 (scalar) or 1 (vector)");
-  if (mode == 0) return 0;
-  if (mode == 1) {
-    TORCH_CHECK(aligned, "xdot.", op, ": vector mode needs 16-byte aligned views and strides");
-    return 1;
-  }
-  return aligned && D % V == 0;
-}
-
-int64_t gate_dims(const at::Tensor& o, const at::Tensor& g, int64_t H, const char* op, bool& headwise) {
-  TORCH_CHECK(o.is_cuda() && o.dim() == 3, "xdot.", op, ": o must be a (B, R, H*D) GPU tensor");
-  TORCH_CHECK(o.scalar_type() == at::kBFloat16 || o.scalar_type() == at::kHalf || o.scalar_type() == at::kFloat,
-              "xdot.", op, ": bf16/fp16/fp32 only");
-  const int64_t C = o.size(2);
-  TORCH_CHECK(H > 0 && C > 0 && C % H == 0, "xdot.", op, ": H*D features, got C=", C, " H=", H);
-  TORCH_CHECK(o.size(0) < (1LL << 31) && o.size(1) < (1LL << 31) && C < (1LL << 31), "xdot.", op, ": too large");
-  TORCH_CHECK(g.dim() == 3 && (g.size(2) == C || g.size(2) == H), "xdot.", op, ": g must be (B, R, ", C, ") or (B, R, ", H, ")");
-  headwise = g.size(2) != C;  // (D = 1: both kinds are the same thing; elementwise it is)
-  return C / H;
-}
-
-// o' = o * sigmoid(g) into out (out of place: out may not share memory with o or g)
-void gate_apply(const at::Tensor& o, const at::Tensor& g, int64_t H, at::Tensor& out, int64_t mode) {
-  Range rr_("xdot.gate_apply");
-  bool hw = false;
-  const int64_t D = gate_dims(o, g, H, "gate_apply", hw);
-  const int64_t B = o.size(0), R = o.size(1), C = o.size(2);
-  const GateView vo = gate_view(o, B, R, C, o, false, "gate_apply", "o");
-  const GateView vg = gate_view(g, B, R, hw ? H : C, o, false, "gate_apply", "g");
-  const GateView vy = gate_view(out, B, R, C, o, true, "gate_apply", "out");
-  if (o.numel() == 0) return;
-  TORCH_CHECK(gate_disjoint(gate_span(out, vy), gate_span(o, vo)) && gate_disjoint(gate_span(out, vy), gate_span(g, vg)),
-              "xdot.gate_apply: out may not share memory with o or g (out of place)");
-  const int64_t V = 16 / (int64_t)o.element_size();
-  const int vec = gate_vec(mode, vo.vec && vy.vec && (hw || vg.vec), D, V, "gate_apply");
-  xdot::GateArgs a{};
-  a.o = o.data_ptr(); a.g = g.data_ptr(); a.y = out.data_ptr();
-  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D; a.headwise = hw ? 1 : 0;
-  a.os_b = vo.sb; a.os_r = vo.sr; a.gs_b = vg.sb; a.gs_r = vg.sr; a.ys_b = vy.sb; a.ys_r = vy.sr;
-  c10::DeviceGuard guard(o.device());
-  launched(xdot_gate_apply_launch(&a, dt_code(o.scalar_type()), vec, cur_stream(o)), "gate_apply", "shape");
-}
-
-// do = dy * sigmoid(g) into dout (which may be dy itself) and dg -> a new contiguous tensor shaped like g
-at::Tensor gate_backward(const at::Tensor& dy, const at::Tensor& o, const at::Tensor& g, int64_t H, at::Tensor& dout,
-                         int64_t mode) {
-  Range rr_("xdot.gate_backward");
-  bool hw = false;
-  const int64_t D = gate_dims(o, g, H, "gate_backward", hw);
-  const int64_t B = o.size(0), R = o.size(1), C = o.size(2);
-  const GateView vo = gate_view(o, B, R, C, o, false, "gate_backward", "o");
-  const GateView vg = gate_view(g, B, R, hw ? H : C, o, false, "gate_backward", "g");
-  const GateView vd = gate_view(dy, B, R, C, o, false, "gate_backward", "dy");
-  const GateView vy = gate_view(dout, B, R, C, o, true, "gate_backward", "dout");
-  auto dg = at::empty({B, R, hw ? H : C}, o.options());
-  if (o.numel() == 0) return dg;
-  TORCH_CHECK(gate_disjoint(gate_span(dout, vy), gate_span(o, vo)) && gate_disjoint(gate_span(dout, vy), gate_span(g, vg)),
-              "xdot.gate_backward: dout may not share memory with o or g");
-  // (every element of do is written by the lane that read that element of dy: dy itself, or apart)
-  TORCH_CHECK((dout.data_ptr() == dy.data_ptr() && vy.sb == vd.sb && vy.sr == vd.sr) ||
-                  gate_disjoint(gate_span(dout, vy), gate_span(dy, vd)),
-              "xdot.gate_backward: dout must be dy itself (same strides) or share no memory with it");
-  const int64_t V = 16 / (int64_t)o.element_size();
-  const int vec = gate_vec(mode, vo.vec && vy.vec && vd.vec && (hw || vg.vec), D, V, "gate_backward");
-  xdot::GateArgs a{};
-  a.o = o.data_ptr(); a.g = g.data_ptr(); a.dy = dy.data_ptr(); a.y = dout.data_ptr(); a.dg = dg.data_ptr();
-  a.B = (int)B; a.R = (int)R; a.H = (int)H; a.D = (int)D; a.headwise = hw ? 1 : 0;
-  a.os_b = vo.sb; a.os_r = vo.sr; a.gs_b = vg.sb; a.gs_r = vg.sr; a.ys_b = vy.sb; a.ys_r = vy.sr;
-  a.ds_b = vd.sb; a.ds_r = vd.sr;
-  c10::DeviceGuard guard(o.device());
-  launched(xdot_gate_backward_launch(&a, dt_code(o.scalar_type()), vec, cur_stream(o)), "gate_backward", "shape");
-  return dg;
-}
-
 // δ = rowsum(dO ⊙ O) per (b, h, row), fp32 (B, H, R)
 at::Tensor flash_bwd_delta(const at::Tensor& dout, const at::Tensor& out, int64_t H) {
   Range rr_("xdot.flash_bwd_delta");
@@ -956,7 +544,6 @@ TORCH_LIBRARY_IMPL(xdot, CompositeExplicitAutograd, m) {
   m.impl("flash_splits", &flash_splits);
   m.impl("flash_fwd_plan", &flash_fwd_plan);
   m.impl("flash_cols_plan", &flash_cols_plan);
-  m.impl("headnorm_plan", &headnorm_plan);
 }
 
 TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
@@ -968,14 +555,6 @@ TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("sum_partials", &sum_partials);
   m.impl("sum_partials_into", &sum_partials_into);
   m.impl("flash_prescale", &flash_prescale);
-  m.impl("rope_table", &rope_table);
-  m.impl("rope_apply", &rope_apply);
-  m.impl("headnorm_fwd", &headnorm_fwd);
-  m.impl("headnorm_bwd", &headnorm_bwd);
-  m.impl("sink_fold", &sink_fold);
-  m.impl("sink_grad", &sink_grad);
-  m.impl("gate_apply", &gate_apply);
-  m.impl("gate_backward", &gate_backward);
   m.impl("flash_fwd_partial", &flash_fwd_partial);
   m.impl("flash_fwd_combine", &flash_fwd_combine);
   m.impl("flash_fwd_merge", &flash_fwd_merge);

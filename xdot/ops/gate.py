@@ -29,6 +29,7 @@ import torch
 from torch import Tensor
 
 from .. import _ext
+from ._rowview import split_heads, unit_inner
 
 __all__ = ["sigmoid_gate", "gate_apply", "gate_backward"]
 
@@ -36,21 +37,12 @@ _HIP_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
 
 
 def _dims(o: Tensor, g: Tensor, heads: int, what: str) -> Tuple[int, int, int, int, bool]:
-    if o.dim() != 3:
-        raise ValueError(f"{what} expects o of shape (B, R, H*D), got {tuple(o.shape)}")
-    B, R, C = o.shape
-    H = int(heads)
-    if H < 1 or C < 1 or C % H:
-        raise ValueError(f"{what}: {C} features do not split over {H} heads")
+    B, R, C, H, _D = split_heads(o, heads, what)
     if g.dim() != 3 or tuple(g.shape[:2]) != (B, R) or g.shape[2] not in (C, H):
         raise ValueError(f"{what}: g must be ({B}, {R}, {C}) or ({B}, {R}, {H}), got {tuple(g.shape)}")
     if g.dtype != o.dtype or g.device != o.device:
         raise ValueError(f"{what}: g must have o's dtype and device, got {g.dtype} on {g.device}")
     return B, R, C, H, g.shape[2] != C
-
-
-def _unit_stride(t: Tensor) -> Tensor:
-    return t if t.shape[-1] == 1 or t.stride(-1) == 1 else t.contiguous()
 
 
 def _sigmoid_parts(g: Tensor):
@@ -76,7 +68,7 @@ def gate_apply(o: Tensor, g: Tensor, heads: int, out: Optional[Tensor] = None, v
     if _ext.use_hip(o) and o.dtype in _HIP_DTYPES:
         if out is None:
             out = torch.empty((B, R, C), dtype=o.dtype, device=o.device)
-        _ext.ops().gate_apply(_unit_stride(o.detach()), _unit_stride(g.detach()), H, out, _mode(vec))
+        _ext.ops().gate_apply(unit_inner(o.detach()), unit_inner(g.detach()), H, out, _mode(vec))
         return out
     sig, _ = _sigmoid_parts(g)
     ov = o.detach().to(sig.dtype)
@@ -101,13 +93,10 @@ def gate_backward(dy: Tensor, o: Tensor, g: Tensor, heads: int, out: Optional[Te
     if out is not None and (out.shape != o.shape or out.dtype != o.dtype or out.device != o.device):
         raise ValueError("gate_backward: out must match o in shape, dtype and device")
     if _ext.use_hip(o) and o.dtype in _HIP_DTYPES:
-        if C > 1 and dy.stride(-1) != 1:
-            if out is dy:
-                raise ValueError("gate_backward: in place needs a unit last stride")
-            dy = dy.contiguous()
+        dy = unit_inner(dy, in_place=out is dy, what="gate_backward")
         if out is None:
             out = torch.empty((B, R, C), dtype=o.dtype, device=o.device)
-        dg = _ext.ops().gate_backward(dy.detach(), _unit_stride(o.detach()), _unit_stride(g.detach()), H, out, _mode(vec))
+        dg = _ext.ops().gate_backward(dy.detach(), unit_inner(o.detach()), unit_inner(g.detach()), H, out, _mode(vec))
         return out, dg
     sig, sp = _sigmoid_parts(g)
     dv, ov = dy.detach().to(sig.dtype), o.detach().to(sig.dtype)

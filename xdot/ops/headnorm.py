@@ -25,6 +25,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _ext
+from ._rowview import rotate_half, split_heads, unit_inner
 from .rope import Rotary, _table_dtype
 
 __all__ = ["HeadRMSNorm", "head_rms_norm", "head_rms_norm_apply", "head_rms_norm_backward", "norm_packed"]
@@ -33,13 +34,7 @@ _HIP_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
 
 
 def _dims(x: Tensor, num_heads: int, weight: Tensor, what: str) -> Tuple[int, int, int, int, int]:
-    if x.dim() != 3:
-        raise ValueError(f"{what} expects (B, R, H*D), got {tuple(x.shape)}")
-    B, R, C = x.shape
-    H = int(num_heads)
-    if H < 1 or C < 1 or C % H:
-        raise ValueError(f"{what}: {C} features do not split over {H} heads")
-    D = C // H
+    B, R, C, H, D = split_heads(x, num_heads, what)
     if tuple(weight.shape) != (D,):
         raise ValueError(f"{what}: weight must have shape ({D},), got {tuple(weight.shape)}")
     return B, R, C, H, D
@@ -63,17 +58,6 @@ def _kernel_weight(weight: Tensor, x: Tensor) -> Tensor:
     return w.contiguous()
 
 
-def _rot(y: Tensor, cos: Tensor, sin: Tensor, inverse: bool) -> Tensor:
-    """Half-split rotation of ``y`` (B, R, H, D) by a (R, D/2) table."""
-    h = y.shape[-1] // 2
-    c = cos.to(y.dtype).view(1, -1, 1, h)
-    s = sin.to(y.dtype).view(1, -1, 1, h)
-    if inverse:
-        s = -s
-    y1, y2 = y[..., :h], y[..., h:]
-    return torch.cat([y1 * c - y2 * s, y2 * c + y1 * s], dim=-1)
-
-
 def head_rms_norm_apply(x: Tensor, num_heads: int, weight: Tensor, eps: float = 1e-6, cos: Optional[Tensor] = None,
                         sin: Optional[Tensor] = None, alpha: float = 1.0, out: Optional[Tensor] = None,
                         save: bool = False) -> Tuple[Tensor, Tensor, Optional[Tensor]]:
@@ -89,10 +73,7 @@ def head_rms_norm_apply(x: Tensor, num_heads: int, weight: Tensor, eps: float = 
     if not float(eps) > 0.0:
         raise ValueError(f"head_rms_norm: eps must be positive, got {eps}")
     if _ext.use_hip(x) and x.dtype in _HIP_DTYPES:
-        if C > 1 and x.stride(-1) != 1:
-            if out is x:
-                raise ValueError("head_rms_norm: in place needs a unit last stride")
-            x = x.contiguous()
+        x = unit_inner(x, in_place=out is x, what="head_rms_norm")
         if out is None:
             out = torch.empty((B, R, C), dtype=x.dtype, device=x.device)
         rstd, saved = _ext.ops().headnorm_fwd(x, _kernel_weight(weight, x), cos, sin, H, float(eps), float(alpha), out,
@@ -104,7 +85,7 @@ def head_rms_norm_apply(x: Tensor, num_heads: int, weight: Tensor, eps: float = 
     rstd = torch.rsqrt(xv.pow(2).mean(dim=-1) + float(eps))
     y = xv * rstd.unsqueeze(-1) * weight.detach().to(cdt)
     if cos is not None:
-        y = _rot(y, cos, sin, False)
+        y = rotate_half(y, cos, sin, False)
     if alpha != 1.0:
         y = y * alpha
     y = y.reshape(B, R, C).to(x.dtype)
@@ -126,12 +107,8 @@ def head_rms_norm_backward(g: Tensor, x: Tensor, rstd: Tensor, num_heads: int, w
     if tuple(x.shape) != (B, R, C) or tuple(rstd.shape) != (B, R, H):
         raise ValueError("head_rms_norm_backward: x must be shaped like g and rstd (B, R, H)")
     if _ext.use_hip(g) and g.dtype in _HIP_DTYPES:
-        if C > 1 and g.stride(-1) != 1:
-            if out is g:
-                raise ValueError("head_rms_norm_backward: in place needs a unit last stride")
-            g = g.contiguous()
-        if C > 1 and x.stride(-1) != 1:
-            x = x.contiguous()
+        g = unit_inner(g, in_place=out is g, what="head_rms_norm_backward")
+        x = unit_inner(x)
         if out is None:
             out = torch.empty((B, R, C), dtype=g.dtype, device=g.device)
         w = _kernel_weight(weight, g)
@@ -142,7 +119,7 @@ def head_rms_norm_backward(g: Tensor, x: Tensor, rstd: Tensor, num_heads: int, w
     cdt = _table_dtype(g)
     gy = g.reshape(B, R, H, D).to(cdt)
     if cos is not None:
-        gy = _rot(gy, cos, sin, True)
+        gy = rotate_half(gy, cos, sin, True)
     if alpha != 1.0:
         gy = gy * alpha
     r = rstd.to(cdt).unsqueeze(-1)

@@ -24,6 +24,7 @@ import torch
 from torch import Tensor
 
 from .. import _ext
+from ._rowview import rotate_half, split_heads, unit_inner
 
 __all__ = ["Rotary", "rope", "rope_apply", "rope_packed"]
 
@@ -145,32 +146,16 @@ def rope_apply(x: Tensor, num_heads: int, cos: Tensor, sin: Tensor, inverse: boo
     ``(B, R, H*D)``; ``out`` may be ``x`` (in place), another tensor, or None (a new contiguous
     one).  GPU bf16 / fp16 / fp32 tensors with unit last stride run ``csrc/rope.hip`` on the view
     as it is (any row / batch strides); everything else is the torch reference math."""
-    if x.dim() != 3:
-        raise ValueError(f"rope expects (B, R, H*D), got {tuple(x.shape)}")
-    B, R, C = x.shape
-    H = int(num_heads)
-    if H < 1 or C % H or (C // H) % 2:
-        raise ValueError(f"rope: {C} features over {H} heads is not an even head dim")
-    h = C // H // 2
-    if tuple(cos.shape) != (R, h) or tuple(sin.shape) != (R, h):
-        raise ValueError(f"rope: table {tuple(cos.shape)} does not fit (R, D/2) = ({R}, {h})")
+    B, R, C, H, D = split_heads(x, num_heads, "rope", even=True)
+    if cos.shape != (R, D // 2) or sin.shape != (R, D // 2):
+        raise ValueError(f"rope: table {tuple(cos.shape)} does not fit (R, D/2) = ({R}, {D // 2})")
     if _ext.use_hip(x) and x.dtype in _HIP_DTYPES:
-        if C > 1 and x.stride(-1) != 1:
-            if out is x:
-                raise ValueError("rope: in place needs a unit last stride")
-            x = x.contiguous()
+        x = unit_inner(x, in_place=out is x, what="rope")
         if out is None:
             out = torch.empty((B, R, C), dtype=x.dtype, device=x.device)
         _ext.ops().rope_apply(x, cos, sin, H, bool(inverse), float(alpha), out)
         return out
-    cdt = _table_dtype(x)
-    xv = x.reshape(B, R, H, 2 * h).to(cdt)
-    x1, x2 = xv[..., :h], xv[..., h:]
-    c = cos.to(cdt).view(1, R, 1, h)
-    s = sin.to(cdt).view(1, R, 1, h)
-    if inverse:
-        s = -s
-    o = torch.cat([x1 * c - x2 * s, x2 * c + x1 * s], dim=-1)
+    o = rotate_half(x.reshape(B, R, H, D).to(_table_dtype(x)), cos, sin, inverse)
     if alpha != 1.0:
         o = o * alpha
     o = o.reshape(B, R, C).to(x.dtype)
@@ -226,14 +211,10 @@ def rope(x: Tensor, num_heads: int, rotary: Rotary, *, offset=None, inverse: boo
     buffer); ``out=x`` rotates in place."""
     if not isinstance(rotary, Rotary):
         raise TypeError(f"rope: rotary must be an xdot.Rotary, got {type(rotary).__name__}")
-    if x.dim() != 3:
-        raise ValueError(f"rope expects (B, R, H*D), got {tuple(x.shape)}")
-    H = int(num_heads)
-    if H < 1 or x.shape[-1] % H or (x.shape[-1] // H) % 2:
-        raise ValueError(f"rope: {x.shape[-1]} features over {H} heads is not an even head dim")
+    _B, R, _C, H, D = split_heads(x, num_heads, "rope", even=True)
     if offset is None:
         offset = rotary.offset if rotary.offset is not None else 0
-    cos, sin = rotary.table(x.shape[1], x.shape[-1] // H, offset, x.device, _table_dtype(x))
+    cos, sin = rotary.table(R, D, offset, x.device, _table_dtype(x))
     if out is not None and (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device):
         raise ValueError("rope: out must match x in shape, dtype and device")
     mode = 0 if out is None else (1 if out is x else 2)
