@@ -1,5 +1,5 @@
 """fp64 definition, rounding model and torch emulation of the gated-attention kernels
-(``csrc/gate.hip``), and the dense module reference with a gate.
+(``csrc/gate.hip``); the definition and the dense module reference are ``tests/_module_ref.py``'s.
 
 Definition (Qiu et al. 2025): a sigmoid gate on the merged attention output, before the output
 projection; ``g`` comes from the row-side input:
@@ -47,61 +47,11 @@ import torch
 import torch.nn.functional as Fn
 
 from _sink_ref import BF16, DT_IDS, EPS_OUT, F, F32, F64, FP16, NINF, TINY, U32, E_EXP, _abs_err, check, ratio  # noqa: F401
-from _sink_ref import definition as sink_definition
+from _module_ref import dense_attn, dense_run, gate  # noqa: F401  (the definition)
 
 SUB = 2.0 ** -125   # absolute error of a value below the fp32 normal range (see the docstring)
 INF = float("inf")
 PLANTED_G = (0.0, 30.0, -30.0, 100.0, -100.0, INF, -INF)
-
-
-# ---- the definition -------------------------------------------------------------------------------------------
-def gate(o, g, H):
-    """``o . sigmoid(g)`` for o (B, R, H D) and g (B, R, H D) or (B, R, H); differentiable."""
-    B, R, C = o.shape
-    s = torch.sigmoid(g)
-    if g.shape[-1] == C:
-        return o * s
-    return (o.reshape(B, R, H, C // H) * s.unsqueeze(-1)).reshape(B, R, C)
-
-
-def _head_norm(t, heads, w, eps):
-    B, R, C = t.shape
-    v = t.view(B, R, heads, C // heads)
-    return (v * torch.rsqrt(v.pow(2).mean(-1, keepdim=True) + eps) * w).reshape(B, R, C)
-
-
-def dense_attn(params, xk, xq, xv, mask, H, Hg=None, rope=False, eps=1e-6):
-    """The module by the definition: projections, QK-norm where the gains are among ``params``,
-    tests/_rope_ref.py's rotation at positions 0..T-1 with ``rope``, the dense attention (with
-    ``params['sinks']`` where present), the gate from the ROW-side input ``xk`` where
-    ``params['gate.weight']`` is present, composition."""
-    Hg = Hg or H
-    k = Fn.linear(xk, params["keys.weight"], params.get("keys.bias"))
-    q = Fn.linear(xq, params["queries.weight"], params.get("queries.bias"))
-    v = Fn.linear(xv, params["values.weight"], params.get("values.bias"))
-    if "keys_norm.weight" in params:
-        k = _head_norm(k, H, params["keys_norm.weight"], eps)
-        q = _head_norm(q, Hg, params["queries_norm.weight"], eps)
-    if rope:
-        from _rope_ref import rotate
-
-        k, q = rotate(k, H, 10000.0), rotate(q, Hg, 10000.0)
-    D = k.shape[-1] // H
-    sinks = params["sinks"] if "sinks" in params else torch.full((H,), NINF, dtype=k.dtype, device=k.device)
-    o = sink_definition(k, q, v, mask, H, 1.0 / math.sqrt(D), sinks, Hg)
-    if "gate.weight" in params:
-        o = gate(o, Fn.linear(xk, params["gate.weight"], params.get("gate.bias")), H)
-    return Fn.linear(o, params["composition.weight"], params.get("composition.bias"))
-
-
-def dense_run(module, x, mask, rope=False):
-    """Forward and backward (loss = mean of squares) of :func:`dense_attn` in fp64 on copies of
-    ``module``'s parameters and of the self-attention input ``x`` -> ``(out, dx, {name: grad})``."""
-    params = {n: p.detach().double().clone().requires_grad_(True) for n, p in module.named_parameters()}
-    xd = x.detach().double().clone().requires_grad_(True)
-    out = dense_attn(params, xd, xd, xd, mask, module.num_heads, module.num_gathered_heads, rope)
-    out.pow(2).mean().backward()
-    return out.detach(), xd.grad, {n: p.grad for n, p in params.items()}
 
 
 def rank_run(module, x_local, peers_qv, rank, mask_rows):

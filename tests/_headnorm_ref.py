@@ -1,5 +1,5 @@
 """fp64 references, a rounding model and a torch emulation of the per-head RMSNorm kernels
-(``csrc/headnorm.hip``), and the dense module reference with QK-norm.
+(``csrc/headnorm.hip``); the dense module reference is ``tests/_module_ref.py``'s.
 
     r = rsqrt(mean_j x[j]^2 + eps),  y = x r w,  out = alpha rotate(y)
     gy = alpha rotate^-1(g),  xh = x r,  gw = gy w,  dx = r (gw - xh mean(gw xh)),  dw = sum gy xh
@@ -40,7 +40,8 @@ Not collected as a test (no ``test_`` prefix).
 import math
 
 import torch
-import torch.nn.functional as Fn
+
+from _module_ref import dense_attn, dense_run, head_norm  # noqa: F401  (the dense module reference)
 
 F32, BF16, FP16, F64 = torch.float32, torch.bfloat16, torch.float16, torch.float64
 DT_IDS = {F32: "fp32", BF16: "bf16", FP16: "fp16"}
@@ -307,47 +308,3 @@ def emulate_backward(g, x, rstd, H, w, offset=None, alpha=1.0, bug=None):
     return dx, dw.to(w.dtype)
 
 
-# ---- dense module reference ---------------------------------------------------------------------------------
-def head_norm(x, H, w, eps):
-    """Per-head RMSNorm of ``x`` (B, T, H*D) in ``x``'s dtype, plain torch ops."""
-    B, T, C = x.shape
-    xv = x.reshape(B, T, H, C // H)
-    return (xv * torch.rsqrt(xv.pow(2).mean(-1, keepdim=True) + eps) * w).reshape(B, T, C)
-
-
-def dense_attn(params, xk, xq, xv, mask, H, Hg=None, eps=1e-6, rope=True, base=10000.0):
-    """tests/_rope_ref.py's dense attention with the norm between the projections and the rotation
-    (``params`` holding ``keys_norm.weight`` / ``queries_norm.weight``; without them: no norm) and
-    grouped gathered heads (``Hg``)."""
-    from _rope_ref import rotate
-
-    Hg = Hg or H
-    k = Fn.linear(xk, params["keys.weight"], params.get("keys.bias"))
-    q = Fn.linear(xq, params["queries.weight"], params.get("queries.bias"))
-    v = Fn.linear(xv, params["values.weight"], params.get("values.bias"))
-    if "keys_norm.weight" in params:
-        k = head_norm(k, H, params["keys_norm.weight"], eps)
-        q = head_norm(q, Hg, params["queries_norm.weight"], eps)
-    if rope:
-        k, q = rotate(k, H, base), rotate(q, Hg, base)
-    B, T, C = k.shape
-    D = C // H
-    kh = k.view(B, T, H, D).transpose(1, 2)
-    qh = q.view(B, T, Hg, D).transpose(1, 2).repeat_interleave(H // Hg, dim=1)
-    vh = v.view(B, T, Hg, -1).transpose(1, 2).repeat_interleave(H // Hg, dim=1)
-    s = torch.matmul(kh, qh.transpose(-1, -2)) / math.sqrt(D)
-    if mask is not None:
-        s = s.masked_fill(mask.view(B, 1, T, T), float("-inf"))
-    o = torch.matmul(torch.softmax(s, dim=-1), vh).transpose(1, 2).reshape(B, T, -1)
-    return Fn.linear(o, params["composition.weight"], params.get("composition.bias"))
-
-
-def dense_run(module, x, mask, rope=True, base=10000.0):
-    """Forward and backward (loss = mean of squares) of :func:`dense_attn` in fp64 on copies of
-    ``module``'s parameters and of the self-attention input ``x`` -> ``(out, dx, {name: grad})``."""
-    params = {n: p.detach().double().clone().requires_grad_(True) for n, p in module.named_parameters()}
-    xd = x.detach().double().clone().requires_grad_(True)
-    out = dense_attn(params, xd, xd, xd, mask, module.num_heads, module.num_gathered_heads,
-                     getattr(module, "qk_norm_eps", 1e-6), rope, base)
-    out.pow(2).mean().backward()
-    return out.detach(), xd.grad, {n: p.grad for n, p in params.items()}

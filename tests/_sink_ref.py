@@ -1,5 +1,5 @@
 """fp64 definition, rounding model and torch emulation of the attention-sink kernels
-(``csrc/sink.hip``), and the dense module reference with sinks.
+(``csrc/sink.hip``); the definition and the dense module reference are ``tests/_module_ref.py``'s.
 
 Definition: one logit ``s_h`` per row head is appended to every row's masked, scaled scores -- it is
 not scaled itself -- takes part in the softmax and contributes no value:
@@ -42,6 +42,8 @@ import math
 import torch
 import torch.nn.functional as Fn
 
+from _module_ref import NINF, attend, definition, dense_attn, dense_run  # noqa: F401  (the definition)
+
 F32, BF16, FP16, F64 = torch.float32, torch.bfloat16, torch.float16, torch.float64
 DT_IDS = {F32: "fp32", BF16: "bf16", FP16: "fp16"}
 F = 2.0
@@ -53,59 +55,6 @@ TINY = {F32: 2.0 ** -125, BF16: 2.0 ** -125, FP16: 2.0 ** -24, F64: 0.0}
 E_EXP = 2.0      # expf: 1 ulp
 E_LOG1P = 4.0    # log1pf: 2 ulp
 CHUNK = 1024     # (b, r) elements of one head per workgroup of the ds kernel: 4 per thread, 256 threads
-NINF = -float("inf")
-
-
-# ---- the definition ---------------------------------------------------------------------------------------
-def attend(scores, sinks, v):
-    """``softmax(cat([scores, s], -1))[..., :T] @ v`` for scores (B, H, R, T) (masked: -inf), sinks
-    (H,), v (B, H, T, d)."""
-    B, H, R, T = scores.shape
-    col = sinks.view(1, H, 1, 1).expand(B, H, R, 1)
-    return torch.matmul(torch.softmax(torch.cat([scores, col], dim=-1), dim=-1)[..., :T], v)
-
-
-def definition(k, q, v, mask, H, scale, sinks, Hg=None):
-    """Attention with sinks by the definition on head-interleaved k (B, R, H D), q / v (B, T, Hg D),
-    mask bool (B, R, T) or None -> (B, R, H Dv); differentiable, in the inputs' dtype."""
-    Hg = Hg or H
-    B, R, C = k.shape
-    T = q.shape[1]
-    kh = k.view(B, R, H, -1).transpose(1, 2)
-    qh = q.view(B, T, Hg, -1).transpose(1, 2).repeat_interleave(H // Hg, dim=1)
-    vh = v.view(B, T, Hg, -1).transpose(1, 2).repeat_interleave(H // Hg, dim=1)
-    s = torch.matmul(kh, qh.transpose(-1, -2)) * scale
-    if mask is not None:
-        s = s.masked_fill(mask.view(B, 1, R, T), NINF)
-    return attend(s, sinks, vh).transpose(1, 2).reshape(B, R, -1)
-
-
-def dense_attn(params, xk, xq, xv, mask, H, Hg=None, rope=False):
-    """The module by the definition (no norm; ``rope``: tests/_rope_ref.py's rotation of k and q at
-    positions 0..T-1): projections, :func:`definition` with ``params['sinks']`` (without the key: a
-    logit of -inf, plain attention), composition."""
-    Hg = Hg or H
-    k = Fn.linear(xk, params["keys.weight"], params.get("keys.bias"))
-    q = Fn.linear(xq, params["queries.weight"], params.get("queries.bias"))
-    v = Fn.linear(xv, params["values.weight"], params.get("values.bias"))
-    if rope:
-        from _rope_ref import rotate
-
-        k, q = rotate(k, H, 10000.0), rotate(q, Hg, 10000.0)
-    D = k.shape[-1] // H
-    sinks = params["sinks"] if "sinks" in params else torch.full((H,), NINF, dtype=k.dtype, device=k.device)
-    o = definition(k, q, v, mask, H, 1.0 / math.sqrt(D), sinks, Hg)
-    return Fn.linear(o, params["composition.weight"], params.get("composition.bias"))
-
-
-def dense_run(module, x, mask, rope=False):
-    """Forward and backward (loss = mean of squares) of :func:`dense_attn` in fp64 on copies of
-    ``module``'s parameters and of the self-attention input ``x`` -> ``(out, dx, {name: grad})``."""
-    params = {n: p.detach().double().clone().requires_grad_(True) for n, p in module.named_parameters()}
-    xd = x.detach().double().clone().requires_grad_(True)
-    out = dense_attn(params, xd, xd, xd, mask, module.num_heads, module.num_gathered_heads, rope)
-    out.pow(2).mean().backward()
-    return out.detach(), xd.grad, {n: p.grad for n, p in params.items()}
 
 
 def sink_scale(k, q, v, mask, H, scale, sinks, dout, Hg=None):

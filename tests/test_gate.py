@@ -300,7 +300,7 @@ def _rank_parity(rank, ws, impl, chunks, kind, mask_kind, rope=False, norm=False
     if rank == 0:
         params = {n: p.detach().clone().requires_grad_(True) for n, p in gt_model.named_parameters()}
         xd = x_full.clone().requires_grad_(True)
-        want = ref.dense_attn(params, xd, xd, xd, dense, H, Hg, rope)
+        want = ref.dense_attn(params, xd, xd, xd, dense, H, Hg, rope=rope)
         want.sum().backward()
         torch.testing.assert_close(gt_out.detach(), want.detach(), atol=tol, rtol=tol)
         torch.testing.assert_close(xg.grad, xd.grad, atol=tol, rtol=tol)

@@ -80,6 +80,39 @@ def test_gradcheck():
     assert torch.autograd.gradcheck(lambda t, g: xdot.head_rms_norm(t, 2, g, 1e-3, out=torch.empty_like(t)), (x, w))
 
 
+@pytest.mark.parametrize("gain", [True, False], ids=["gain", "no_gain"])
+def test_prep_prefix_of_a_packed_tensor(gain):
+    """The one autograd node of ``xdot.ops.qkprep`` on the first 6 of 10 features (a packed
+    ``[q | v]``), with a gain (norm and rotation) and without (the rotation alone): the prefix is
+    what the op gives on the prefix alone, the tail is copied bit for bit into a new tensor, and the
+    backward hands the tail's gradient through unchanged."""
+    import xdot
+    from xdot.ops.qkprep import prep
+
+    gen = torch.Generator().manual_seed(6)
+    x = torch.randn(1, 3, 10, dtype=torch.float64, generator=gen).requires_grad_(True)
+    w = (torch.rand(6, dtype=torch.float64, generator=gen) + 0.5).requires_grad_(True) if gain else None
+    g = torch.randn(1, 3, 10, dtype=torch.float64, generator=gen)
+    rot = xdot.Rotary()
+    tab = rot.table(3, 6, 3, x.device, torch.float64)
+    out = prep(x, 6, 1, tab, w, 1e-3, alpha=0.5, bwd_alpha=1.0)
+    assert out.data_ptr() != x.data_ptr() and out.shape == x.shape
+    assert torch.equal(out[..., 6:], x.detach()[..., 6:])
+    xp = x.detach()[..., :6].clone().requires_grad_(True)
+    if gain:
+        wp = w.detach().clone().requires_grad_(True)
+        alone = xdot.head_rms_norm(xp, 1, wp, 1e-3, rotary=rot, offset=3, alpha=0.5)
+    else:
+        alone = xdot.rope(xp, 1, rot, offset=3, alpha=0.5)
+    assert torch.equal(out[..., :6], alone)
+    out.backward(g)
+    assert torch.equal(x.grad[..., 6:], g[..., 6:])
+    alone.backward(2.0 * g[..., :6])  # (bwd_alpha = 1 against the whole op's alpha = 0.5)
+    torch.testing.assert_close(x.grad[..., :6], xp.grad, rtol=1e-12, atol=1e-12)
+    if gain:
+        torch.testing.assert_close(w.grad, wp.grad, rtol=1e-12, atol=1e-12)
+
+
 def test_scale_invariance():
     """With ``eps`` -> 0 the norm forgets the scale of its input."""
     import xdot
@@ -256,7 +289,7 @@ def _rank_parity(rank, ws, impl, chunks, kind, rope, Hg=None, layout="contiguous
     if rank == 0:
         params = {n: p.detach().clone().requires_grad_(True) for n, p in gt_model.named_parameters()}
         xd = x_full.clone().requires_grad_(True)
-        want = ref.dense_attn(params, xd, xd, xd, dense, H, Hg, 1e-5, rope)
+        want = ref.dense_attn(params, xd, xd, xd, dense, H, Hg, rope=rope, eps=1e-5)
         want.sum().backward()
         torch.testing.assert_close(gt_out.detach(), want.detach(), atol=tol, rtol=tol)
         torch.testing.assert_close(xg.grad, xd.grad, atol=tol, rtol=tol)

@@ -151,7 +151,7 @@ def _rank_parity(rank, ws, heads, impl, kind, call, tol=1e-9):
         kd = k_full.clone().requires_grad_(True)
         qd = q_full.clone().requires_grad_(True)
         xk, xq, xv = pick(kd, qd)
-        ref = dense_attn(params, xk, xq, xv, dense, heads)
+        ref = dense_attn(params, xk, xq, xv, dense, heads, rope=True)
         ref.sum().backward()
         torch.testing.assert_close(gt_out.detach(), ref.detach(), atol=tol, rtol=tol)
         torch.testing.assert_close(kg.grad, kd.grad, atol=tol, rtol=tol)
@@ -196,7 +196,7 @@ def test_single_device_vs_dense_reference(impl):
     mask, dense = _make_mask("dense", B, T, g)
     m = xdot.DistributedDotProductAttn(DIM, num_heads=H, distributed=False, impl=impl, rope=xdot.Rotary()).double()
     params = dict(m.named_parameters())
-    ref = dense_attn(params, x, x, x, dense, H)
+    ref = dense_attn(params, x, x, x, dense, H, rope=True)
     torch.testing.assert_close(m(x, x, x, mask), ref, atol=1e-9, rtol=1e-9)
     with torch.no_grad():
         torch.testing.assert_close(m(x, x, x, mask), ref, atol=1e-9, rtol=1e-9)
@@ -211,7 +211,7 @@ def test_single_device_vs_dense_reference(impl):
     m32.load_state_dict({k: v.float() for k, v in m.state_dict().items()})
     p32 = {n: p.double() for n, p in m32.named_parameters()}
     x32 = x.float()
-    ref32 = dense_attn(p32, x32.double(), x32.double(), x32.double(), dense, H)
+    ref32 = dense_attn(p32, x32.double(), x32.double(), x32.double(), dense, H, rope=True)
     out32 = m32(x32, x32, x32, mask)
     assert out32.dtype == torch.float32
     torch.testing.assert_close(out32.double(), ref32, atol=1e-6, rtol=1e-6)

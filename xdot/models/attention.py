@@ -106,10 +106,13 @@ from .. import _ext
 from ..ops.gate import sigmoid_gate
 from ..ops.linear import linear
 from ..ops.mask import StructuredMask
-from ..ops.headnorm import HeadRMSNorm, head_rms_norm, norm_packed
-from ..ops.rope import Rotary, rope as _rope, rope_packed
+from ..ops.headnorm import HeadRMSNorm
+from ..ops.qkprep import prep
+from ..ops.rope import Rotary, _table_dtype
 from ..ops.softmax import scale_mask_softmax
+from ..parallel import attention as pa
 from ..parallel.autograd import FullMultiplication, RightTransposeMultiplication
+from ..parallel.ring import ring_attention_packed
 from ..parallel.layout import check_layout
 from ..utils import comm as _comm
 from ..utils.env import FLAGS
@@ -242,8 +245,6 @@ class DistributedDotProductAttn(nn.Module):
     def _pick_impl(self, x: Tensor) -> str:
         if self.impl != "auto":
             return self.impl
-        from ..parallel import attention as pa
-
         with _ext.backend(self.backend):
             if self.compute_dtype is not None:
                 x = x.to(self.compute_dtype) if x.is_floating_point() else x
@@ -278,115 +279,104 @@ class DistributedDotProductAttn(nn.Module):
         return self._forward_impl(keys, queries, values, attn_mask)
 
     def _forward_impl(self, keys: Tensor, queries: Tensor, values: Tensor, attn_mask: Optional[Tensor]) -> Tensor:
-        scale = 1.0 / math.sqrt(self.dim)
+        """The dispatch.  Every path below is: project, prep ``k`` / ``q`` (:meth:`_prep`), attend,
+        gate, compose."""
+        impl = self._pick_impl(keys)
         lay = self.layout if self.distributed else "contiguous"  # (a world of one: the identity)
-        if self._pick_impl(keys) == "flash":
-            from ..parallel import attention as pa
-            from ..parallel.attention import seq_parallel_attention_packed, start_gather
+        comm = (self.comm or _comm.get_comm()) if self.distributed else _comm.LocalComm()
+        scale = 1.0 / math.sqrt(self.dim)
+        if impl == "ring":
+            return self._ring(keys, queries, values, attn_mask, scale, comm, lay)
+        if impl != "flash":
+            return self._materialized(keys, queries, values, attn_mask, scale, comm, lay)
+        dk, dv = self.dim, self.value_dim // self.num_heads
+        Dp = pa.flash_head_dim(dk, dv) if keys.is_cuda else dk
+        if keys.is_cuda and Dp is not None and (Dp != dk or Dp != dv):
+            return self._flash_padded(keys, queries, values, attn_mask, scale, comm, lay, Dp)
+        if isinstance(attn_mask, Tensor) and attn_mask.is_cuda and attn_mask.dim() == 3 and FLAGS.mask_async \
+                and (lay == "contiguous" or comm.world_size == 1):
+            # pack the mask on a side stream while the projection GEMMs run (its columns as they
+            # are: the gathered side's order only under the contiguous layout)
+            from ..ops import flash
 
-            comm = (self.comm or _comm.get_comm()) if self.distributed else _comm.LocalComm()
-            H, dk, dv = self.num_heads, self.dim, self.value_dim // self.num_heads
-            Hg = self.num_gathered_heads  # (gh: None for the default, what the attention functions take)
-            gh = None if Hg == H else Hg
-            Dp = pa.flash_head_dim(dk, dv) if keys.is_cuda else dk
-            if keys.is_cuda and Dp is not None and (Dp != dk or Dp != dv):
-                # head dims the kernels do not take (or value width != key width): every head
-                # zero-padded to the next kernel dim, same scale 1/sqrt(dk)
-                qv = self._project_qv(queries, values)
-                q, k = qv[..., :Hg * dk], self._proj(self.keys, keys)
-                if self.rope is not None or self.qk_norm:  # at width dk, before the zero padding
-                    off = self._rope_offset(comm, k.shape[1], lay)
-                    q, k = self._norm_rope(q, Hg, False, off), self._norm_rope(k, H, True, off)
-                # (the Hg gathered heads and the H row heads are padded separately)
-                qv = torch.cat([pa.pad_heads(q, Hg, dk, Dp), pa.pad_heads(qv[..., Hg * dk:], Hg, dv, Dp)], dim=-1)
-                k = pa.pad_heads(k, H, dk, Dp)
-                o = seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm, gathered_heads=gh, layout=lay,
-                                                  sinks=self.sinks)
-                return self._proj(self.composition, self._gated(pa.unpad_heads(o, H, dv, Dp), keys))
-            if isinstance(attn_mask, Tensor) and attn_mask.is_cuda and attn_mask.dim() == 3 and FLAGS.mask_async \
-                    and (lay == "contiguous" or comm.world_size == 1):
-                # pack the mask on a side stream while the projection GEMMs run (its columns as they
-                # are: the gathered side's order only under the contiguous layout)
-                from ..ops import flash
+            attn_mask = flash.prepare_mask_async(attn_mask.to(torch.bool), attn_mask.shape[0],
+                                                 attn_mask.shape[1], attn_mask.shape[2])
+        if (FLAGS.fused_module and queries is values and self.queries.in_features == self.values.in_features
+                and (self.compute_dtype is None or self.keys.weight.dtype == self.compute_dtype)):
+            return self._flash_one_node(keys, queries, attn_mask, scale, comm, lay)
+        return self._flash_per_op(keys, queries, values, attn_mask, scale, comm, lay)
 
-                attn_mask = flash.prepare_mask_async(attn_mask.to(torch.bool), attn_mask.shape[0],
-                                                     attn_mask.shape[1], attn_mask.shape[2])
-            if (FLAGS.fused_module and queries is values and self.queries.in_features == self.values.in_features
-                    and (self.compute_dtype is None or self.keys.weight.dtype == self.compute_dtype)):
-                # the whole module as ONE autograd node (xdot.models.fused): same kernels, streams
-                # and numerics, a fraction of the per-op host work
-                from .fused import AttnBlockFn
+    @property
+    def _gh(self) -> Optional[int]:
+        """The gathered heads as the attention functions take them: None for the default."""
+        return None if self.num_gathered_heads == self.num_heads else self.num_gathered_heads
 
-                wq, wv = self.queries.weight, self.values.weight
-                bq, bv = self.queries.bias, self.values.bias
-                if isinstance(wq, nn.Parameter) and isinstance(wv, nn.Parameter):
-                    _stacked_rows(wq, wv)  # (re)pack the two parameters into one storage once
-                    if bq is not None:
-                        _stacked_rows(bq, bv)
-                gs = self._xdot_grad_sync() if self._xdot_grad_sync is not None else None
-                sync = None
-                has_gate = self.gate_kind is not None
-                if gs is not None and torch.is_grad_enabled():
-                    gs.note_use(id(self))
-                    sync = (gs, id(self))
-                return AttnBlockFn.apply(keys, queries, attn_mask, self.keys.weight, self.keys.bias, wq, bq, wv, bv,
-                                         self.composition.weight, self.composition.bias, self.num_heads, scale, comm,
-                                         self.chunk_plan, sync, torch.is_grad_enabled(), self.rope, gh, lay,
-                                         *((self.keys_norm.weight, self.queries_norm.weight, self.qk_norm_eps)
-                                           if self.qk_norm else ((None, None, 1e-6) if self.sinks is not None or has_gate
-                                                                 else ())),
-                                         *((self.sinks,) if self.sinks is not None or has_gate else ()),
-                                         *((self.gate.weight, self.gate.bias) if has_gate else ()))
-            # gathered side first: its all-gather runs while the row-side GEMM computes
-            qv = self._project_qv(queries, values)
-            pre = False
-            off = self._rope_offset(comm, qv.shape[1], lay)
-            if self.qk_norm:  # q normalised and rotated, in one pass, before the gather is issued
-                qv = norm_packed(qv, Hg * dk, Hg, self.queries_norm.weight, self.qk_norm_eps, self.rope, off)
-            elif self.rope is not None:  # q rotated before the gather is issued
-                qv = rope_packed(qv, Hg * dk, Hg, self.rope, off)
-            pending = start_gather(qv, comm, chunks=self.chunk_plan)
-            k = self._proj(self.keys, keys)
-            if self.rope is not None or self.qk_norm:
-                # the row side's pre-scale rides in the rotation / norm pass (its gradient comes back
-                # w.r.t. the unscaled rows: no factor in the backward)
-                pre = pa.prescale_wanted(k, qv, H, gh)
-                al = scale * _LOG2E if pre else 1.0
-                if self.qk_norm:
-                    k = norm_packed(k, H * dk, H, self.keys_norm.weight, self.qk_norm_eps, self.rope, off, alpha=al,
-                                    bwd_alpha=1.0)
-                else:
-                    k = rope_packed(k, H * dk, H, self.rope, off, alpha=al, bwd_alpha=1.0)
-            o = seq_parallel_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm, pending=pending,
-                                              k_prescaled=pre, gathered_heads=gh, layout=lay, sinks=self.sinks)
-            return self._proj(self.composition, self._gated(o, keys))
-        if self._pick_impl(keys) == "ring":
-            from ..parallel.ring import ring_attention_packed
+    def _flash_padded(self, keys, queries, values, attn_mask, scale, comm, lay, Dp):
+        """Head dims the flash kernels do not take (or value width != key width): every head
+        zero-padded to the next kernel dim ``Dp``, same scale ``1/sqrt(dk)``."""
+        H, Hg, dk, dv = self.num_heads, self.num_gathered_heads, self.dim, self.value_dim // self.num_heads
+        qv = self._project_qv(queries, values)
+        q, k = qv[..., :Hg * dk], self._proj(self.keys, keys)
+        off = self._rope_offset(comm, k.shape[1], lay)
+        # at width dk, before the zero padding
+        q, k = self._prep(q, Hg * dk, Hg, False, off), self._prep(k, H * dk, H, True, off)
+        # (the Hg gathered heads and the H row heads are padded separately)
+        qv = torch.cat([pa.pad_heads(q, Hg, dk, Dp), pa.pad_heads(qv[..., Hg * dk:], Hg, dv, Dp)], dim=-1)
+        k = pa.pad_heads(k, H, dk, Dp)
+        o = pa.seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm, gathered_heads=self._gh, layout=lay,
+                                             sinks=self.sinks)
+        return self._proj(self.composition, self._gated(pa.unpad_heads(o, H, dv, Dp), keys))
 
-            comm = (self.comm or _comm.get_comm()) if self.distributed else _comm.LocalComm()
-            qv = self._project_qv(queries, values)
-            k = self._proj(self.keys, keys)
-            off = self._rope_offset(comm, k.shape[1], lay)
-            if self.qk_norm:
-                qv = norm_packed(qv, self.num_gathered_heads * self.dim, self.num_gathered_heads,
-                                 self.queries_norm.weight, self.qk_norm_eps, self.rope, off)
-                k = norm_packed(k, k.shape[-1], self.num_heads, self.keys_norm.weight, self.qk_norm_eps, self.rope, off)
-            elif self.rope is not None:
-                qv = rope_packed(qv, self.num_gathered_heads * self.dim, self.num_gathered_heads, self.rope, off)
-                k = rope_packed(k, k.shape[-1], self.num_heads, self.rope, off)
-            o = ring_attention_packed(k, qv, attn_mask, self.num_heads, scale, comm=comm,
-                                      gathered_heads=None if self.num_gathered_heads == self.num_heads
-                                      else self.num_gathered_heads, layout=lay, sinks=self.sinks)
-            return self._proj(self.composition, self._gated(o, keys))
+    def _flash_one_node(self, keys, queries, attn_mask, scale, comm, lay):
+        """The whole module as ONE autograd node (:mod:`xdot.models.fused`): same kernels, streams
+        and numerics, a fraction of the per-op host work."""
+        from .fused import AttnBlockFn
+
+        wq, wv = self.queries.weight, self.values.weight
+        bq, bv = self.queries.bias, self.values.bias
+        if isinstance(wq, nn.Parameter) and isinstance(wv, nn.Parameter):
+            _stacked_rows(wq, wv)  # (re)pack the two parameters into one storage once
+            if bq is not None:
+                _stacked_rows(bq, bv)
+        gs = self._xdot_grad_sync() if self._xdot_grad_sync is not None else None
+        sync = None
+        if gs is not None and torch.is_grad_enabled():
+            gs.note_use(id(self))
+            sync = (gs, id(self))
+        wkn, wqn = (self.keys_norm.weight, self.queries_norm.weight) if self.qk_norm else (None, None)
+        wg, bg = (self.gate.weight, self.gate.bias) if self.gate_kind is not None else (None, None)
+        return AttnBlockFn.apply(keys, queries, attn_mask, self.keys.weight, self.keys.bias, wq, bq, wv, bv,
+                                 self.composition.weight, self.composition.bias, self.num_heads, scale, comm,
+                                 self.chunk_plan, sync, torch.is_grad_enabled(), self.rope, self._gh, lay,
+                                 wkn, wqn, self.qk_norm_eps, self.sinks, wg, bg)
+
+    def _flash_per_op(self, keys, queries, values, attn_mask, scale, comm, lay):
+        """One autograd node per op.  The gathered side first: its all-gather runs while the
+        row-side GEMM computes."""
+        H, Hg, dk = self.num_heads, self.num_gathered_heads, self.dim
+        qv = self._project_qv(queries, values)
+        off = self._rope_offset(comm, qv.shape[1], lay)
+        qv = self._prep(qv, Hg * dk, Hg, False, off)  # q before the gather is issued
+        pending = pa.start_gather(qv, comm, chunks=self.chunk_plan)
         k = self._proj(self.keys, keys)
-        q = self._proj(self.queries, queries)
-        v = self._proj(self.values, values)
-        if self.rope is not None or self.qk_norm:
-            c = (self.comm or _comm.get_comm()) if self.distributed else _comm.LocalComm()
-            off = self._rope_offset(c, k.shape[1], lay)
-            k = self._norm_rope(k, self.num_heads, True, off)
-            q = self._norm_rope(q, self.num_gathered_heads, False, off)
-        return self._proj(self.composition, self._gated(self._materialized(k, q, v, attn_mask, scale), keys))
+        # the row side's pre-scale rides in the rotation / norm pass (its gradient comes back w.r.t.
+        # the unscaled rows: no factor in the backward)
+        pre = (self.rope is not None or self.qk_norm) and pa.prescale_wanted(k, qv, H, self._gh)
+        k = self._prep(k, H * dk, H, True, off, alpha=scale * _LOG2E if pre else 1.0, bwd_alpha=1.0)
+        o = pa.seq_parallel_attention_packed(k, qv, attn_mask, H, scale, comm=comm, pending=pending, k_prescaled=pre,
+                                             gathered_heads=self._gh, layout=lay, sinks=self.sinks)
+        return self._proj(self.composition, self._gated(o, keys))
+
+    def _ring(self, keys, queries, values, attn_mask, scale, comm, lay):
+        H, Hg = self.num_heads, self.num_gathered_heads
+        qv = self._project_qv(queries, values)
+        k = self._proj(self.keys, keys)
+        off = self._rope_offset(comm, k.shape[1], lay)
+        qv = self._prep(qv, Hg * self.dim, Hg, False, off)
+        k = self._prep(k, k.shape[-1], H, True, off)
+        o = ring_attention_packed(k, qv, attn_mask, H, scale, comm=comm, gathered_heads=self._gh, layout=lay,
+                                  sinks=self.sinks)
+        return self._proj(self.composition, self._gated(o, keys))
 
     def _gated(self, o: Tensor, keys: Tensor) -> Tensor:
         """``o * sigmoid(gate(keys))`` (``o`` itself without a gate): after the attention, sink fold
@@ -399,13 +389,16 @@ class DistributedDotProductAttn(nn.Module):
         """This rank's rotary positions (None without ``rope``)."""
         return None if self.rope is None else self.rope.resolve(comm.rank, R, comm.world_size, lay)
 
-    def _norm_rope(self, t: Tensor, heads: int, row_side: bool, off) -> Tensor:
-        """projection -> norm -> rope of one operand as a tensor of its own (the paths that do not
-        pack ``[q | v]``): one pass where both are set."""
-        if not self.qk_norm:
-            return _rope(t, heads, self.rope, offset=off)
-        norm = self.keys_norm if row_side else self.queries_norm
-        return head_rms_norm(t, heads, norm.weight, self.qk_norm_eps, rotary=self.rope, offset=off)
+    def _prep(self, x: Tensor, ncols: int, heads: int, row_side: bool, off, alpha: float = 1.0,
+              bwd_alpha: Optional[float] = None) -> Tensor:
+        """norm -> rope of the first ``ncols`` features of a projection's output (all of a ``k`` or ``q``; the
+        ``q`` part of a packed ``[q | v]``, whose rest is copied) as one autograd node and one pass; ``x`` itself with
+        neither.  ``row_side``: ``keys_norm``'s gain, else ``queries_norm``'s; ``off``: :meth:`_rope_offset`."""
+        if self.rope is None and not self.qk_norm:
+            return x
+        tab = None if self.rope is None else self.rope.table(x.shape[1], ncols // heads, off, x.device, _table_dtype(x))
+        gain = (self.keys_norm if row_side else self.queries_norm).weight if self.qk_norm else None
+        return prep(x, ncols, heads, tab, gain, self.qk_norm_eps, alpha, bwd_alpha)
 
     def _proj(self, layer: nn.Linear, x: Tensor) -> Tensor:
         """``layer(x)`` (compute dtype) with the split-K MFMA weight gradient (:mod:`xdot.ops.linear`)."""
@@ -424,8 +417,14 @@ class DistributedDotProductAttn(nn.Module):
             return linear(queries, w, b)
         return torch.cat([self._proj(self.queries, queries), self._proj(self.values, values)], dim=-1)
 
-    def _materialized(self, k, q, v, attn_mask, scale):
+    def _materialized(self, keys, queries, values, attn_mask, scale, comm, lay):
         H = self.num_heads
+        k = self._proj(self.keys, keys)
+        q = self._proj(self.queries, queries)
+        v = self._proj(self.values, values)
+        off = self._rope_offset(comm, k.shape[1], lay)
+        k = self._prep(k, k.shape[-1], H, True, off)
+        q = self._prep(q, q.shape[-1], self.num_gathered_heads, False, off)
         B, R = k.shape[0], k.shape[1]
         if H > 1:
             k = k.view(B, R, H, self.dim).transpose(1, 2)
@@ -435,7 +434,6 @@ class DistributedDotProductAttn(nn.Module):
             if Hg != H:  # grouped heads: every gathered head repeated for its group's products
                 q, v = q.repeat_interleave(H // Hg, dim=1), v.repeat_interleave(H // Hg, dim=1)
         if self.distributed:
-            comm = self.comm or _comm.get_comm()
             s = RightTransposeMultiplication.apply(k, q, self.offset, comm)
         else:
             s = torch.matmul(k, q.transpose(-1, -2))
@@ -445,8 +443,7 @@ class DistributedDotProductAttn(nn.Module):
             # layout is not the global order a dense tensor's columns come in
             from ..ops.mask import resolve as resolve_mask
 
-            attn_mask = resolve_mask(attn_mask, B, R, s.shape[-1], comm.rank if self.distributed else 0, False,
-                                     s.device, self.layout if self.distributed else "contiguous")
+            attn_mask = resolve_mask(attn_mask, B, R, s.shape[-1], comm.rank, False, s.device, lay)
         if self.sinks is not None:
             p = self._sink_softmax(s, attn_mask, scale)
         else:
@@ -457,7 +454,7 @@ class DistributedDotProductAttn(nn.Module):
             o = torch.matmul(p, v)
         if H > 1:
             o = o.transpose(1, 2).reshape(B, R, self.value_dim)
-        return o
+        return self._proj(self.composition, self._gated(o, keys))
 
     def _sink_softmax(self, s: Tensor, mask: Optional[Tensor], scale: float) -> Tensor:
         """``softmax([s * scale (masked), sinks])[..., :T]`` in torch (the reference-structured path):

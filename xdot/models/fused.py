@@ -37,13 +37,15 @@ gradients; its input gradient is ADDED to ``dx_k`` (one add pass).
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
+
 import torch
 
 from .. import _ext
 from ..ops.linear import linear_backward, native_wgrad, proj, weight_grad_pair
 from ..ops.gate import gate_apply, gate_backward
-from ..ops.headnorm import head_rms_norm_apply, head_rms_norm_backward
-from ..ops.rope import _table_dtype, rope_apply
+from ..ops.qkprep import prep_apply, prep_backward
+from ..ops.rope import _table_dtype
 from ..utils.env import FLAGS
 from ..utils.streams import _on_stream, _side_stream
 from ..parallel.attention import SeqParallelAttention, gather_plan, prescale_wanted, start_gather
@@ -51,6 +53,12 @@ from ..parallel.attention import SeqParallelAttention, gather_plan, prescale_wan
 _LOG2E = 1.4426950408889634  # as the kernels' scale * log2 e (csrc/flash_common.h, csrc/reduce.hip)
 
 __all__ = ["AttnBlockFn"]
+
+# AttnBlockFn.forward's parameters after ``ctx``, in order (tests/test_fused_args.py holds the two
+# together); the backward reads ``needs_input_grad`` and fills its return through ``_I.<name>``
+ARG_NAMES = ("xk", "xqv", "mask", "wk", "bk", "wq", "bq", "wv", "bv", "wc", "bc", "H", "scale", "comm", "chunk_plan",
+             "sync", "grad_on", "rope", "Hg", "layout", "wkn", "wqn", "norm_eps", "sinks", "wg", "bg")
+_I = SimpleNamespace(**{name: i for i, name in enumerate(ARG_NAMES)})
 
 
 class _Ctx:
@@ -89,12 +97,28 @@ def _ready_on(t, side):
     return side
 
 
+def _prep_backward_dq(dqv, nq, *args, **kw):
+    """:func:`prep_backward` in place on the ``q`` part of ``d[q|v]`` -> ``dw``.  d[q|v] may be handed
+    on with ``_xdot_ready_on`` (its weight gradient then runs on that stream without waiting for the
+    current one): the pass runs on that same stream, and the current stream waits for it."""
+    dq, on = dqv[..., :nq], getattr(dqv, "_xdot_ready_on", None)
+    if on is None:
+        return prep_backward(dq, *args, out=dq, **kw)[1]
+    here = torch.cuda.current_stream(dqv.device)
+    with _on_stream(on, here):
+        dw = prep_backward(dq, *args, out=dq, **kw)[1]
+    here.wait_stream(on)
+    if dw is not None:
+        dw.record_stream(here)
+    return dw
+
+
 class AttnBlockFn(torch.autograd.Function):
     @staticmethod
     @_ext.pinned
-    def forward(ctx, xk, xqv, mask, wk, bk, wq, bq, wv, bv, wc, bc, H, scale, comm, chunk_plan, sync=None,
-                grad_on=True, rope=None, Hg=None, layout="contiguous", wkn=None, wqn=None, norm_eps=1e-6, sinks=None,
-                wg=None, bg=None):
+    def forward(ctx, xk, xqv, mask, wk, bk, wq, bq, wv, bv, wc, bc, H, scale, comm, chunk_plan, sync, grad_on, rope, Hg,
+                layout, wkn, wqn, norm_eps, sinks, wg, bg):
+        # every argument is passed, None for an absent feature: the backward returns one gradient per name
         # Hg: gathered heads when fewer than H (grouped-query attention): wq / wv hold Hg heads
         # layout: the row sharding (xdot.parallel.layout): the rotary positions and the mask follow it
         # wkn / wqn: the (D,) gains of QK-norm on k / q (both or neither), norm_eps its eps
@@ -117,36 +141,28 @@ class AttnBlockFn(torch.autograd.Function):
             qv = proj(xqv, wqv, bqv)
         nq = wq.shape[0]
         tab = None
-        if rope is not None:
-            # q rotated at this rank's global positions, in place and BEFORE the gather is issued
-            # (with the in-place gather this block is what the peers pull); v is untouched
+        if rope is not None:  # this rank's global positions
             tab = rope.table(R, nq // (Hg or H), rope.resolve(comm.rank, R, n, layout), qv.device, _table_dtype(qv))
-            if wqn is None:
-                rope_apply(qv[..., :nq], Hg or H, *tab, out=qv[..., :nq])
         nsaved = ()
         keep = any(ctx.needs_input_grad)  # a backward can run: the norm passes keep their inputs
-        if wqn is not None:
-            # q normalised and rotated in ONE pass, in place in the gather slot, before the gather
-            _, rstd_q, q0 = head_rms_norm_apply(qv[..., :nq], Hg or H, wqn, norm_eps, *(tab or (None, None)),
-                                                out=qv[..., :nq], save=keep)
+        if tab is not None or wqn is not None:
+            # q normalised and / or rotated in ONE pass, in place and BEFORE the gather is issued (with
+            # the in-place gather this block is what the peers pull); v is untouched
+            _, rstd_q, q0 = prep_apply(qv[..., :nq], Hg or H, tab, wqn, norm_eps, out=qv[..., :nq], save=keep)
         pending = start_gather(qv, comm, chunks=chunk_plan, out=gbuf)  # in flight under the row-side GEMM
         # the row side's pre-scale (scale * log2 e) folded into the k projection: one rounding, no
         # separate pass (the attention backward's dk is w.r.t. the unscaled k either way)
         # (the probe reads shape, dtype and device only: a stride-0 view shaped like k)
         k_like = qv[..., :wk.shape[0]] if Hg is None else qv[..., :1].expand(B, R, wk.shape[0])
         pre = xk.shape[-1] == wk.shape[1] and prescale_wanted(k_like, qv, H, Hg)
-        if wkn is not None:
-            # RMSNorm cancels a scalar: the projection runs unscaled and the norm pass carries the
-            # pre-scale (and the rotation)
-            k = proj(xk, wk, bk)
-            _, rstd_k, k0 = head_rms_norm_apply(k, H, wkn, norm_eps, *(tab or (None, None)),
-                                                alpha=scale * _LOG2E if pre else 1.0, out=k, save=keep)
-            if keep:
+        # with a gain RMSNorm cancels a scalar: the projection runs unscaled and the prep pass carries
+        # the pre-scale; without one it sits in the projection (a rotation commutes with a scalar)
+        al = scale * _LOG2E if pre else 1.0
+        k = proj(xk, wk, bk, alpha=1.0 if wkn is not None else al)
+        if tab is not None or wkn is not None:
+            _, rstd_k, k0 = prep_apply(k, H, tab, wkn, norm_eps, alpha=al if wkn is not None else 1.0, out=k, save=keep)
+            if keep and wkn is not None:
                 nsaved = (k0, rstd_k, wkn, q0, rstd_q, wqn)
-        else:
-            k = proj(xk, wk, bk, alpha=scale * _LOG2E if pre else 1.0)
-            if tab is not None:  # the pre-scale sits in the projection: a rotation commutes with a scalar
-                rope_apply(k, H, *tab, out=k)
         # the gate projection beside the k projection: under the all-gather too
         g = proj(xk, wg, bg) if wg is not None else None
         actx = _Ctx()
@@ -199,11 +215,11 @@ class AttnBlockFn(torch.autograd.Function):
                else None) if sync is not None else (lambda *ps: None)
         side = _wgrad_stream(dout)
         if side is None:
-            do, dwc, dbc = linear_backward(dout, oc, wc, True, ng[9], hc and ng[10], dw_dtype=wdt(wc_, bc_))
+            do, dwc, dbc = linear_backward(dout, oc, wc, True, ng[_I.wc], hc and ng[_I.bc], dw_dtype=wdt(wc_, bc_))
         else:
             do, _, _ = linear_backward(dout, oc, wc, True, False, False)
             dout._xdot_ready_on = _ready_on(dout, side)
-            _, dwc, dbc = linear_backward(dout, oc, wc, False, ng[9], hc and ng[10], join=False, dw_dtype=wdt(wc_, bc_))
+            _, dwc, dbc = linear_backward(dout, oc, wc, False, ng[_I.wc], hc and ng[_I.bc], join=False, dw_dtype=wdt(wc_, bc_))
         # the current stream is only looked up when a side stream is in play (host cost per call)
         cur = torch.cuda.current_stream(dout.device) if side is not None else None
         if sync is not None:  # hand the output projection's gradients to GradSync now: their
@@ -215,68 +231,44 @@ class AttnBlockFn(torch.autograd.Function):
             _, dg = gate_backward(do, o, gsaved[1], ctx.H, out=do)
         agrads = SeqParallelAttention.backward(ctx.actx, do)
         dk, dqv, dsk = agrads[0], agrads[1], agrads[-1]  # (dsk: this rank's rows' share of the sinks' gradient)
-        if dsk is not None and not ng[23]:
+        if dsk is not None and not ng[_I.sinks]:
             dsk = None
         if dsk is not None and sync is not None:  # a replicated parameter like the others: summed by GradSync
             sync.deliver([(ctx.sinks, dsk)])
             dsk = None
         dwkn = dwqn = None
-        if nsaved:
-            # QK-norm: gradients w.r.t. the normalised, rotated k / q -> w.r.t. the projections'
-            # outputs, in place, the inverse rotation folded in; on the streams the inverse rotation
-            # alone runs on (below).  The gain gradients are ordered sums (csrc/headnorm.hip)
-            k0, rstd_k, wkn, q0, rstd_q, wqn = nsaved
-            tab = ctx.rope_tab or (None, None)
-            _, dwkn = head_rms_norm_backward(dk, k0, rstd_k, ctx.H, wkn, *tab, out=dk, need_dw=ng[20])
-            dq, on = dqv[..., :ctx.nq], getattr(dqv, "_xdot_ready_on", None)
-            if on is None:
-                _, dwqn = head_rms_norm_backward(dq, q0, rstd_q, ctx.Hg, wqn, *tab, out=dq, need_dw=ng[21])
-            else:
-                here = torch.cuda.current_stream(dqv.device)
-                with _on_stream(on, here):
-                    _, dwqn = head_rms_norm_backward(dq, q0, rstd_q, ctx.Hg, wqn, *tab, out=dq, need_dw=ng[21])
-                here.wait_stream(on)
-                if dwqn is not None:
-                    dwqn.record_stream(here)
-        elif ctx.rope_tab is not None:
-            # gradients w.r.t. the rotated k / q -> w.r.t. the projections' outputs: the inverse
-            # rotation, in place, before anything below reads them.  d[q|v] may be handed on with
-            # ``_xdot_ready_on`` (its weight gradient then runs on that stream without waiting for
-            # this one): it is rotated on that same stream, and this stream waits for it
-            rope_apply(dk, ctx.H, *ctx.rope_tab, inverse=True, out=dk)
-            dq, on = dqv[..., :ctx.nq], getattr(dqv, "_xdot_ready_on", None)
-            if on is None:
-                rope_apply(dq, ctx.Hg, *ctx.rope_tab, inverse=True, out=dq)
-            else:
-                here = torch.cuda.current_stream(dqv.device)
-                with _on_stream(on, here):
-                    rope_apply(dq, ctx.Hg, *ctx.rope_tab, inverse=True, out=dq)
-                here.wait_stream(on)
+        if nsaved or ctx.rope_tab is not None:
+            # gradients w.r.t. the normalised and / or rotated k / q -> w.r.t. the projections'
+            # outputs, in place, before anything below reads them: the inverse rotation, with QK-norm
+            # folded into the norm's backward, whose gain gradients are ordered sums (csrc/headnorm.hip)
+            k0, rstd_k, wkn, q0, rstd_q, wqn = nsaved or (None,) * 6
+            _, dwkn = prep_backward(dk, ctx.H, ctx.rope_tab, wkn, k0, rstd_k, out=dk, need_dw=ng[_I.wkn])
+            dwqn = _prep_backward_dq(dqv, ctx.nq, ctx.Hg, ctx.rope_tab, wqn, q0, rstd_q, need_dw=ng[_I.wqn])
         # the row-side weight gradient also runs beside the input-gradient GEMMs that follow
         # d[q|v] may be ready on the backward's priority stream (``_xdot_ready_on``): its weight
         # gradient runs there, under the row-side kernel (linear_backward)
         qv_on = getattr(dqv, "_xdot_ready_on", None) if native_wgrad(dqv, xqv) else None  # (as linear_backward)
-        need_wk, need_wqv = ng[3], ng[5] or ng[7]
+        need_wk, need_wqv, need_bqv = ng[_I.wk], ng[_I.wq] or ng[_I.wv], hq and (ng[_I.bq] or ng[_I.bv])
         kdt, qvdt = wdt(wk_, bk_), wdt(wq_, bq_, wv_, bv_)
         if side is None and qv_on is None and need_wk and need_wqv:
             # one stream: dWk and dW[q|v] in ONE launch (weight_grad_pair)
-            dxk, _, dbk = linear_backward(dk, xk, wk, ng[0], False, hk and ng[4], dw_dtype=kdt)
-            dxqv, _, dbqv = linear_backward(dqv, xqv, wqv, ng[1], False, hq and (ng[6] or ng[8]), dw_dtype=qvdt)
+            dxk, _, dbk = linear_backward(dk, xk, wk, ng[_I.xk], False, hk and ng[_I.bk], dw_dtype=kdt)
+            dxqv, _, dbqv = linear_backward(dqv, xqv, wqv, ng[_I.xqv], False, need_bqv, dw_dtype=qvdt)
             dwk, dwqv = weight_grad_pair(dk, xk, dqv, xqv, kdt or qvdt or wk.dtype)
         else:
             if side is None:
-                dxk, dwk, dbk = linear_backward(dk, xk, wk, ng[0], need_wk, hk and ng[4], dw_dtype=kdt)
+                dxk, dwk, dbk = linear_backward(dk, xk, wk, ng[_I.xk], need_wk, hk and ng[_I.bk], dw_dtype=kdt)
             else:
                 dk._xdot_ready_on = _ready_on(dk, side)
-                dxk, _, _ = linear_backward(dk, xk, wk, ng[0], False, False)
-                _, dwk, dbk = linear_backward(dk, xk, wk, False, need_wk, hk and ng[4], join=False, dw_dtype=kdt)
-            dxqv, dwqv, dbqv = linear_backward(dqv, xqv, wqv, ng[1], need_wqv, hq and (ng[6] or ng[8]), dw_dtype=qvdt)
+                dxk, _, _ = linear_backward(dk, xk, wk, ng[_I.xk], False, False)
+                _, dwk, dbk = linear_backward(dk, xk, wk, False, need_wk, hk and ng[_I.bk], join=False, dw_dtype=kdt)
+            dxqv, dwqv, dbqv = linear_backward(dqv, xqv, wqv, ng[_I.xqv], need_wqv, need_bqv, dw_dtype=qvdt)
         dwg = dbg = None
         if dg is not None:
             # the gate projection reads the row-side input too: its input gradient is added to dx_k
             # (one add pass), its weight / bias gradients are this rank's partial over its rows
             wg_, bg_ = ctx.gate
-            dxg, dwg, dbg = linear_backward(dg, xk, gsaved[2], ng[0], ng[24], bg_ is not None and ng[25],
+            dxg, dwg, dbg = linear_backward(dg, xk, gsaved[2], ng[_I.xk], ng[_I.wg], bg_ is not None and ng[_I.bg],
                                             dw_dtype=wdt(wg_, bg_))
             if dxg is not None:
                 dxk = dxg if dxk is None else dxk.add_(dxg)
@@ -288,9 +280,9 @@ class AttnBlockFn(torch.autograd.Function):
         # the packed products cover both halves; hand back only what is asked for (a frozen
         # queries weight next to a trained values weight gets None, and is never delivered)
         if dwqv is not None:
-            dwq, dwv = (dwqv[:n] if ng[5] else None), (dwqv[n:] if ng[7] else None)
+            dwq, dwv = (dwqv[:n] if ng[_I.wq] else None), (dwqv[n:] if ng[_I.wv] else None)
         if dbqv is not None:
-            dbq, dbv = (dbqv[:n] if ng[6] else None), (dbqv[n:] if ng[8] else None)
+            dbq, dbv = (dbqv[:n] if ng[_I.bq] else None), (dbqv[n:] if ng[_I.bv] else None)
         if sync is not None:
             qv_pairs, k_pairs = [(wq_, dwq), (bq_, dbq), (wv_, dwv), (bv_, dbv)], [(wk_, dwk), (bk_, dbk)]
             if qv_on is side:  # one call: the buckets it completes share one grouped all-reduce
@@ -307,6 +299,8 @@ class AttnBlockFn(torch.autograd.Function):
         # the attention's tensors were only borrowed from ctx.saved_tensors (rebuilt from there by
         # every backward): do not keep them alive through the node after this backward
         ctx.actx._saved = None
-        grads = (dxk, dxqv, None, dwk, dbk, dwq, dbq, dwv, dbv, dwc, dbc, None, None, None, None, None, None, None, None,
-                 None)
-        return (grads + (dwkn, dwqn, None, dsk, dwg, dbg))[:len(ng)]
+        grads = [None] * len(ARG_NAMES)  # (a list filled by index: a dict keyed by name costs 2 us more per call)
+        grads[_I.xk], grads[_I.xqv], grads[_I.wkn], grads[_I.wqn], grads[_I.sinks] = dxk, dxqv, dwkn, dwqn, dsk
+        grads[_I.wk], grads[_I.bk], grads[_I.wq], grads[_I.bq], grads[_I.wv], grads[_I.bv] = dwk, dbk, dwq, dbq, dwv, dbv
+        grads[_I.wc], grads[_I.bc], grads[_I.wg], grads[_I.bg] = dwc, dbc, dwg, dbg
+        return tuple(grads)

@@ -133,58 +133,9 @@ def head_rms_norm_backward(g: Tensor, x: Tensor, rstd: Tensor, num_heads: int, w
     return out, dw
 
 
-class _HeadNormFn(torch.autograd.Function):
-    """The first ``ncols`` features of ``x`` normalised (and rotated) (``ncols`` = all of them but
-    for a packed ``[q | v]``, whose rest is copied).  ``mode``: 0 a new tensor, 1 in place on ``x``,
-    2 into ``out``.  Kept for the backward: ``rstd`` and the pre-norm input -- the input itself where
-    the call leaves it alone, the pass's own bit copy where it is overwritten (``mode`` 1)."""
-
-    @staticmethod
-    @_ext.pinned
-    def forward(ctx, x, weight, out, ncols, H, eps, cos, sin, alpha, bwd_alpha, mode):
-        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
-        full = ncols == x.shape[-1]
-        src = x if full else x[..., :ncols]
-        if mode == 0:
-            if full:
-                res, rstd, _ = head_rms_norm_apply(src, H, weight, eps, cos, sin, alpha)
-            else:
-                res = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-                _, rstd, _ = head_rms_norm_apply(src, H, weight, eps, cos, sin, alpha, out=res[..., :ncols])
-                res[..., ncols:].copy_(x[..., ncols:])
-            kept = src
-        else:
-            res = x if mode == 1 else out
-            _, rstd, kept = head_rms_norm_apply(src, H, weight, eps, cos, sin, alpha, out=res[..., :ncols],
-                                                save=need and mode == 1)
-            if mode == 2:
-                kept = src
-            ctx.mark_dirty(res)
-        ctx.tab, ctx.args = (cos, sin), (ncols, H, bwd_alpha)
-        if need:
-            ctx.save_for_backward(kept, weight, rstd)
-        return res
-
-    @staticmethod
-    @_ext.pinned
-    def backward(ctx, g):
-        ncols, H, bwd_alpha = ctx.args
-        cos, sin = ctx.tab
-        xs, weight, rstd = ctx.saved_tensors
-        need_dw = ctx.needs_input_grad[1]
-        if ncols == g.shape[-1]:
-            gx, dw = head_rms_norm_backward(g, xs, rstd, H, weight, cos, sin, bwd_alpha, need_dw=need_dw)
-        else:
-            gx = torch.empty(g.shape, dtype=g.dtype, device=g.device)
-            _, dw = head_rms_norm_backward(g[..., :ncols], xs, rstd, H, weight, cos, sin, bwd_alpha, out=gx[..., :ncols],
-                                           need_dw=need_dw)
-            gx[..., ncols:].copy_(g[..., ncols:])
-        return gx, dw, None, None, None, None, None, None, None, None, None
-
-
 def _table(x: Tensor, ncols: int, H: int, rotary: Optional[Rotary], offset, what: str):
     if rotary is None:
-        return None, None
+        return None
     if not isinstance(rotary, Rotary):
         raise TypeError(f"{what}: rotary must be an xdot.Rotary or None, got {type(rotary).__name__}")
     D = ncols // H
@@ -207,26 +158,26 @@ def head_rms_norm(x: Tensor, num_heads: int, weight: Tensor, eps: float = 1e-6, 
     _B, _R, C, H, _D = _dims(x, num_heads, weight, what)
     if not float(eps) > 0.0:
         raise ValueError(f"{what}: eps must be positive, got {eps}")
-    cos, sin = _table(x, C, H, rotary, offset, what)
+    tab = _table(x, C, H, rotary, offset, what)
     if out is not None and (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device):
         raise ValueError(f"{what}: out must match x in shape, dtype and device")
-    mode = 0 if out is None else (1 if out is x else 2)
-    return _HeadNormFn.apply(x, weight, out if mode == 2 else None, C, H, float(eps), cos, sin, float(alpha),
-                             float(alpha), mode)
+    from .qkprep import prep  # (imports this module)
+
+    return prep(x, C, H, tab, weight, eps, alpha, out=out)
 
 
 def norm_packed(qv: Tensor, ncols: int, num_heads: int, weight: Tensor, eps: float = 1e-6,
                 rotary: Optional[Rotary] = None, offset=None, alpha: float = 1.0,
                 bwd_alpha: Optional[float] = None) -> Tensor:
     """A copy of ``qv`` with its first ``ncols`` features normalised (and, with ``rotary``, rotated
-    at ``offset``) as one autograd node: :func:`xdot.ops.rope.rope_packed` with the norm in the same
-    pass (the ``q`` half of a packed ``[q | v]``; all of a ``k``).  ``bwd_alpha``: the factor of
-    the backward (default ``alpha``; 1 where ``alpha`` is the row side's pre-scale)."""
+    at ``offset``) as one autograd node (the ``q`` half of a packed ``[q | v]``; all of a ``k``):
+    :func:`xdot.ops.qkprep.prep` with the table built here.  ``bwd_alpha``: the factor of the
+    backward (default ``alpha``; 1 where ``alpha`` is the row side's pre-scale)."""
+    from .qkprep import prep  # (imports this module)
+
     ncols, H = int(ncols), int(num_heads)
     _dims(qv[..., :ncols], H, weight, "norm_packed")
-    cos, sin = _table(qv, ncols, H, rotary, offset, "norm_packed")
-    return _HeadNormFn.apply(qv, weight, None, ncols, H, float(eps), cos, sin, float(alpha),
-                             float(alpha if bwd_alpha is None else bwd_alpha), 0)
+    return prep(qv, ncols, H, _table(qv, ncols, H, rotary, offset, "norm_packed"), weight, eps, alpha, bwd_alpha)
 
 
 class HeadRMSNorm(nn.Module):

@@ -26,7 +26,7 @@ from torch import Tensor
 from .. import _ext
 from ._rowview import rotate_half, split_heads, unit_inner
 
-__all__ = ["Rotary", "rope", "rope_apply", "rope_packed"]
+__all__ = ["Rotary", "rope", "rope_apply"]
 
 _HIP_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
 _MAX_POS = 2**31 - 1
@@ -62,8 +62,8 @@ class Rotary:
     def resolve(self, rank: int, R: int, world_size: Optional[int] = None, layout: str = "contiguous"):
         """This rank's global positions: ``offset``, or where it is None ``rank * R`` -- under a
         ``layout`` whose rank holds several runs of rows (``"zigzag"`` with ``world_size > 1``) the
-        tuple of its row runs ``(local_start, length, global_start)``, which :meth:`table`,
-        :func:`rope` and :func:`rope_packed` take in place of an offset."""
+        tuple of its row runs ``(local_start, length, global_start)``, which :meth:`table`
+        and :func:`rope` take in place of an offset."""
         if layout != "contiguous":
             from ..parallel import layout as L  # (xdot.parallel imports this module)
 
@@ -165,42 +165,6 @@ def rope_apply(x: Tensor, num_heads: int, cos: Tensor, sin: Tensor, inverse: boo
     return out
 
 
-class _RopeFn(torch.autograd.Function):
-    """The first ``ncols`` features of ``x`` rotated (``ncols`` = all of them but for a packed
-    ``[q | v]``, whose rest is copied).  ``mode``: 0 a new tensor, 1 in place on ``x``, 2 into
-    ``out``.  Backward: the inverse rotation of the incoming gradient times ``bwd_alpha``; only
-    the table is kept."""
-
-    @staticmethod
-    @_ext.pinned
-    def forward(ctx, x, out, ncols, H, cos, sin, inverse, alpha, bwd_alpha, mode):
-        ctx.tab, ctx.args = (cos, sin), (ncols, H, inverse, bwd_alpha)
-        if mode == 0:
-            if ncols == x.shape[-1]:
-                return rope_apply(x, H, cos, sin, inverse, alpha)
-            new = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-            rope_apply(x[..., :ncols], H, cos, sin, inverse, alpha, out=new[..., :ncols])
-            new[..., ncols:].copy_(x[..., ncols:])
-            return new
-        dst = x if mode == 1 else out
-        rope_apply(x[..., :ncols], H, cos, sin, inverse, alpha, out=dst[..., :ncols])
-        ctx.mark_dirty(dst)
-        return dst
-
-    @staticmethod
-    @_ext.pinned
-    def backward(ctx, g):
-        ncols, H, inverse, bwd_alpha = ctx.args
-        cos, sin = ctx.tab
-        if ncols == g.shape[-1]:
-            gx = rope_apply(g, H, cos, sin, not inverse, bwd_alpha)
-        else:
-            gx = torch.empty(g.shape, dtype=g.dtype, device=g.device)
-            rope_apply(g[..., :ncols], H, cos, sin, not inverse, bwd_alpha, out=gx[..., :ncols])
-            gx[..., ncols:].copy_(g[..., ncols:])
-        return gx, None, None, None, None, None, None, None, None, None
-
-
 def rope(x: Tensor, num_heads: int, rotary: Rotary, *, offset=None, inverse: bool = False,
          alpha: float = 1.0, out: Optional[Tensor] = None) -> Tensor:
     """``alpha * rotate(x)`` for ``x`` ``(B, R, H*D)`` whose row ``r`` sits at position
@@ -214,23 +178,9 @@ def rope(x: Tensor, num_heads: int, rotary: Rotary, *, offset=None, inverse: boo
     _B, R, _C, H, D = split_heads(x, num_heads, "rope", even=True)
     if offset is None:
         offset = rotary.offset if rotary.offset is not None else 0
-    cos, sin = rotary.table(R, D, offset, x.device, _table_dtype(x))
+    tab = rotary.table(R, D, offset, x.device, _table_dtype(x))
     if out is not None and (out.shape != x.shape or out.dtype != x.dtype or out.device != x.device):
         raise ValueError("rope: out must match x in shape, dtype and device")
-    mode = 0 if out is None else (1 if out is x else 2)
-    return _RopeFn.apply(x, out if mode == 2 else None, x.shape[-1], H, cos, sin, bool(inverse), float(alpha),
-                         float(alpha), mode)
+    from .qkprep import prep  # (imports this module)
 
-
-def rope_packed(qv: Tensor, ncols: int, num_heads: int, rotary: Rotary, offset, alpha: float = 1.0,
-                bwd_alpha: Optional[float] = None) -> Tensor:
-    """A copy of ``qv`` with its first ``ncols`` features rotated at ``offset`` (an int, or row runs
-    as :meth:`Rotary.table` takes them) (the ``q`` half of a packed
-    ``[q | v]``; all of a ``k``), as one autograd node: the per-op graph's form (a projection's
-    output may be a view, which autograd does not let a later node overwrite; the one-node module
-    of :mod:`xdot.models.fused` rotates in place).  ``bwd_alpha``: the factor of the backward
-    (default ``alpha``; 1 where ``alpha`` is the row side's pre-scale, whose gradient
-    :class:`xdot.parallel.attention.SeqParallelAttention` already returns w.r.t. the unscaled rows)."""
-    cos, sin = rotary.table(qv.shape[1], ncols // int(num_heads), offset, qv.device, _table_dtype(qv))
-    return _RopeFn.apply(qv, None, int(ncols), int(num_heads), cos, sin, False, float(alpha),
-                         float(alpha if bwd_alpha is None else bwd_alpha), 0)
+    return prep(x, x.shape[-1], H, tab, alpha=alpha, out=out, inverse=inverse)
