@@ -252,3 +252,57 @@ def test_packed_entry_points_check_the_width():
         assert o.shape == (1, 6, 32)
         with pytest.raises(ValueError):
             fn(k, qv, None, 4, 0.3, comm=LocalComm(), gathered_heads=3)
+
+
+# ---- the gathered side as the kernels read it --------------------------------------------------
+@pytest.mark.parametrize("grad_fp32", [False, True])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16, torch.float32, torch.float64])
+def test_wire_dtype_is_the_three_rules_it_replaces(monkeypatch, dtype, grad_fp32):
+    """``wire_dtype`` against the three expressions it replaced, written out: the ring's accumulator
+    dtype, the rounding of the flash torch path's partials (else they stay in the compute dtype), and
+    the flash HIP path's ``gdt`` (on the dtypes that path takes: fp64 never reaches a kernel)."""
+    from xdot.parallel import _ref
+    from xdot.parallel._gathered import wire_dtype
+    from xdot.parallel.attention import FLASH_DTYPES
+    from xdot.utils.env import FLAGS
+
+    monkeypatch.setattr(FLAGS, "grad_fp32", grad_fp32)
+    k = torch.empty(0, dtype=dtype)
+    got = wire_dtype(dtype)
+    ring = k.dtype if (k.dtype in (torch.bfloat16, torch.float16) and not FLAGS.grad_fp32) else (
+        torch.float32 if k.dtype != torch.float64 else k.dtype)
+    assert got == ring
+    parts = torch.empty(0, dtype=_ref.compute_dtype(k))
+    if k.dtype in (torch.bfloat16, torch.float16) and not FLAGS.grad_fp32:
+        parts = parts.to(k.dtype)
+    assert got == parts.dtype
+    if dtype in FLASH_DTYPES:
+        assert got == (k.dtype if not FLAGS.grad_fp32 else torch.float32)
+
+
+def test_gathered_side_view_and_fold():
+    """H = 4, Hg = 2, D = 2 on the CPU, ``expand`` forced: every gathered head stands G = 2 times in the
+    kernel view, the halves split at H * D, and a partial of distinct integers folds to the group sums in
+    head order; without ``expand`` the view is the buffer itself, the halves split at Hg * D and the fold
+    is the identity."""
+    from xdot.parallel._gathered import GatheredSide
+
+    k = torch.zeros(1, 1, 8)
+    g = torch.arange(8.0).view(1, 1, 8)            # [q0 q1 | v0 v1], two columns a head
+    gs = GatheredSide(k, 4, 2, 0.5, False, expand=True)
+    assert (gs.Cq, gs.kC, gs.kHg, gs.Hg) == (4, 8, None, 2)
+    x = gs.view(g)
+    assert x.tolist() == [[[0, 1, 0, 1, 2, 3, 2, 3, 4, 5, 4, 5, 6, 7, 6, 7]]]
+    q, v = gs.halves(x)
+    assert q.tolist() == [[[0, 1, 0, 1, 2, 3, 2, 3]]] and v.tolist() == [[[4, 5, 4, 5, 6, 7, 6, 7]]]
+    part = torch.arange(16.0).view(1, 1, 16)       # [dq of row heads 0..3 | dv of row heads 0..3]
+    folded = gs.fold(part, torch.float64)
+    assert folded.dtype == torch.float64 and folded.tolist() == [[[2, 4, 10, 12, 18, 20, 26, 28]]]
+
+    same = GatheredSide(k, 4, 2, 0.5, False)       # a CPU tensor never expands by itself
+    assert not same.expand and (same.Cq, same.kC, same.kHg) == (4, 4, 2)
+    assert same.view(g) is g and same.fold(part, torch.float64) is part
+    q, v = same.halves(g)
+    assert q.tolist() == [[[0, 1, 2, 3]]] and v.tolist() == [[[4, 5, 6, 7]]]
+    plain = GatheredSide(k, 4, None, 0.5, False)   # no grouping: the q half is as wide as k
+    assert (plain.Cq, plain.kC, plain.kHg) == (8, 8, None) and not plain.expand

@@ -2,7 +2,7 @@
 kernels against an fp32 torch reference with the gathered heads repeated, bitwise against the same
 call on operands expanded to ``H`` heads, the column kernel's row splits and output modes, the
 module (fused node, per-op graph, ring, the families that expand after the gather), an emulated
-middle rank and a HIP-graph captured step."""
+middle rank, the expanding families' flash and ring paths on three ranks, and a HIP-graph captured step."""
 import math
 
 import pytest
@@ -339,7 +339,7 @@ def test_module_families_that_expand(gpu, family):
             pa.SeqParallelAttention.forward = staticmethod(orig)
         e = _errors(got, _step(ref, x.double(), mask))
     print(f"gqa {family}:", {k: f"{v:.2e}" for k, v in e.items()})
-    assert spy.ctx.expand and spy.ctx.Hg == Hg
+    assert spy.ctx.gs.expand and spy.ctx.gs.Hg == Hg
     # saved: k, o, lse, then the gathered buffer(s) (and score buffers, 1-D): the [q|v] buffer is Hg wide
     bufs = [s for s in saved[0][3:] if len(s) == 3]
     assert bufs and all(s == (1, T, 2 * Hg * D) for s in bufs), saved
@@ -401,6 +401,97 @@ def test_emulated_middle_rank(gpu, chunks, B):
     from _dist import run_gloo
 
     run_gloo(_middle_rank_case, 3, chunks, B, timeout=400)
+
+
+# ---- the families that expand, on several ranks ------------------------------------------------------
+# family -> (D, dtype, relative Frobenius bound against fp64 for out and every gradient: the op-level bound of
+# tests/test_flash_wide_gpu.py::test_flash_wide_bf16 and of tests/test_flash_f32_gpu.py::test_flash_f32_fwd_bwd)
+EXPANDING = {"wide_bf16": (160, torch.bfloat16, 2e-2), "exact_fp32": (64, torch.float32, 2e-6)}
+
+
+def _expanding_case(rank, ws, path, chunks, B):
+    """One rank of ``ws``, 200 rows each, H = 4, Hg = 2, the random 0.3 mask of :func:`_middle_rank_case` (rank
+    0's own block fully masked), both families of ``EXPANDING``.  (a) ``o`` and ``k.grad`` are bitwise those of
+    the same call without ``gathered_heads`` on a ``qv`` whose heads are repeated here: the kernels then get
+    the same values under the same launch plan.  (b) ``o``, ``k.grad`` and ``qv.grad`` (the group sums),
+    gathered over the ranks, against fp64 torch on the whole sequence with repeated heads."""
+    import os
+
+    from xdot.parallel import gather_sequence
+    from xdot.parallel.attention import seq_parallel_attention_packed, start_gather
+    from xdot.parallel.ring import ring_attention_packed
+    from xdot.utils.env import FLAGS
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    os.environ["XDOT_LOCAL_FIRST"] = "1"
+    FLAGS.reload()
+    H, Hg, L = 4, 2, 200
+    T, G = L * ws, H // Hg
+    sl = slice(rank * L, (rank + 1) * L)
+    for family, (D, dt, tol) in EXPANDING.items():
+        C, Cg, scale = H * D, Hg * D, 1.0 / math.sqrt(D)
+        g = torch.Generator().manual_seed(9)
+        k_full = torch.randn(B, T, C, generator=g).to(dev, dt)
+        qv_full = torch.randn(B, T, 2 * Cg, generator=g).to(dev, dt)
+        do_full = torch.randn(B, T, C, generator=g).to(dev, dt)
+        mask = torch.rand(B, T, T, generator=g) < 0.3
+        mask[:, :L, :L] = True                        # rank 0's rows: own block fully masked
+        mask[:, :L, L] = False
+        mask = mask.to(dev)
+        qv_rep = torch.cat([_expand(qv_full[..., :Cg], Hg, G), _expand(qv_full[..., Cg:], Hg, G)], dim=-1)
+
+        def run(src, hg):
+            k = k_full[:, sl].clone().requires_grad_(True)
+            qv = src[:, sl].clone().requires_grad_(True)
+            if path == "flash":
+                o = seq_parallel_attention_packed(k, qv, mask[:, sl], H, scale, pending=start_gather(qv, chunks=chunks),
+                                                  gathered_heads=hg)
+            else:
+                o = ring_attention_packed(k, qv, mask[:, sl], H, scale, gathered_heads=hg)
+            o.backward(do_full[:, sl])
+            torch.cuda.synchronize()
+            assert qv.grad.shape == qv.shape, f"{family}: d[q|v] {tuple(qv.grad.shape)}, qv {tuple(qv.shape)}"
+            return o.detach(), k.grad, qv.grad
+
+        o, dk, dqv = run(qv_full, Hg)
+        o_rep, dk_rep, _ = run(qv_rep, None)
+        assert torch.equal(o, o_rep), f"{family}: o differs from the call on repeated heads"
+        assert torch.equal(dk, dk_rep), f"{family}: dk differs from the call on repeated heads"
+
+        kf = k_full.double().requires_grad_(True)
+        qvf = qv_full.double().requires_grad_(True)
+        kh = kf.view(B, T, H, D).transpose(1, 2)
+        qh = qvf[..., :Cg].reshape(B, T, Hg, D).transpose(1, 2).repeat_interleave(G, dim=1)
+        vh = qvf[..., Cg:].reshape(B, T, Hg, D).transpose(1, 2).repeat_interleave(G, dim=1)
+        s = (kh @ qh.transpose(-1, -2) * scale).masked_fill(mask.unsqueeze(1), -float("inf"))
+        ref = (s.softmax(-1) @ vh).transpose(1, 2).reshape(B, T, C)
+        ref.backward(do_full.double())
+        errs = {"o": _rel(gather_sequence(o, -2), ref.detach()), "dk": _rel(gather_sequence(dk, -2), kf.grad),
+                "d[q|v]": _rel(gather_sequence(dqv, -2), qvf.grad)}
+        if rank == 1:
+            print(f"gqa expanding [{path} {family} chunks={chunks} B={B}]:", {n: f"{e:.2e}" for n, e in errs.items()})
+        for n, e in errs.items():
+            assert e <= tol, f"{family} {n}: {e:.3e} > {tol:.0e}"
+
+
+@pytest.mark.parametrize("chunks,B", [(1, 1), (2, 1), (2, 2)])
+def test_expanding_families_flash_three_ranks(gpu, chunks, B):
+    """The flash path where the gathered heads are repeated for the kernels and the gradients folded, on a
+    middle rank of 3: wide bf16 (D = 160, no score buffer: the segmented forward) and exact fp32 (D = 64, one
+    kernel on the score buffer); one gather chunk, two chunks in one buffer (the per-chunk fold of one
+    kernel's partial) and two chunks as separate buffers (B = 2: a column kernel and a fold per chunk)."""
+    from _dist import run_gloo
+
+    run_gloo(_expanding_case, 3, "flash", chunks, B, timeout=400)
+
+
+def test_expanding_families_ring_three_ranks(gpu):
+    """The ring's per-block expansion and fold on 3 ranks (B = 1: the bidirectional merged-lane schedule),
+    same families and checks."""
+    from _dist import run_gloo
+
+    run_gloo(_expanding_case, 3, "ring", 1, 1, timeout=400)
 
 
 def test_module_padded_heads(gpu):

@@ -54,6 +54,7 @@ from ..utils.checks import check_consistent
 from ..utils.env import FLAGS
 from ..utils.streams import _on_stream, _prep_event, _side_stream
 from . import _ref
+from ._gathered import GatheredSide, _q_width, pop_sinks, sinks_grad, wire_dtype
 from .layout import check_layout
 
 __all__ = ["seq_parallel_attention", "seq_parallel_attention_packed", "start_gather", "flash_supported",
@@ -139,33 +140,6 @@ def sinks_arg(sinks, H: int, like: Tensor):
     if sinks.device != like.device:
         raise ValueError(f"sinks must be on the tensors' device {like.device}, got {sinks.device}")
     return sinks
-
-
-def _native_gqa(k: Tensor, H: int) -> bool:
-    """The kernels index a narrower gathered side themselves: the 16-bit families up to head dim
-    128.  Exact fp32, split-bf16 and the wide heads get the gathered heads expanded after the
-    gather and their gradients folded before the reduce-scatter (:func:`_expand_heads`)."""
-    return k.dtype != torch.float32 and k.shape[-1] // H <= 128
-
-
-def _expand_heads(g: Tensor, H: int, Hg: int) -> Tensor:
-    """Packed ``[q | v]`` (..., 2 * Hg * D) -> (..., 2 * H * D): every gathered head repeated for
-    the row heads of its group (one copy)."""
-    D = g.shape[-1] // (2 * Hg)
-    lead = tuple(g.shape[:-1])
-    return g.reshape(*lead, 2, Hg, 1, D).expand(*lead, 2, Hg, H // Hg, D).reshape(*lead, 2 * H * D)
-
-
-def _fold_heads(d: Tensor, H: int, Hg: int, dtype) -> Tensor:
-    """Packed ``[dq | dv]`` (..., 2 * H * D) per row head -> (..., 2 * Hg * D) in ``dtype``: the sum
-    over each group, in fp32 and in head order (deterministic)."""
-    D = d.shape[-1] // (2 * H)
-    lead = tuple(d.shape[:-1])
-    x = d.reshape(*lead, 2, Hg, H // Hg, D)
-    acc = x[..., 0, :].float()
-    for j in range(1, H // Hg):
-        acc = acc + x[..., j, :]
-    return acc.reshape(*lead, 2 * Hg * D).to(dtype)
 
 
 def _prescale_rows(k: Tensor) -> bool:
@@ -280,50 +254,32 @@ def _as_global(g: Tensor) -> Tensor:
 # ----------------------------------------------------------------------------------------
 # torch path of the per-rank compute (CPU / fallback / testing): layout adapters over _ref
 # ----------------------------------------------------------------------------------------
-def _forward_torch(k, qvg, mask, H, scale, Hg=None):
-    """Whole-row forward from the rank-major gathered (N, B, R, Cq + Cv): one block, combined
-    alone (a fully masked row comes out NaN)."""
-    C = _q_width(k, H, Hg)
-    part = _ref.block_fwd(k, _as_global(qvg[..., :C]), _as_global(qvg[..., C:]), mask, H, scale, Hg)
-    return _ref.combine([part], k.dtype)
-
-
-def _q_width(k, H, Hg):
-    """Columns of the ``q`` half of a packed ``[q | v]``: ``Hg`` heads of the row side's head dim."""
-    return k.shape[-1] if not Hg else Hg * (k.shape[-1] // H)
-
-
-def _segmented_forward_torch(k, qv, mask, H, scale, pending, n, rank, Hg=None):
+def _segmented_forward_torch(k, qv, mask, gs, pending, n, rank):
     B, R = k.shape[:2]
-    C = _q_width(k, H, Hg)
     plan = _segment_plan(n, rank, len(pending.chunks), FLAGS.local_first)
     parts = []
     if FLAGS.local_first:
         own = None if mask is None else _mask_cols(B, R, n, rank, rank + 1, 0, R)(mask)
-        parts.append(_ref.block_fwd(k, qv[..., :C], qv[..., C:], own, H, scale, Hg))
-    gs = []
+        parts.append(gs.ref_fwd(k, qv, own))
+    bufs = []
     for c, (r0, rc) in enumerate(pending.chunks):
         g = pending.wait(c)                                      # (N, B, rc, 2C)
-        gs.append(g)
+        bufs.append(g)
         for _, j0, j1 in (p for p in plan if p[0] == c):
-            seg = _as_global(g[j0:j1])
             m = None if mask is None else _mask_cols(B, R, n, j0, j1, r0, rc)(mask)
-            parts.append(_ref.block_fwd(k, seg[..., :C], seg[..., C:], m, H, scale, Hg))
+            parts.append(gs.ref_fwd(k, _as_global(g[j0:j1]), m))
     o, lse = _ref.combine(parts, k.dtype)
-    return o, lse, [torch.cat(gs, dim=2) if len(gs) > 1 else gs[0]]
+    return o, lse, [torch.cat(bufs, dim=2) if len(bufs) > 1 else bufs[0]]
 
 
 def _backward_torch(ctx, do, k, o, lse, qvg, sinks=None):
     """-> (dk, d[q|v] of this rank's rows, ds or None) from the rank-major gathered ``qvg`` (N, B, R, Cq + Cv)."""
-    C = _q_width(k, ctx.H, ctx.Hg)
-    n, B, Rg = qvg.shape[:3]
-    delta = _ref.delta(do, o, ctx.H, lse.dtype)
+    gs, (n, B, Rg) = ctx.gs, qvg.shape[:3]
+    delta = _ref.delta(do, o, gs.H, lse.dtype)
     ds = None if sinks is None else _ref.sink_grad(delta, lse, sinks)
-    dk, dq, dv = _ref.block_bwd(do, k, _as_global(qvg[..., :C]), _as_global(qvg[..., C:]), lse, delta, ctx.mask,
-                                ctx.H, ctx.scale, ctx.Hg)
+    dk, dq, dv = gs.ref_bwd(do, k, qvg, lse, delta, ctx.mask, rows=_as_global)
     parts = torch.cat([dq, dv], dim=-1).view(B, n, Rg, -1).permute(1, 0, 2, 3).contiguous()  # rank-major
-    if k.dtype in (torch.bfloat16, torch.float16) and not FLAGS.grad_fp32:
-        parts = parts.to(k.dtype)  # the HIP path's wire dtype (one rounding per partial)
+    parts = parts.to(wire_dtype(k.dtype))  # as the HIP path (16-bit: one rounding per partial)
     h, dqv = _reduce_async(ctx.comm, parts)
     if h is not None:
         h.wait()
@@ -357,18 +313,15 @@ def _mask_cols(B: int, R: int, n: int, j0: int, j1: int, r0: int, rc: int):
     return lambda m: m.reshape(*m.shape[:-1], n, R)[..., j0:j1, r0:r0 + rc].reshape(*m.shape[:-1], (j1 - j0) * rc)
 
 
-def _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescaled, fp32_mode=0, Hg=None,
-                       expand=False):
+def _segmented_forward(k, qv, mask, gs, pending, n, rank):
     """Forward of a multi-rank step as column segments merged by one log-sum-exp combine:
     the rank's OWN [q|v] block first (it needs no communication, so its partial runs while the
     all-gather is in flight), then each gathered chunk's peer blocks as soon as that chunk
     lands.  Every segment is a subset of a row's columns, so the partials (o normalised over
     the segment, its lse) merge exactly.  -> (o, lse, gathered buffers saved for backward)."""
-    if not use_hip:
-        return _segmented_forward_torch(k, qv, mask, H, scale, pending, n, rank, Hg)
-    B, R, C = k.shape
-    Cq = _q_width(k, H, Hg)
-    kHg = None if expand else Hg  # gathered heads the kernels see
+    if not gs.use_hip:
+        return _segmented_forward_torch(k, qv, mask, gs, pending, n, rank)
+    (B, R, C), H = k.shape, gs.H
     chunks = pending.chunks
     local_first = FLAGS.local_first
     plan = _segment_plan(n, rank, len(chunks), local_first)
@@ -384,13 +337,7 @@ def _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescal
     slots = iter([(sum(ns[:i]), nsi) for i, nsi in enumerate(ns)])  # (first slot, slots) per launch
 
     def run(seg, mk):  # seg: (B, Tseg, 2 Cq) = [q | v] of the segment's columns
-        slot, nsi = next(slots)
-        if expand:  # a family without a grouped kernel: the segment's heads repeated (one copy)
-            seg = _expand_heads(seg, H, Hg)
-            flash.fwd_partial(k, seg[..., :C], seg[..., C:], mk, H, scale, opart, lpart, slot, nsi, prescaled, fp32_mode)
-            return
-        flash.fwd_partial(k, seg[..., :Cq], seg[..., Cq:], mk, H, scale, opart, lpart, slot, nsi, prescaled, fp32_mode,
-                          kHg)
+        gs.fwd_partial(k, gs.view(seg), mk, opart, lpart, *next(slots))
 
     if local_first:
         own = _mask_cols(B, R, n, rank, rank + 1, 0, R)
@@ -491,27 +438,6 @@ def _score_buffers(k, H, T, fm, one_kernel, segmented):
     return sbuf, dsbuf, segmented
 
 
-def _whole_forward_hip(k, mask, packed_full, pending, n, H, scale, prescaled, fm, sbuf, Hg=None, expand=False):
-    """One kernel over the whole gathered side -> (o, lse, the (B, T, 2 Cq) buffer, its packed mask)."""
-    B, R, C = k.shape
-    chunks = pending.chunks
-    if len(chunks) > 1:  # several gather chunks, one buffer in (chunk, rank, row) order
-        pending.wait_all()
-        qvg = pending.permuted()
-        mk = _whole_mask(mask, B, R, n, chunks)
-    else:
-        mk = packed_full if packed_full is not None else _whole_mask(mask, B, R, n, chunks)
-        qvg = flash.gathered_to_btc(pending.wait(0))     # (B, T, 2C), a view for B = 1
-    if expand:  # a family without a grouped kernel: H heads for the kernel, the Hg-wide buffer is kept
-        x = _expand_heads(qvg, H, Hg)
-        o, lse = flash.fwd(k, x[..., :C], x[..., C:], mk, H, scale, prescaled=prescaled, fp32_mode=fm, sbuf=sbuf)
-        return o, lse, qvg, mk
-    Cq = _q_width(k, H, Hg)
-    o, lse = flash.fwd(k, qvg[..., :Cq], qvg[..., Cq:], mk, H, scale, prescaled=prescaled, fp32_mode=fm, sbuf=sbuf,
-                       Hg=Hg)
-    return o, lse, qvg, mk
-
-
 def _whole_mask(mask, B, R, n, chunks):
     """Packed (cached) mask of the one gathered buffer: rank-major columns, or with several gather
     chunks their (chunk, rank, row) order."""
@@ -545,7 +471,7 @@ def _saved_scores(ctx, sbt, k, H):
             sbuf = None
         ctx.sb_used = True
     D = k.shape[-1] // H
-    if sbuf is None and k.dtype == torch.float32 and D > WIDE_F32_NEEDS_SCORES and ctx.fp32_mode == 0:
+    if sbuf is None and k.dtype == torch.float32 and D > WIDE_F32_NEEDS_SCORES and ctx.gs.fp32_mode == 0:
         raise RuntimeError(
             f"xdot: a second backward through a retained graph of exact-fp32 attention at head dim "
             f"{D} needs the scores, which the first backward overwrote in place (no kernel "
@@ -579,27 +505,19 @@ def _cols_one_buffer(cols, g, mk, sbuf, dsbuf, fused, hi):
 def _rows_hip(ctx, do, k, lse, delta, bufs, mks, sbuf, dsbuf, cur):
     """Row-side dk on the current stream: one kernel over the one buffer, or one partial launch
     per chunk buffer and their sum."""
-    H, scale = ctx.H, ctx.scale
-    B, R, C = k.shape
-    # (bufs: expanded to H heads by the caller for a family without a grouped kernel)
-    Hg = None if ctx.expand else ctx.Hg
-    Cq = _q_width(k, H, Hg)
-    if len(bufs) == 1:
-        g = bufs[0]
-        dk = flash.bwd_rows(do, k, g[..., :Cq], g[..., Cq:], lse, delta, mks[0], H, scale,
-                            nsplit=FLAGS.rows_split, prescaled=ctx.prescaled, fp32_mode=ctx.fp32_mode,
-                            sbuf=sbuf, dsbuf=dsbuf, Hg=Hg)
+    gs, (B, R, C) = ctx.gs, k.shape
+    if len(bufs) == 1:  # (bufs: the kernel views the column kernels read)
+        dk = gs.bwd_rows(do, k, bufs[0], lse, delta, mks[0], sbuf, dsbuf)
         if sbuf is not None:
             sbuf.record_stream(cur)
         if dsbuf is not None:
             dsbuf.record_stream(cur)
         return dk
-    ns = flash.splits(B, R, ctx.comm.world_size * ctx.chunks[0][1], H, True)
+    ns = flash.splits(B, R, ctx.comm.world_size * ctx.chunks[0][1], gs.H, True)
     dpart = torch.empty(len(bufs) * ns, B, R, C, dtype=torch.float32, device=k.device)
-    for c, (g, mk) in enumerate(zip(bufs, mks)):
-        flash.bwd_rows_partial(do, k, g[..., :Cq], g[..., Cq:], lse, delta, mk, H, scale, dpart, c * ns, ns,
-                               ctx.prescaled, ctx.fp32_mode, Hg)
-    return flash.bwd_rows_sum(dpart, H, k)
+    for c, (x, mk) in enumerate(zip(bufs, mks)):
+        gs.bwd_rows_partial(do, k, x, lse, delta, mk, dpart, c * ns, ns)
+    return flash.bwd_rows_sum(dpart, gs.H, k)
 
 
 def _backward_hip(ctx, do, k, o, lse, bufs, sbt, sinks=None):
@@ -610,14 +528,10 @@ def _backward_hip(ctx, do, k, o, lse, bufs, sbt, sinks=None):
     early as when it runs alone.  δ runs on the priority stream too, so 1) reaches
     the GPU first.  Per-chunk kernels (chunk c's reduce-scatter under chunk c+1's
     kernel) only when the chunks are separate buffers (B > 1)."""
-    comm, H, scale, chunks = ctx.comm, ctx.H, ctx.scale, ctx.chunks
-    n = comm.world_size
+    comm, gs, chunks = ctx.comm, ctx.gs, ctx.chunks
+    n, H = comm.world_size, gs.H
     B, R, C = k.shape
-    Hg, expand = ctx.Hg, ctx.expand
-    Cq = _q_width(k, H, Hg)  # the saved buffers, the wire and d[q|v] are 2 Cq wide
-    if expand:  # a family without a grouped kernel: H heads for the kernels, gradients folded below
-        bufs = [_expand_heads(g, H, Hg) for g in bufs]
-    kHg, kC = (None, C) if expand else (Hg, Cq)  # what the kernels see
+    bufs = [gs.view(g) for g in bufs]  # (saved at the wire width 2 Cq; both kernels read ONE view of each)
     one = len(bufs) == 1  # one gathered buffer: natural order, or chunks permuted (B = 1)
     mks = _backward_masks(ctx, B, R, n, one)
     cur = torch.cuda.current_stream(do.device)
@@ -626,7 +540,7 @@ def _backward_hip(ctx, do, k, o, lse, bufs, sbt, sinks=None):
     hi = _side_stream(do.device, -1) if _two_stream_backward() else cur
     hi.wait_stream(cur)
     handles, outs = [], []
-    gdt = k.dtype if not FLAGS.grad_fp32 else torch.float32
+    gdt = wire_dtype(k.dtype)
     sbuf, dsbuf = _saved_scores(ctx, sbt, k, H)
     ev_cols = None
     with _on_stream(hi, cur):
@@ -635,24 +549,20 @@ def _backward_hip(ctx, do, k, o, lse, bufs, sbt, sinks=None):
         ev.record(hi)
         dqv = None
         if n > 1 and len(chunks) > 1 and B == 1:
-            dqv = torch.empty(B, R, 2 * Cq, dtype=gdt, device=k.device)
-        # partials rounded once to the compute dtype in the kernel (XDOT_GRAD_FP32=1
-        # keeps fp32): half the epilogue stores and half the reduce-scatter bytes
-        cargs = dict(fp32_out=FLAGS.grad_fp32 or expand, prescaled=ctx.prescaled, lse2=lse2, fp32_mode=ctx.fp32_mode,
-                     Hg=kHg)
+            dqv = torch.empty(B, R, 2 * gs.Cq, dtype=gdt, device=k.device)
+        # partials rounded once to the compute dtype in the kernel (XDOT_GRAD_FP32=1 keeps fp32): half
+        # the epilogue stores and half the reduce-scatter bytes; fp32 per row head where they are folded
+        def cols(x, mk, **kw):
+            return gs.bwd_cols(do, k, x, o, lse, mk, delta, FLAGS.grad_fp32, lse2=lse2, **kw)
 
-        def cols(g, mk, **kw):
-            return flash.bwd_cols(do, k, g[..., :kC], g[..., kC:], o, lse, mk, H, scale, delta, **cargs, **kw)
-
-        def scatter(part, r0, rc):  # (B, n*rc, 2 Cq) of one chunk -> its reduce-scatter
-            if expand:  # per-row-head fp32 partials -> the group sums in the wire dtype
-                part = _fold_heads(part, H, Hg, gdt)
-            h, oc = _reduce_async(comm, flash.btc_to_rank_major(part, n), None if dqv is None else dqv[:, r0:r0 + rc])
+        def scatter(part, r0, rc):  # one chunk's (B, n*rc, ·) partial -> the wire width and dtype -> its reduce-scatter
+            h, oc = _reduce_async(comm, flash.btc_to_rank_major(gs.fold(part, gdt), n),
+                                  None if dqv is None else dqv[:, r0:r0 + rc])
             handles.append(h)
             outs.append(oc)
 
         if one:
-            fused = sbuf is not None and dsbuf is None and flash.fused_cols_wanted(ctx.fp32_mode, C // H)
+            fused = sbuf is not None and dsbuf is None and flash.fused_cols_wanted(gs.fp32_mode, C // H)
             dkv, ev_cols = _cols_one_buffer(cols, bufs[0], mks[0], sbuf, dsbuf, fused, hi)
             off = 0
             for r0, rc in chunks:  # (chunk, rank, row) order: chunk c's ranks are contiguous
@@ -710,16 +620,14 @@ class SeqParallelAttention(torch.autograd.Function):
         n, rank = comm.world_size, comm.rank
         T = n * qv.shape[1]
         use_hip = _hip_ok(k, qv, H, Hg)
-        # grouped heads in a family without a grouped kernel: expanded after the gather
-        expand = bool(Hg) and use_hip and not _native_gqa(k, H)
         if pending is None:
             pending = _PendingGather(comm, qv, _row_chunks(n, qv.shape[1], use_hip))
         chunks = pending.chunks
-        prescaled = False
-        fm = 0  # fp32 kernel family (XDOT_FP32_MODE), fixed at forward for the backward too
+        prescaled, fm = False, 0  # (fm: the fp32 kernel family (XDOT_FP32_MODE), fixed here for the backward too)
         packed_full = None  # the whole-row packed mask, when the caller packed it ahead
         if use_hip:
-            fm = flash.fp32_code(k.dtype) if C // H <= 128 else 0  # wide fp32 heads are exact only
+            # wide fp32 heads are exact only (the ring asks fp32_code at every head dim: the two rules differ)
+            fm =flash.fp32_code(k.dtype) if C // H <= 128 else 0
             # the row side pre-multiplied by scale*log2 e once (XDOT_PRESCALE, default on): the
             # forward and both backward kernels read this same buffer and seed their score
             # accumulators instead of scaling every score (saved in place of k for backward)
@@ -736,7 +644,8 @@ class SeqParallelAttention(torch.autograd.Function):
         # a StructuredMask: bound to this rank's rows for the kernels' generated packed masks; the
         # torch path below gets its dense tensor, built once here
         mask = resolve_mask(mask, B, R, T, rank, use_hip, k.device, layout)
-        segmented = n > 1 and (FLAGS.local_first or len(chunks) > 1)
+        gs = GatheredSide(k, H, Hg, scale, use_hip, prescaled, fm)  # how the kernels read the gathered side
+        segmented =n > 1 and (FLAGS.local_first or len(chunks) > 1)
         sbuf = dsbuf = None
         # a backward can run on this forward (grad mode is off inside Function.forward: autograd's
         # needs_input_grad, or the fused node's, says it); without one no score buffer is taken
@@ -745,29 +654,31 @@ class SeqParallelAttention(torch.autograd.Function):
         if use_hip and k.dtype == torch.float32 and need_bwd:
             sbuf, dsbuf, segmented = _score_buffers(k, H, T, fm, len(chunks) == 1 or B == 1, segmented)
         if segmented:
-            o, lse, bufs = _segmented_forward(k, qv, mask, H, scale, pending, n, rank, use_hip, prescaled, fm, Hg, expand)
+            o, lse, bufs = _segmented_forward(k, qv, mask, gs, pending, n, rank)
             mks = [packed_full] if packed_full is not None else None  # backward packs its own (cached)
-        elif use_hip:
-            o, lse, qvg, mk = _whole_forward_hip(k, mask, packed_full, pending, n, H, scale, prescaled, fm, sbuf, Hg,
-                                                 expand)
+        elif use_hip:  # one kernel over the whole gathered side; the (B, T, 2 Cq) wire buffer is what is saved
+            if len(chunks) > 1:  # several gather chunks, one buffer in (chunk, rank, row) order
+                pending.wait_all()
+                qvg = pending.permuted()
+                mk = _whole_mask(mask, B, R, n, chunks)
+            else:
+                mk = packed_full if packed_full is not None else _whole_mask(mask, B, R, n, chunks)
+                qvg = flash.gathered_to_btc(pending.wait(0))     # (B, T, 2C), a view for B = 1
+            o, lse = gs.fwd(k, gs.view(qvg), mk, sbuf)
             bufs, mks = [qvg], [mk]
         else:
-            qvg = pending.wait(0)                            # (N, B, R, 2C)
-            o, lse = _forward_torch(k, qvg, mask, H, scale, Hg)
+            qvg = pending.wait(0)                            # (N, B, R, Cq + Cv) rank-major
+            # one block, combined alone (a fully masked row comes out NaN)
+            o, lse = _ref.combine([gs.ref_fwd(k, qvg, mask, rows=_as_global)], k.dtype)
             bufs, mks = [qvg], [mask]
-        if sinks is not None:
-            # the sink logit joins the finished softmax: lse' = logaddexp(lse, s_h), o' = exp(lse - lse') o.
-            # The backward kernels run unchanged on the folded pair
-            o, lse = flash.sink_fold(o, lse, sinks, H) if use_hip else _ref.sink_fold(o, lse, sinks, H)
+        o, lse = gs.sink_fold(o, lse, sinks)
         # the score buffers travel as saved tensors: autograd frees them after the backward unless
         # the graph is retained (a ctx attribute would keep 20-40 GB alive as long as the graph is
         # referenced, e.g. through the previous step's loss)
         sbt = tuple(t for t in (sbuf, dsbuf) if t is not None)
         ctx.save_for_backward(k, o, lse, *bufs, *sbt, *(() if sinks is None else (sinks,)))
         ctx.has_sinks = sinks is not None
-        ctx.mks, ctx.mask, ctx.chunks, ctx.H, ctx.scale, ctx.comm, ctx.use_hip = mks, mask, chunks, H, scale, comm, use_hip
-        ctx.prescaled, ctx.fp32_mode = prescaled, fm
-        ctx.Hg, ctx.expand = Hg, expand
+        ctx.mks, ctx.mask, ctx.chunks, ctx.comm, ctx.gs = mks, mask, chunks, comm, gs
         # (has S buffer, has dS buffer); the in-place mode (S only) is consumed by the first backward
         ctx.sb_kind = (sbuf is not None, dsbuf is not None)
         return o
@@ -776,17 +687,13 @@ class SeqParallelAttention(torch.autograd.Function):
     @_ext.pinned
     def backward(ctx, do):
         k, o, lse, *bufs = ctx.saved_tensors
-        sinks = bufs.pop() if getattr(ctx, "has_sinks", False) else None
+        sinks = pop_sinks(ctx, bufs)
         nsb = sum(getattr(ctx, "sb_kind", (False, False)))
         bufs, sbt = bufs[:len(bufs) - nsb], bufs[len(bufs) - nsb:]
         do = do.contiguous()
-        if ctx.use_hip:
-            dk, dqv, ds = _backward_hip(ctx, do, k, o, lse, bufs, sbt, sinks)
-        else:
-            dk, dqv, ds = _backward_torch(ctx, do, k, o, lse, bufs[0], sinks)
-        if ds is not None:
-            ds = ds.to(sinks.dtype)
-        return dk.to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None, None, None, None, ds
+        dk, dqv, ds = (_backward_hip(ctx, do, k, o, lse, bufs, sbt, sinks) if ctx.gs.use_hip else
+                       _backward_torch(ctx, do, k, o, lse, bufs[0], sinks))
+        return dk.to(k.dtype), dqv.to(k.dtype), None, None, None, None, None, None, None, None, None, sinks_grad(ds, sinks)
 
 
 def gather_plan(qv_shape, qv: Tensor, comm: _comm.Communicator, chunks: Optional[int] = None):

@@ -48,8 +48,8 @@ from ..utils.env import FLAGS
 from ..utils.streams import _on_stream, _side_stream
 from . import _ref
 from .layout import check_layout
-from .attention import (WIDE_F32_NEEDS_SCORES, _checked_mask, _expand_heads, _fold_heads, _hip_ok, _native_gqa,
-                        _prescale_rows, _q_width, gathered_heads_arg, sinks_arg)
+from ._gathered import GatheredSide, _q_width, pop_sinks, sinks_grad, wire_dtype
+from .attention import WIDE_F32_NEEDS_SCORES, _checked_mask, _hip_ok, _prescale_rows, gathered_heads_arg, sinks_arg
 
 __all__ = ["RingAttention", "ring_attention", "ring_attention_packed"]
 
@@ -155,20 +155,11 @@ def _block_mask(mask: Optional[Tensor], src: int, R: int, a: int = 0, b: Optiona
     return None if mask is None else mask[..., src * R + a:src * R + b]
 
 
-def _bidir() -> bool:
-    return FLAGS.ring_bidir
-
-
-def _forward_hip(k, rings, mask, H, scale, n, Hg=None, expand=False):
+def _forward_hip(k, rings, mask, gs, n):
     """-> (o, lse, the row side the kernels read (pre-scaled or not: saved for the backward), the
-    packed masks per step and launch, prescaled, fp32 kernel family).  ``Hg``: gathered heads when
-    fewer than ``H``; ``expand``: the kernel family has no grouped form, every arriving block's
-    heads are repeated (one copy per block) and the ring slots stay ``Hg`` wide."""
-    B, R, C = k.shape
-    Cq = _q_width(k, H, Hg)
-    fm = flash.fp32_code(k.dtype)
-    prescaled = _prescale_rows(k)
-    kk = flash.prescale(k, scale) if prescaled else k.contiguous()
+    packed masks per step and launch).  The ring slots stay ``Hg`` wide whatever the kernels read."""
+    (B, R, C), H = k.shape, gs.H
+    kk = flash.prescale(k, gs.scale) if gs.prescaled else k.contiguous()
     U, ns = rings.launches, flash.splits(B, R, rings.width, H)
     # slot 0: the running (O, LSE) of the blocks seen so far (fp32), then ns slots per launch
     # for the arriving pieces' split partials, merged into slot 0 after each step -- resident
@@ -184,28 +175,22 @@ def _forward_hip(k, rings, mask, H, scale, n, Hg=None, expand=False):
         for ui, (g, view, tag, _lanes) in enumerate(rings.units(s, mask, R)):
             mk = flash.prepare_mask_cached(mask, B, R, g.shape[1], tag=tag, view=view)
             step.append(mk)
-            if expand:
-                g = _expand_heads(g, H, Hg)
-                flash.fwd_partial(kk, g[..., :C], g[..., C:], mk, H, scale, opart, lpart, 1 + ui * ns, ns, prescaled, fm)
-                continue
-            flash.fwd_partial(kk, g[..., :Cq], g[..., Cq:], mk, H, scale, opart, lpart, 1 + ui * ns, ns, prescaled, fm,
-                              Hg)
+            gs.fwd_partial(kk, gs.view(g), mk, opart, lpart, 1 + ui * ns, ns)
         mks.append(step)
         if s < n - 1:
             flash.fwd_merge(opart, lpart, lrun, H)
             lpart[0].copy_(lrun)
         rings.advance()
     o, lse = flash.fwd_combine(opart, lpart, H, k)
-    return o, lse, kk, mks, prescaled, fm
+    return o, lse, kk, mks
 
 
-def _forward_torch(k, qv, rings, mask, H, scale, n, Hg=None):
+def _forward_torch(k, qv, rings, mask, gs, n):
     """-> (o, lse, the mask slices per step and lane): a running log-sum-exp merge of the blocks'
     partials, as the kernels' slot 0."""
-    B, R = k.shape[:2]
-    C = _q_width(k, H, Hg)
+    (B, R), H = k.shape[:2], gs.H
     cdt = _ref.compute_dtype(k)
-    acc = torch.zeros(B, H, R, (qv.shape[-1] - C) // (Hg or H), dtype=cdt, device=k.device)
+    acc = torch.zeros(B, H, R, (qv.shape[-1] - gs.Cq) // (gs.Hg or H), dtype=cdt, device=k.device)
     lse = torch.full((B, H, R), -float("inf"), dtype=cdt, device=k.device)
     mks: List = []
     for s in range(n):
@@ -214,7 +199,7 @@ def _forward_torch(k, qv, rings, mask, H, scale, n, Hg=None):
         for (_d, a, b), ring in zip(rings.lanes, rings.rings):
             m = _block_mask(mask, ring.src(s), R, a, b)
             step.append(m)
-            ob, lb = _ref.block_fwd(k, ring.cur[..., :C], ring.cur[..., C:], m, H, scale, Hg)
+            ob, lb = gs.ref_fwd(k, ring.cur, m)
             new = torch.logaddexp(lse, lb)
             live = torch.isfinite(new).unsqueeze(-1)
             w_old = torch.where(live, torch.exp(lse - new).unsqueeze(-1), torch.zeros_like(acc[..., :1]))
@@ -231,10 +216,8 @@ def _forward_torch(k, qv, rings, mask, H, scale, n, Hg=None):
 def _backward_hip(ctx, do, k, o, lse, rings, sinks=None):
     """-> (step(s): the launches of ring step s -> the lanes' fp32 [dq | dv] contributions,
     dk(): the row-side gradient after the last step, ds: the sinks' gradient or None)"""
-    H, scale, n = ctx.H, ctx.scale, ctx.comm.world_size
-    B, R, C = k.shape
-    Hg, expand = ctx.Hg, ctx.expand
-    kHg, kC = (None, C) if expand else (Hg, _q_width(k, H, Hg))  # what the kernels see
+    gs, n = ctx.gs, ctx.comm.world_size
+    (B, R, C), H = k.shape, gs.H
     lanes = rings.lanes
     cur = torch.cuda.current_stream(do.device)
     ov = FLAGS.ring_overlap
@@ -256,20 +239,14 @@ def _backward_hip(ctx, do, k, o, lse, rings, sinks=None):
         hi.wait_stream(cur)
         with _on_stream(hi, cur):
             for ui, (g, _v, _t, ls) in enumerate(units):
-                if expand:  # (one copy per block; the row-side launch below makes its own)
-                    g = _expand_heads(g, H, Hg)
-                c_, _ = flash.bwd_cols(do, k, g[..., :kC], g[..., kC:], o, lse, ctx.mks[s][ui], H, scale, delta,
-                                       fp32_out=True, prescaled=ctx.prescaled, fp32_mode=ctx.fp32_mode, Hg=kHg)
-                if expand:  # the group sums, before the ring accumulator
-                    c_ = _fold_heads(c_, H, Hg, torch.float32)
+                # (repeated heads: one copy per block here, and the row-side launch below makes its own)
+                c_, _ = gs.bwd_cols(do, k, gs.view(g), o, lse, ctx.mks[s][ui], delta, True)
+                c_ = gs.fold(c_, torch.float32)  # the group sums, before the ring accumulator
                 full.append(c_)
                 # a merged launch covers both lanes: lane li's contribution is its row range
                 contribs.extend(c_ if len(ls) == 1 else c_[:, lanes[li][1]:lanes[li][2]] for li in ls)
         for ui, (g, _v, _t, _ls) in enumerate(units):
-            if expand:
-                g = _expand_heads(g, H, Hg)
-            flash.bwd_rows_partial(do, k, g[..., :kC], g[..., kC:], lse, delta, ctx.mks[s][ui], H, scale, dpart,
-                                   1 + ui * nsr, nsr, ctx.prescaled, ctx.fp32_mode, kHg)
+            gs.bwd_rows_partial(do, k, gs.view(g), lse, delta, ctx.mks[s][ui], dpart, 1 + ui * nsr, nsr)
         if s < n - 1:
             _ext.ops().sum_partials_into(dpart, dpart[0])
         cur.wait_stream(hi)
@@ -282,17 +259,16 @@ def _backward_hip(ctx, do, k, o, lse, rings, sinks=None):
 
 def _backward_torch(ctx, do, k, o, lse, rings, sinks=None):
     """As :func:`_backward_hip`, in torch."""
-    C = _q_width(k, ctx.H, ctx.Hg)
+    gs = ctx.gs
     cdt = lse.dtype
-    delta = _ref.delta(do, o, ctx.H, cdt)
+    delta = _ref.delta(do, o, gs.H, cdt)
     ds = None if sinks is None else _ref.sink_grad(delta, lse, sinks)
     dk = torch.zeros(k.shape, dtype=cdt, device=k.device)
 
     def step(s):
         contribs = []
         for li, ring in enumerate(rings.rings):
-            dkb, dq, dv = _ref.block_bwd(do, k, ring.cur[..., :C], ring.cur[..., C:], lse, delta, ctx.mks[s][li],
-                                         ctx.H, ctx.scale, ctx.Hg)
+            dkb, dq, dv = gs.ref_bwd(do, k, ring.cur, lse, delta, ctx.mks[s][li])
             dk.add_(dkb)
             contribs.append(torch.cat([dq, dv], dim=-1))
         return contribs
@@ -311,30 +287,27 @@ class RingAttention(torch.autograd.Function):
         n = comm.world_size
         # (the ring has no score buffer: exact fp32 heads past 256 run the torch path)
         use_hip = _hip_ok(k, qv, H, Hg) and not (k.dtype == torch.float32 and C // H > WIDE_F32_NEEDS_SCORES)
-        expand = bool(Hg) and use_hip and not _native_gqa(k, H)
+        gs = GatheredSide(k, H, Hg, scale, use_hip, use_hip and _prescale_rows(k), flash.fp32_code(k.dtype) if use_hip else 0)
         # a StructuredMask: bound to this rank's rows (packed masks generated per block), or its
         # dense tensor, built once, for the torch path
         mask = resolve_mask(mask, B, R, n * R, comm.rank, use_hip, k.device, layout)
         qv = qv.contiguous()
-        rings = _Rings(comm, qv, _bidir())
-        prescaled, fm = False, 0
+        rings = _Rings(comm, qv, FLAGS.ring_bidir)
         if use_hip:
-            o, lse, k, mks, prescaled, fm = _forward_hip(k, rings, mask, H, scale, n, Hg, expand)
+            o, lse, k, mks = _forward_hip(k, rings, mask, gs, n)
         else:
-            o, lse, mks = _forward_torch(k, qv, rings, mask, H, scale, n, Hg)
-        if sinks is not None:  # folded after the last combine; the folded pair is what is saved
-            o, lse = flash.sink_fold(o, lse, sinks, H) if use_hip else _ref.sink_fold(o, lse, sinks, H)
+            o, lse, mks = _forward_torch(k, qv, rings, mask, gs, n)
+        o, lse = gs.sink_fold(o, lse, sinks)  # after the last combine; the folded pair is what is saved
         ctx.save_for_backward(k, qv, o, lse, *(() if sinks is None else (sinks,)))
-        ctx.mks, ctx.H, ctx.scale, ctx.comm, ctx.use_hip, ctx.prescaled = mks, H, scale, comm, use_hip, prescaled
-        ctx.fp32_mode, ctx.bidir = fm, len(rings.lanes) > 1
-        ctx.Hg, ctx.expand = Hg, expand
+        ctx.has_sinks = sinks is not None
+        ctx.mks, ctx.comm, ctx.gs, ctx.bidir = mks, comm, gs, len(rings.lanes) > 1
         return o
 
     @staticmethod
     @_ext.pinned
     def backward(ctx, do):
         k, qv, o, lse, *rest = ctx.saved_tensors
-        sinks = rest[0] if rest else None
+        sinks = pop_sinks(ctx, rest)
         comm = ctx.comm
         n = comm.world_size
         B = k.shape[0]
@@ -344,15 +317,12 @@ class RingAttention(torch.autograd.Function):
         # the [dq | dv] accumulators travel one hop behind their blocks, in the compute dtype (as
         # the fused path's reduce-scatter; XDOT_GRAD_FP32=1 keeps fp32 on the wire) -- each rank
         # adds its fp32 contribution to the arriving partial sum before forwarding it
-        wdt = k.dtype if (k.dtype in (torch.bfloat16, torch.float16) and not FLAGS.grad_fp32) else (
-            torch.float32 if k.dtype != torch.float64 else k.dtype)
+        wdt = wire_dtype(k.dtype)
         acc_in = [torch.empty(B, b - a, qv.shape[-1], dtype=wdt, device=k.device) for (_d, a, b) in lanes] \
             if n > 1 else None
-        acc_h = None
-        accs = None
-        step, dk, ds = (_backward_hip if ctx.use_hip else _backward_torch)(ctx, do, k, o, lse, rings, sinks)
-        if ds is not None:
-            ds = ds.to(sinks.dtype)
+        acc_h = accs = None
+        step, dk, ds = (_backward_hip if ctx.gs.use_hip else _backward_torch)(ctx, do, k, o, lse, rings, sinks)
+        ds = sinks_grad(ds, sinks)
         for s in range(n):
             rings.start(s)
             contribs = step(s)
