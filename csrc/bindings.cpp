@@ -429,6 +429,7 @@ TORCH_LIBRARY(xdot, m) {
   m.def("sum_partials(Tensor part, ScalarType out_dtype) -> Tensor");
   m.def("flash_splits(int B, int R, int T, int H, bool rows_kernel) -> int");
   m.def("flash_fwd_plan(int B, int R, int T, int H, int D, ScalarType dtype, int fp32_mode, bool sbuf, int nsplit) -> int[]");
+  m.def("flash_rows_plan(int B, int R, int T, int H, int D, ScalarType dtype, int fp32_mode, bool prescaled, int nsplit) -> int[]");
   m.def("flash_cols_plan(int B, int R, int T, int H, int D, ScalarType dtype, int fp32_mode, bool sbuf, bool dsbuf, "
         "int passes, bool prescaled, bool fp32_out, int Hg=0) -> int[]");
   m.def("flash_fwd_partial(Tensor rows, Tensor kc, Tensor vc, Tensor? bits, Tensor? flags, int H, float scale, "

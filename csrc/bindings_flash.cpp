@@ -273,6 +273,18 @@ std::vector<int64_t> flash_fwd_plan(int64_t B, int64_t R, int64_t T, int64_t H, 
   return {p.nsplit, p.heavy, p.whole, p.rem};
 }
 
+// [nsplit, workgroups per CU, rounds]: what flash_bwd_rows would choose for this shape on the current
+// device without a score or dS buffer (workgroups per CU: XDOT_ROWS_WPC, read per call; 0 and no rounds
+// outside the 16-bit D <= 128 family)
+std::vector<int64_t> flash_rows_plan(int64_t B, int64_t R, int64_t T, int64_t H, int64_t D, at::ScalarType dtype,
+                                     int64_t fp32_mode, bool prescaled, int64_t nsplit) {
+  const int ns = plan_rows(query_geom(B, R, T, H, D), H, dtype, fp32_mode, false, false, nsplit);
+  xdot::fa::BwdArgs a{};
+  a.B = (int)B; a.R = (int)R; a.T = (int)T; a.H = (int)H; a.nsplit = ns; a.prescaled = prescaled ? 1 : 0;
+  const int wpc = xdot_flash_bwd_rows_wpc(&a, dt_code(dtype), (int)D);
+  return {ns, wpc, wpc > 0 ? rows_rounds(B, R, H, ns, wpc, xdot_num_cus()) : 0};
+}
+
 // gathered-side grads, packed fp32 (B, T, 2C) = [dq | dv] partials for ONE reduce-scatter,
 // + δ = rowsum(dO·O)
 std::tuple<at::Tensor, at::Tensor> flash_bwd_cols(const at::Tensor& dout, const at::Tensor& rows, const at::Tensor& kc,
@@ -544,6 +556,7 @@ TORCH_LIBRARY_IMPL(xdot, CompositeExplicitAutograd, m) {
   m.impl("flash_splits", &flash_splits);
   m.impl("flash_fwd_plan", &flash_fwd_plan);
   m.impl("flash_cols_plan", &flash_cols_plan);
+  m.impl("flash_rows_plan", &flash_rows_plan);
 }
 
 TORCH_LIBRARY_IMPL(xdot, CUDA, m) {

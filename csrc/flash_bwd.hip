@@ -78,10 +78,24 @@ __global__ __launch_bounds__(256) void flash_bwd_prep_kernel(BwdArgs a, const vo
 // Masks never reach the VALU: a masked (or past-T) column seeds its Sᵀ accumulator with -inf
 // (pre-scaled: P = 2^acc = 0; otherwise P = 2^(acc·c2 - lse2) = 0), so masked and unmasked
 // tiles run the same body and only the seeds differ.
-template <int DT, int D, bool PS = false>
-__global__ __launch_bounds__(256, 2) void flash_bwd_rows_kernel(BwdArgs a) {
+//
+// WPC = 3 (pre-scaled, D <= 96): three workgroups per CU instead of two.  The pipelined body holds
+// a second S/dP pair (32 registers) to overlap MFMA and VALU inside one wave; here a third resident
+// wave per SIMD supplies that overlap, so the body is plain, one 32-column half at a time on ONE
+// S/dP pair: chains -> exp * multiply -> pack -> dk.  168 registers leave no room for loop-invariant
+// seed blocks (2 x 16), so each chain's seed is built from the lane's -lse2 / δ register just before
+// its first MFMA.  The ring has two stages, one tile ahead (Rows3Cfg).  Every accumulator sees the
+// same k-steps and the same dk contributions in the same order as in the pipelined body (half 0:
+// key fragments 0, 16; half 1: 32, 48), so the two variants agree bit for bit.
+__device__ __forceinline__ double pair_of(float v) {
+  const uint64_t b = __builtin_bit_cast(uint32_t, v);
+  return __builtin_bit_cast(double, (b << 32) | b);
+}
+template <int DT, int D, bool PS = false, int WPC = 2>
+__global__ __launch_bounds__(256, WPC) void flash_bwd_rows_kernel(BwdArgs a) {
+  static_assert(WPC == 2 || (WPC == 3 && PS && D <= 96), "three per CU: pre-scaled, D <= 96");
   using T16 = typename dt_traits<DT>::T;
-  using CF = RowsCfg<D>;
+  using CF = std::conditional_t<WPC == 3, Rows3Cfg<D>, RowsCfg<D>>;
   constexpr int IMG = CF::IMG, NG = CF::NG, PF = CF::PF, NBUF = CF::NBUF;
   constexpr int KS = D / 16, DB = D / 32;
 
@@ -236,15 +250,78 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_rows_kernel(BwdArgs a) {
       dk[db] = mfma32<DT>::run(tr_frag<D>(qs, 48, db * 32, L), p11, dk[db]);
     }
   };
+  // WPC = 3: -lse2 and δ twice each in a register pair, the source of the seed moves
+  const double spair = pair_of(-lse2), dpair = pair_of(dlt);
+  auto splat16 = [](double p) {
+    typedef __attribute__((ext_vector_type(8))) double f64x8;
+    f64x8 q;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      double t;
+      asm volatile("v_mov_b64 %0, %1" : "=v"(t) : "v"(p));
+      q[r] = t;
+    }
+    return __builtin_bit_cast(f32x16, q);
+  };
+  // WPC = 3: the plain body.  The sched_barriers keep the phases of a half apart: interleaved, the
+  // scheduler holds both halves' S/dP pairs and every operand at once and the allocator spills.
+  auto plain_body = [&](const char* qs, const char* vs, bool masked, uint64_t w) __attribute__((always_inline)) {
+    constexpr int NA = 2 * KS, NK = 2 * DB;
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+      auto opnd = [&](int i) { return (i & 1) ? row_frag<D>(vs, tt * 32, i >> 1, L) : row_frag<D>(qs, tt * 32, i >> 1, L); };
+      u32x4 o0 = opnd(0), o1 = opnd(1);
+      // the seeds, rebuilt per half: 8 v_mov_b64 each from a register pair holding the value twice
+      // (volatile: a hoisted, loop-invariant seed block would stay resident)
+      f32x16 s = splat16(spair), d = splat16(dpair);
+      if (masked) sel_bits16(s, (uint32_t)(w >> (32 * tt)), NINF_BITS);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        u32x4 o2 = o1;
+        if (i + 2 < NA) o2 = opnd(i + 2);
+        const int ks = i >> 1;
+        if (i & 1) d = mfma32<DT>::run(o0, df[ks], d);
+        else s = mfma32<DT>::run(o0, kf[ks], s);
+        __builtin_amdgcn_sched_barrier(0);
+        o0 = o1;
+        o1 = o2;
+      }
+      u32x4 t0 = tr_frag<D>(qs, tt * 32, 0, L), t1 = tr_frag<D>(qs, tt * 32 + 16, 0, L);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[r] = fast_exp2(s[r]) * d[r];  // -dSᵀ (unscaled)
+      const u32x4 p0 = acc_to_frag<DT>(s, 0), p1 = acc_to_frag<DT>(s, 1);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < NK; ++i) {
+        u32x4 t2 = t1;
+        if (i + 2 < NK) t2 = tr_frag<D>(qs, tt * 32 + ((i + 2) & 1) * 16, ((i + 2) >> 1) * 32, L);
+        dk[i >> 1] = mfma32<DT>::run(t0, (i & 1) ? p1 : p0, dk[i >> 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        t0 = t1;
+        t1 = t2;
+      }
+    }
+  };
 
   auto tile = [&](auto bufc, int kt) {
-    constexpr int BUF = decltype(bufc)::value;
+    constexpr int BUF = decltype(bufc)::value;  // < 0 (WPC = 3): the stage follows kt at run time
     if (kt + PF < kt_end) issue(kt + PF);
-    const char* qs = smem + BUF * CF::STAGE;
+    const char* qs = smem + (BUF < 0 ? (kt - kt_beg) % NBUF : BUF) * CF::STAGE;
     const char* vs = qs + IMG;
     const int flag = r0 >= a.R ? 1 : (fwg ? staged_flag(qs + CF::OFF_F, wave, kt & 3) : 0);
     const bool tail = (kt + 1) * 64 > a.T;
-    if (flag != 1) {
+    if constexpr (WPC == 3) {
+      // ONE copy of the body for both stages and for masked and open tiles (only the seed select is
+      // branched over): every further copy is another set of accumulator joins for the allocator
+      if (flag != 1) {
+        const bool masked = flag == 2 || tail;
+        uint64_t w = 0ull;
+        if (masked)
+          w = tile_bits(flag == 2 ? staged_word(qs + CF::OFF_W, wave * 32 + (lane & 31)) : 0ull, a.T - kt * 64, hf);
+        plain_body(qs, vs, masked, w);
+      }
+    } else if (flag != 1) {
       if (flag == 2 || tail) {
         const uint64_t w = tile_bits(flag == 2 ? staged_word(qs + CF::OFF_W, wave * 32 + (lane & 31)) : 0ull,
                                      a.T - kt * 64, hf);
@@ -264,25 +341,39 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_rows_kernel(BwdArgs a) {
   if (PF > 1 && kt_beg + 1 < kt_end) wait_vm<NG * (PF - 1)>();
   else wait_vm<0>();
   raw_barrier();
-  for (int kt = kt_beg; kt < kt_end; kt += NBUF) {
-    tile(std::integral_constant<int, 0>{}, kt);
-    if (kt + 1 < kt_end) tile(std::integral_constant<int, 1>{}, kt + 1);
-    if constexpr (NBUF > 2) {
-      if (kt + 2 < kt_end) tile(std::integral_constant<int, 2>{}, kt + 2);
+  if constexpr (WPC == 3) {
+    for (int kt = kt_beg; kt < kt_end; ++kt) tile(std::integral_constant<int, -1>{}, kt);
+  } else {
+    for (int kt = kt_beg; kt < kt_end; kt += NBUF) {
+      tile(std::integral_constant<int, 0>{}, kt);
+      if (kt + 1 < kt_end) tile(std::integral_constant<int, 1>{}, kt + 1);
+      if constexpr (NBUF > 2) {
+        if (kt + 2 < kt_end) tile(std::integral_constant<int, 2>{}, kt + 2);
+      }
     }
   }
+  // WPC = 3: the epilogue's row is rebuilt from the thread id, so nothing of it stays live across
+  // (or spills around) the tile loop
+  int erow = row, ehf = hf;
+  if constexpr (WPC == 3) {
+    int t = threadIdx.x;
+    asm volatile("" : "+v"(t));
+    erow = rb * 128 + (t >> 6) * 32 + (t & 31);
+    ehf = (t >> 5) & 1;
+  }
+  const bool erow_ok = erow < a.R;
   const float nscale = -a.scale;  // dk was accumulated from -dS
-  if (row_ok && (a.nsplit > 1 || a.force_partial)) {
-    float* op = a.dpart + (((int64_t)(a.sp0 + sp) * a.B + b) * a.R + row) * C + h * D;
+  if (erow_ok && (a.nsplit > 1 || a.force_partial)) {
+    float* op = a.dpart + (((int64_t)(a.sp0 + sp) * a.B + b) * a.R + erow) * C + h * D;
 #pragma unroll
     for (int db = 0; db < DB; ++db)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         f32x4 v = {dk[db][4 * g] * nscale, dk[db][4 * g + 1] * nscale, dk[db][4 * g + 2] * nscale, dk[db][4 * g + 3] * nscale};
-        *reinterpret_cast<f32x4*>(op + db * 32 + 8 * g + 4 * hf) = v;
+        *reinterpret_cast<f32x4*>(op + db * 32 + 8 * g + 4 * ehf) = v;
       }
-  } else if (row_ok) {
-    T16* op = reinterpret_cast<T16*>(a.drows) + ((int64_t)b * a.R + row) * C + h * D;
+  } else if (erow_ok) {
+    T16* op = reinterpret_cast<T16*>(a.drows) + ((int64_t)b * a.R + erow) * C + h * D;
 #pragma unroll
     for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -290,7 +381,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_rows_kernel(BwdArgs a) {
         u32x2 wv;
         wv[0] = pack2<DT>(dk[db][4 * g + 0] * nscale, dk[db][4 * g + 1] * nscale);
         wv[1] = pack2<DT>(dk[db][4 * g + 2] * nscale, dk[db][4 * g + 3] * nscale);
-        *reinterpret_cast<u32x2*>(op + db * 32 + 8 * g + 4 * hf) = wv;
+        *reinterpret_cast<u32x2*>(op + db * 32 + 8 * g + 4 * ehf) = wv;
       }
   }
 }
@@ -707,12 +798,29 @@ static void launch_rows_sum(const BwdArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((flash_bwd_rows_sum<DT, D>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, a);
 }
 
+// The three-per-CU instantiation (pre-scaled, D <= 96), empty where there is none: the launcher and
+// the planner both ask here.
+template <int DT, int D>
+static Kern<BwdArgs> rows3_kern() {
+  if constexpr (D <= 96) return kern<flash_bwd_rows_kernel<DT, D, true, 3>, Rows3Cfg<D>::NBUF * Rows3Cfg<D>::STAGE>();
+  else return Kern<BwdArgs>{};
+}
+
+// Workgroups per CU of this launch: XDOT_ROWS_WPC (read per call) through rows_wpc (flash_plan.h)
+template <int DT, int D>
+static int rows_launch_wpc(const BwdArgs& a) {
+  const auto k3 = rows3_kern<DT, D>();
+  if (!a.prescaled || !k3) return 2;
+  return rows_wpc(a.B, a.R, a.H, a.nsplit, env_int("XDOT_ROWS_WPC", 2, 3), k3.wgs_per_cu(), xdot_num_cus());
+}
+
 template <int DT, int D>
 static void launch_bwd_rows(const BwdArgs& a, hipStream_t st) {
   const int nrb = (a.R + 127) / 128;
   constexpr int LDS = RowsCfg<D>::NBUF * RowsCfg<D>::STAGE;
   const dim3 grid(nrb * a.B * a.H * a.nsplit);
-  if (a.prescaled) hipLaunchKernelGGL((flash_bwd_rows_kernel<DT, D, true>), grid, dim3(256), LDS, st, a);
+  if (rows_launch_wpc<DT, D>(a) == 3) rows3_kern<DT, D>().launch(grid, st, a);
+  else if (a.prescaled) hipLaunchKernelGGL((flash_bwd_rows_kernel<DT, D, true>), grid, dim3(256), LDS, st, a);
   else hipLaunchKernelGGL((flash_bwd_rows_kernel<DT, D, false>), grid, dim3(256), LDS, st, a);
   if (a.nsplit > 1 && !a.force_partial) launch_rows_sum<DT, D>(a, st);
 }
@@ -805,6 +913,14 @@ extern "C" int xdot_flash_bwd_rows_sum_launch(const xdot::fa::BwdArgs* a, int dt
     launch_rows_sum<decltype(t)::value, decltype(d)::value>(*a, st);
     return 0;
   });
+}
+
+// workgroups per CU of the 16-bit row-side kernel this launch would run (2 or 3); 0: another family
+extern "C" int xdot_flash_bwd_rows_wpc(const xdot::fa::BwdArgs* a, int dt, int D) {
+  using namespace xdot;
+  using namespace xdot::fa;
+  if (D > 128 || dt == DT_F32) return 0;
+  return for_dtype16_head_dim(dt, D, 0, [&](auto t, auto d) { return rows_launch_wpc<decltype(t)::value, decltype(d)::value>(*a); });
 }
 
 extern "C" int xdot_flash_bwd_rows_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st) {

@@ -387,6 +387,13 @@ template <int D> struct RowsCfg {
   static constexpr int PF = NBUF - 1;
   static constexpr int NG = 2 * IPW + 2;
 };
+// The same stage in a two-stage ring, one tile ahead: three workgroups per CU (D = 96: 3 x 2 x
+// 26112 = 156672 of the 160 KiB).  The three-per-CU row-side backward kernel (flash_bwd.hip).
+template <int D> struct Rows3Cfg : RowsCfg<D> {
+  static constexpr int NBUF = 2;
+  static constexpr int PF = NBUF - 1;
+  static_assert(3 * NBUF * RowsCfg<D>::STAGE <= 160 * 1024, "three workgroups per CU");
+};
 
 // Tile flags travel with their tile through the LDS ring (a scalar load per tile would put
 // its ~µs latency and an lgkmcnt(0) on every iteration's critical path).  One 4-byte DMA per

@@ -59,6 +59,29 @@ inline int rows_split(int64_t B, int64_t R, int64_t T, int64_t H) {
   return std::max(base, (int)conc);
 }
 
+// Rounds of a row-side backward launch: its row blocks x column splits over the resident slots of
+// the instantiation that runs it (workgroups per CU x CUs: 512 for the two-per-CU kernel, 768 for
+// the three-per-CU one).  rows_split above stays the split of both: the split fixes the order of
+// the partial sums, and a launch gives the same bits whichever instantiation runs it.
+inline int64_t rows_rounds(int64_t B, int64_t R, int64_t H, int64_t nsplit, int wgs_per_cu, int cus = 256) {
+  const int64_t wgs = ((R + 127) / 128) * B * H * std::max<int64_t>(1, nsplit);
+  const int64_t slots = std::max<int64_t>(1, (int64_t)wgs_per_cu * cus);
+  return (wgs + slots - 1) / slots;
+}
+
+// Workgroups per CU of a pre-scaled 16-bit row-side launch with D <= 96: 2 (the software-pipelined
+// kernel) or 3 (the plain-body kernel, csrc/flash_bwd.hip).  req: XDOT_ROWS_WPC (-1 = auto, 2, 3);
+// occ3: what the three-per-CU instantiation reports as resident (fewer than 3: there is no such
+// launch).  auto: profiles/rows_3wg.md.
+constexpr bool ROWS_WPC3_AUTO = true;
+inline int rows_wpc(int64_t B, int64_t R, int64_t H, int64_t nsplit, int req, int occ3, int cus = 256) {
+  if (occ3 < 3 || req == 2) return 2;
+  if (req == 3) return 3;
+  // a round of three per CU holds 1.5x the workgroups: it has to need fewer rounds to be considered
+  if (rows_rounds(B, R, H, nsplit, 3, cus) >= rows_rounds(B, R, H, nsplit, 2, cus)) return 2;
+  return ROWS_WPC3_AUTO ? 3 : 2;
+}
+
 // Row splits of a column-side launch: W workgroups of `nrt` 32-row tiles each, `slots` of them
 // resident at once.  Fewest splits minimising ceil(W s / slots) / s (the idle share of the last
 // round), each split >= 16 tiles, at most `maxs` splits, `per` charged per extra split (partials +

@@ -327,6 +327,10 @@ int xdot_flash_bwd_delta_launch(const xdot::fa::BwdArgs* a, const void* out, flo
 // gathered-side grads; a->delta must hold δ
 int xdot_flash_bwd_cols_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st);
 int xdot_flash_bwd_rows_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st);
+// workgroups per CU of the 16-bit row-side kernel that launch would run: 2, or 3 (pre-scaled, D <= 96,
+// XDOT_ROWS_WPC through rows_wpc of flash_plan.h); 0 = not the 16-bit D <= 128 family.  Reads a->B/R/H,
+// a->nsplit and a->prescaled
+int xdot_flash_bwd_rows_wpc(const xdot::fa::BwdArgs* a, int dt, int D);
 // software-pipelined column kernel (csrc/flash_cols.hip): pre-scaled 16-bit, D <= 96; -1 = not taken
 int xdot_flash_bwd_cols2_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st);
 // out (n elements, dtype dto) = Σ_s part[s] (fp32 partials, n % 4 == 0)

@@ -97,6 +97,11 @@ variable                    default   effect
                                       tail (fp32 partials, ordered sum; auto: occupancy round
                                       model; n: n splits <= 4, also for the 16-bit pipelined kernel,
                                       whose auto is 1)
+``XDOT_ROWS_WPC`` (C++)      auto      workgroups per CU of the 16-bit row-side backward kernel, pre-scaled
+                                      launches with D <= 96: 2 = the software-pipelined kernel, 3 = the
+                                      plain-body kernel (two-stage ring; bitwise the same result), auto =
+                                      ``rows_wpc`` of ``csrc/flash_plan.h`` (profiles/rows_3wg.md); read
+                                      per call
 ``XDOT_F32_SPLIT`` (C++)     auto      column splits of the fp32 forward / row-side kernels: auto =
                                       occupancy round model of the fp32 instantiation (up to 8);
                                       fwd = forward only; old = the 16-bit model; n = forced
