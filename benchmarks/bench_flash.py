@@ -48,13 +48,16 @@ def main():
                     help="with --mask: fraction of randomly masked entries (0: all-False)")
     ap.add_argument("--nsplit", type=int, default=0)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
-    ap.add_argument("--fp32-mode", default=None, choices=["split", "exact"],
+    ap.add_argument("--fp32-mode", default=None, choices=["split", "split3", "exact"],
                     help="fp32 kernel family (default: XDOT_FP32_MODE)")
     ap.add_argument("--no-prescale", action="store_true",
                     help="kernels scale every score (default: pre-scaled rows + seeded accumulators, the module's path)")
     ap.add_argument("--scores", action="store_true",
                     help="fp32 (exact or split): score-buffer mode (forward stores S, bwd_cols reads S and writes dS, "
                          "bwd_rows reads dS; products 2 / 3 / 1 instead of 2 / 4 / 3)")
+    ap.add_argument("--ds-only", action="store_true",
+                    help="fp32: dS-buffer mode, the split families' default schedule (the forward stores nothing, "
+                         "bwd_cols recomputes S and stores dS, bwd_rows reads dS; products 2 / 4 / 1)")
     ap.add_argument("--torch", action="store_true", help="also time torch SDPA (aotriton) on the same shape")
     ap.add_argument("--concurrent", action="store_true",
                     help="also time bwd_cols and bwd_rows launched together on two streams (cols on a normal "
@@ -89,13 +92,18 @@ def main():
         assert dt == torch.float32, "--scores is an fp32 (exact or split) mode"
         sb = flash.score_buffer(B, H, R, T, dev)
         assert sb is not None, "score buffer does not fit"
+    dsb = None
+    if a.ds_only:
+        assert dt == torch.float32 and sb is None, "--ds-only is an fp32 mode without --scores"
+        dsb = flash.score_buffer(B, H, R, T, dev)
+        assert dsb is not None, "dS buffer does not fit"
     # (timing only: after the first bwd_cols the buffer holds dS, which later calls read as S)
     out, lse = flash.fwd(rk, kc, vc, mk, H, scale, a.nsplit, prescaled=ps, sbuf=sb)
     # score-buffer mode: the fused exact column pass where the module uses it (XDOT_F32_FUSED_COLS)
     cpasses = 4 if sb is not None and flash.fused_cols_wanted(flash.fp32_code(dt), D) else 3
-    dkv, delta = flash.bwd_cols(do, rk, kc, vc, out, lse, mk, H, scale, prescaled=ps, sbuf=sb, passes=cpasses)
+    dkv, delta = flash.bwd_cols(do, rk, kc, vc, out, lse, mk, H, scale, prescaled=ps, sbuf=sb, dsbuf=dsb, passes=cpasses)
     gemm = 2.0 * B * R * T * H * D
-    np_cols, np_rows = (3, 1) if sb is not None else (4, 3)
+    np_cols, np_rows = (3, 1) if sb is not None else (4, 1) if dsb is not None else (4, 3)
     res = []
     if a.only in ("all", "mask") and mask is not None:
         ms, mn = timeit(lambda: flash.prepare_mask(mask, B, R, T), a.iters)
@@ -106,13 +114,13 @@ def main():
                     "TFLOPs": 2 * gemm / ms / 1e9})
     if a.only in ("all", "bwd_cols"):
         ms, mn = timeit(lambda: flash.bwd_cols(do, rk, kc, vc, out, lse, mk, H, scale, prescaled=ps, sbuf=sb,
-                                               passes=cpasses), a.iters)
-        res.append({"kernel": "flash_bwd_cols" + ("(S->dS)" if sb is not None else ""), "ms": ms, "min_ms": mn,
+                                               dsbuf=dsb, passes=cpasses), a.iters)
+        res.append({"kernel": "flash_bwd_cols" + ("(S->dS)" if sb is not None else "(->dS)" if dsb is not None else ""), "ms": ms, "min_ms": mn,
                     "TFLOPs": np_cols * gemm / ms / 1e9})
     if a.only in ("all", "bwd_rows"):
         ms, mn = timeit(lambda: flash.bwd_rows(do, rk, kc, vc, lse, delta, mk, H, scale, a.nsplit, prescaled=ps,
-                                               sbuf=sb), a.iters)
-        res.append({"kernel": "flash_bwd_rows" + ("(dS)" if sb is not None else ""), "ms": ms, "min_ms": mn,
+                                               sbuf=sb, dsbuf=dsb), a.iters)
+        res.append({"kernel": "flash_bwd_rows" + ("(dS)" if sb is not None or dsb is not None else ""), "ms": ms, "min_ms": mn,
                     "TFLOPs": np_rows * gemm / ms / 1e9})
     if a.concurrent:
         for prio in (0, -1):
@@ -148,6 +156,8 @@ def main():
         res.append({"kernel": "torch_sdpa_fwd+bwd", "ms": ms, "min_ms": mn, "TFLOPs": 7 * gemm / ms / 1e9})
     for r in res:
         r.update({"B": B, "R": R, "T": T, "H": H, "D": D})
+        if dt == torch.float32:
+            r["fp32_mode"] = a.fp32_mode or "default"
         print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}))
 
 

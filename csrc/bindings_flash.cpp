@@ -78,13 +78,15 @@ FlashGeom query_geom(int64_t B, int64_t R, int64_t T, int64_t H, int64_t D) {
 }
 
 // fp32 score buffer (flash_f32.hip exact, flash_x3.hip split): (B*H, ceil(R/32), ceil(T/32)) blocks
-// of 1024 floats
+// of 1024 floats.  ds: the dS buffer, which split3 (fp32_mode 2) takes too; it keeps no S buffer
 float* sbuf_ptr(const OptT& sbuf, const FlashGeom& g, int64_t H, const at::Tensor& rows, int64_t fp32_mode,
-                const char* what) {
+                const char* what, bool ds = false) {
   if (!sbuf.has_value() || !sbuf->defined()) return nullptr;
   const auto& t = *sbuf;
-  TORCH_CHECK(rows.scalar_type() == at::kFloat && (fp32_mode == 0 || fp32_mode == 1), what,
-              ": the score buffer is an fp32 (exact or split) feature");
+  TORCH_CHECK(rows.scalar_type() == at::kFloat && fp32_mode >= 0 && fp32_mode <= 2, what,
+              ": the score buffer is an fp32 (exact, split or split3) feature");
+  TORCH_CHECK(ds || fp32_mode != 2, what,
+              ": fp32_mode 2 (split3) keeps no S buffer (sbuf); it takes a dS buffer (dsbuf) or recomputes");
   const int64_t need = (g.B * H * ((g.R + 31) / 32) * ((g.T + 31) / 32) + 1) * 1024;  // + the dump block
   TORCH_CHECK(t.is_cuda() && t.device() == rows.device() && t.scalar_type() == at::kFloat && t.is_contiguous() &&
                   t.numel() == need && aligned16(t.data_ptr()),
@@ -177,6 +179,7 @@ A flash_args(const FlashGeom& g, const at::Tensor& rows, const at::Tensor& kc, c
   a.ldkv = g.ld;
   a.G = g.G > 1 ? (int)g.G : 0;
   a.gmul = g.G > 1 ? (int)(((1 << 20) + g.G - 1) / g.G) : 0;
+  TORCH_CHECK(fp32_mode >= 0 && fp32_mode <= 2, "xdot.flash: fp32_mode must be 0 (exact), 1 (split) or 2 (split3), got ", fp32_mode);
   a.prescaled = prescaled ? 1 : 0; a.fp32_mode = (int)fp32_mode;
   return a;
 }
@@ -296,7 +299,7 @@ std::tuple<at::Tensor, at::Tensor> flash_bwd_cols(const at::Tensor& dout, const 
   Range rr_("xdot.flash_bwd_cols");
   const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags, /*colmajor=*/true, Hg);
   float* sb = sbuf_ptr(sbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_cols");
-  float* dsb = sbuf_ptr(dsbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_cols (dS buffer)");
+  float* dsb = sbuf_ptr(dsbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_cols (dS buffer)", true);
   // a dS buffer alone: dS-only mode (the recomputing column kernel stores dS, D <= 128)
   TORCH_CHECK(!dsb || sb || g.D <= 128, "xdot.flash_bwd_cols: a dS buffer without the score buffer needs D <= 128");
   TORCH_CHECK(out.sizes() == rows.sizes() && out.is_contiguous() && out.scalar_type() == rows.scalar_type(),
@@ -433,7 +436,7 @@ at::Tensor flash_bwd_rows(const at::Tensor& dout, const at::Tensor& rows, const 
   Range rr_("xdot.flash_bwd_rows");
   const FlashGeom g = flash_check(rows, kc, vc, H, bits, flags, false, Hg);
   float* sb = sbuf_ptr(sbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_rows");
-  float* dsb = sbuf_ptr(dsbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_rows (dS buffer)");
+  float* dsb = sbuf_ptr(dsbuf, g, H, rows, fp32_mode, "xdot.flash_bwd_rows (dS buffer)", true);
   TORCH_CHECK(!dsb || sb || g.D <= 128, "xdot.flash_bwd_rows: a dS buffer without the score buffer needs D <= 128");
   check_bhr(delta, g.B, H, g.R, rows.device(), "xdot.flash_bwd_rows: delta");
   auto a = bwd_args(g, dout, rows, kc, vc, lse, bits, flags, H, scale, prescaled, fp32_mode);

@@ -885,7 +885,7 @@ extern "C" int xdot_flash_f32_row_splits(int kernel, int fp32_mode, int D, bool 
   } else if (!dflt) {
     return (int)std::min<int64_t>(xdot::fa::env_int("XDOT_F32_SPLIT", 0), (T + 31) / 32);
   }
-  return fp32_mode ? xdot_flash_f32_row_splits_x3(kernel, D, sbuf, W, T)
+  return fp32_mode ? xdot_flash_f32_row_splits_x3(kernel, fp32_mode, D, sbuf, W, T)
                    : xdot_flash_f32_row_splits_exact(kernel, D, sbuf, W, T);
 }
 

@@ -55,7 +55,7 @@ struct FwdArgs {
   int prescaled;           // 1: rows hold K * scale * log2(e) (xdot_prescale_rows_launch)
   float* out32;            // combine only: non-null -> write the merged O in fp32 here (fully
                            // masked rows: 0 with lse -inf), a running partial for the ring
-  int fp32_mode;           // fp32 inputs: 0 exact (flash_f32.hip), 1 split-bf16 (flash_x3.hip)
+  int fp32_mode;           // fp32 inputs: 0 exact (flash_f32.hip), 1 split-bf16 (flash_x3.hip), 2 split3 (flash_x6.hip)
   // head-heavy grid (16-bit forward, xrbs > 0): XCD x = blockIdx % 8 owns row blocks
   // [x*xrbs, (x+1)*xrbs) (linear index bh*nrb + rb); the first xwhole run whole, the last xrem
   // are split into nsplit column pieces whose partials go to a compact buffer
@@ -93,7 +93,7 @@ struct BwdArgs {
   int sp0;                 // first partial slot of this launch (chunked launches)
   int force_partial;       // 1: write partials even with nsplit == 1 (summed separately)
   int prescaled;           // 1: rows hold K * scale * log2(e) (same buffer as the forward's)
-  int fp32_mode;           // fp32 inputs: 0 exact (flash_f32.hip), 1 split-bf16 (flash_x3.hip)
+  int fp32_mode;           // fp32 inputs: 0 exact (flash_f32.hip), 1 split-bf16 (flash_x3.hip), 2 split3 (flash_x6.hip)
   // fp32 (exact / split): the forward's score buffer (FwdArgs::sbuf).  The column kernel reads S
   // from it instead of recomputing it and writes dS; the row kernel then reads dS
   float* sbuf;
@@ -405,10 +405,10 @@ int xdot_flash_cols_splits_cols2(const xdot::fa::BwdArgs* a, int dt, int D, int*
 // column splits of the fp32 row-block kernels (kernel 0: forward, 1: row-side backward; sbuf: the
 // kernel the launcher picks with a score / dS buffer) for W unsplit workgroups over T columns:
 // occupancy of that instantiation x CUs, round model (XDOT_F32_SPLIT: unset / auto = model, "old" =
-// the 16-bit model, n = forced); 0: not handled.  _exact / _x3: the two families' own kernels
+// the 16-bit model, n = forced); 0: not handled.  _exact / _x3: the families' own kernels (_x3: fp32_mode 1 / 2)
 int xdot_flash_f32_row_splits(int kernel, int fp32_mode, int D, bool sbuf, int64_t W, int64_t T);
 int xdot_flash_f32_row_splits_exact(int kernel, int D, bool sbuf, int64_t W, int64_t T);
-int xdot_flash_f32_row_splits_x3(int kernel, int D, bool sbuf, int64_t W, int64_t T);
+int xdot_flash_f32_row_splits_x3(int kernel, int fp32_mode, int D, bool sbuf, int64_t W, int64_t T);
 // split counts of the wide (D > 128) kernels from their own occupancy: kernel 0 / 1 = column
 // splits of the forward / row side (0: use the caller's model), 2 / 3 = row splits of the
 // column side's dQ / dV pass (XDOT_WIDE_SPLIT: auto, 0 = off, n = forced)
@@ -420,7 +420,8 @@ int xdot_flash_rows_sum_f32_launch(const xdot::fa::BwdArgs* a, int D, hipStream_
 int xdot_flash_wide_fwd_launch(const xdot::fa::FwdArgs* a, int dt, int D, hipStream_t st);
 int xdot_flash_wide_rows_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st);
 int xdot_flash_wide_cols_launch(const xdot::fa::BwdArgs* a, int dt, int D, hipStream_t st);
-// split-bf16 fp32 family (csrc/flash_x3.hip, fp32_mode = 1); prep / combine / sum are shared
+// split-bf16 fp32 families (csrc/flash_x3.hip: fp32_mode = 1 two-way, 2 three-way with the kernels of
+// csrc/flash_x6.hip); prep / combine / sum are shared
 int xdot_flash_fwd_x3_launch(const xdot::fa::FwdArgs* a, int D, hipStream_t st);
 int xdot_flash_bwd_rows_x3_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st);
 int xdot_flash_bwd_cols_x3_launch(const xdot::fa::BwdArgs* a, int D, hipStream_t st);

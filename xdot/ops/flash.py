@@ -272,13 +272,16 @@ def prescale(rows: torch.Tensor, scale: float) -> torch.Tensor:
     return _ext.ops().flash_prescale(rows.contiguous(), float(scale))
 
 
-FP32_MODES = {"exact": 0, "split": 1}
+FP32_MODES = {"exact": 0, "split": 1, "split3": 2}
 
 
 def fp32_code(dtype: torch.dtype, mode: Optional[str] = None) -> int:
     """Kernel family of fp32 operands: 0 exact fp32 (``csrc/flash_f32.hip``, the default: ~5e-7
     relative error vs fp64, the reference's precision), 1 split-bf16 (``csrc/flash_x3.hip``,
-    opt-in: 3 bf16 MFMAs per product, <= 9e-6; profiles/r3_fp32_split.md).  ``mode`` None: ``XDOT_FP32_MODE``.  0 for 16-bit dtypes."""
+    opt-in: 3 bf16 MFMAs per product, <= 9e-6; profiles/r3_fp32_split.md), 2 split3
+    (``csrc/flash_x6.hip``, opt-in: three bf16 parts per operand, 6 bf16 MFMAs per product, the exact
+    family's error; D <= 128, no S buffer: a dS buffer or recompute; profiles/split3.md).
+    ``mode`` None: ``XDOT_FP32_MODE``.  0 for 16-bit dtypes."""
     if dtype != torch.float32:
         return 0
     mode = FLAGS.fp32_mode if mode is None else mode
@@ -347,15 +350,16 @@ def score_buffers(B: int, H: int, R: int, T: int, device, dsbuf: bool = True):
 
 
 def ds_only_wanted(fp32_mode: int, D: int) -> bool:
-    """Whether fp32 family ``fp32_mode`` (0 exact, 1 split) at head dim ``D`` keeps only a dS
+    """Whether fp32 family ``fp32_mode`` (0 exact, 1 split, 2 split3) at head dim ``D`` keeps only a dS
     buffer (``XDOT_FP32_DS_ONLY``): the forward stores nothing, the single-pass column kernel
     recomputes S and stores dS, the row kernel reads dS.  The split family's kernels are bound by
     the score traffic (S written, read twice, dS written and read: 100 GB per step at T = R =
-    25000, H = 8); this mode moves 40 GB for one recomputed product on the column side."""
+    25000, H = 8); this mode moves 40 GB for one recomputed product on the column side.  split3 has
+    no S-buffer kernels: it keeps the dS buffer unless ``XDOT_FP32_DS_ONLY=none`` (then it recomputes)."""
     if D > 128:
         return False
     m = FLAGS.fp32_ds_only
-    return m == "all" or (m == "split" and fp32_mode == 1)
+    return m == "all" or (m == "split" and fp32_mode == 1) or (m != "none" and fp32_mode == 2)
 
 
 def fwd(rows: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, mk: Optional[PackedMask], H: int,
@@ -366,7 +370,7 @@ def fwd(rows: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, mk: Optional[Pac
 
     ``nsplit``: column splits (0 = auto: split only when R is too small to fill the GPU).
     ``prescaled``: ``rows`` is :func:`prescale` output.  ``fp32_mode``: :func:`fp32_code`
-    (None: from ``XDOT_FP32_MODE``).  ``sbuf``: fp32 (exact or split) only, a :func:`score_buffer` the
+    (None: from ``XDOT_FP32_MODE``).  ``sbuf``: fp32 (exact or split, not split3) only, a :func:`score_buffer` the
     raw scores are stored into for :func:`bwd_cols` / :func:`bwd_rows`."""
     bits, flags = _mask_args(mk)
     fm = fp32_code(rows.dtype) if fp32_mode is None else int(fp32_mode)

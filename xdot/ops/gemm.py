@@ -33,7 +33,8 @@ def strided_gemm(A, B, C, *, M, N, K, nseg=1, nb1=1, nb2=1, lda, ldb, ldc, sA1=0
     with the split-fp32 route allowed (what path 0 becomes for fp32 operands under
     ``XDOT_FP32_MODE=split``; the default ``exact`` keeps fp32 products on the exact fp32 MFMA kernel).
     ``FLAGS.fp32_mode`` is read here on every call: the one source of truth for the GEMMs too.
-    ``split_ok=False`` keeps an fp32 call on the exact kernels under either mode."""
+    ``split_ok=False`` keeps an fp32 call on the exact kernels under either mode.  ``split3`` is a
+    mode of the flash kernels alone: fp32 GEMMs (the distributed products too) stay exact under it."""
     _ext.ops().gemm(A, B, C, int(M), int(N), int(K), int(nseg), int(nb1), int(nb2), int(lda),
                     int(ldb), int(ldc), int(sA1), int(sA2), int(sB1), int(sB2), int(sC1), int(sC2),
                     int(sAseg), int(sBseg), bool(a_mc), bool(b_mc), float(alpha),

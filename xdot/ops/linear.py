@@ -57,11 +57,11 @@ def _proj_ok(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]
 def _f32_ok(*ts) -> bool:
     """Exact-fp32 products of a projection on the exact-fp32 GEMM kernels (through xdot.gemm with
     split_ok off): fp32 GPU tensors, ``XDOT_F32_PROJ`` on (the library's fp32 GEMM otherwise).
-    Under ``XDOT_FP32_MODE=split`` too: only the attention products take the split-bf16 route there
+    Under ``XDOT_FP32_MODE=split`` and ``split3`` too: only the attention products take the split-bf16 route there
     (the library's fp32 projections cost the split step 4.3 ms against 2.6 on these kernels,
     profiles/r5_fp32.md), the projections stay exact."""
     return (FLAGS.f32_proj and all(t is None or (t.dtype == torch.float32 and t.is_cuda) for t in ts)
-            and FLAGS.fp32_mode in ("exact", "split") and _ext.use_hip(*[t for t in ts if t is not None]))
+            and FLAGS.fp32_mode in ("exact", "split", "split3") and _ext.use_hip(*[t for t in ts if t is not None]))
 
 
 def _force() -> int:

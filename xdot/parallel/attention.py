@@ -421,7 +421,7 @@ def _score_buffers(k, H, T, fm, one_kernel, segmented):
             dsbuf = flash.score_buffer(B, H, R, T, k.device)
             if dsbuf is not None:
                 segmented = False
-        else:
+        elif fm != 2:  # (split3 keeps no S buffer: without the dS buffer it recomputes)
             # the fused exact column pass overwrites S with dS in place: no second buffer
             sbs = flash.score_buffers(B, H, R, T, k.device, dsbuf=not flash.fused_cols_wanted(fm, D))
             if sbs is not None:

@@ -44,9 +44,12 @@ variable                    default   effect
                                       (seeded score accumulators; forward 2.11 -> 1.98 ms)
 ``XDOT_FP32_MODE``          exact     fp32 flash kernels and fp32 GEMMs (read by Python only, per
                                       call; passed to the kernels): ``exact`` (fp32 MFMA, ~5e-7
-                                      relative vs fp64: the reference's precision) or ``split``
+                                      relative vs fp64: the reference's precision), ``split``
                                       (opt-in, like TF32: hi/lo bf16 halves, 3 bf16 products:
-                                      <= 9e-6 flash, <= 2e-5 GEMM; profiles/r3_fp32_split.md)
+                                      <= 9e-6 flash, <= 2e-5 GEMM; profiles/r3_fp32_split.md) or
+                                      ``split3`` (opt-in, flash kernels only, D <= 128: three bf16
+                                      parts, 6 bf16 products, the exact family's error; GEMMs and
+                                      wide heads stay exact; profiles/split3.md)
 ``XDOT_FP32_SCORES``        1         fp32 flash (exact and split): the forward stores the raw scores and the
                                       backward reads S / dS instead of recomputing them (6 fp32
                                       products per step instead of 9; needs R*T*H*4 bytes)
