@@ -427,6 +427,9 @@ TORCH_LIBRARY(xdot, m) {
   m.def("flash_bwd_prep(Tensor dout, Tensor out, Tensor lse, int H) -> (Tensor, Tensor)");
   m.def("flash_bwd_delta(Tensor dout, Tensor out, int H) -> Tensor");
   m.def("sum_partials(Tensor part, ScalarType out_dtype) -> Tensor");
+  m.def("flash_decode(Tensor rows, Tensor qc, Tensor vc, Tensor col_pos, int pos0, int window, int H, float scale, "
+        "int Hg=0, int nsplit=0, bool out_fp32=False) -> (Tensor, Tensor)");
+  m.def("flash_decode_plan(int B, int Hg, int G, int Rn, int Tcap) -> int");
   m.def("flash_splits(int B, int R, int T, int H, bool rows_kernel) -> int");
   m.def("flash_fwd_plan(int B, int R, int T, int H, int D, ScalarType dtype, int fp32_mode, bool sbuf, int nsplit) -> int[]");
   m.def("flash_rows_plan(int B, int R, int T, int H, int D, ScalarType dtype, int fp32_mode, bool prescaled, int nsplit) -> int[]");

@@ -452,6 +452,71 @@ at::Tensor flash_bwd_rows(const at::Tensor& dout, const at::Tensor& rows, const 
   return drows;
 }
 
+// ---- decode (csrc/flash_decode.hip) ----------------------------------------------------
+// Rn new rows at positions pos0, pos0 + 1, ... against one rank's cache qc / vc (B, Tcap, Hg*D) whose slot
+// positions are col_pos (B, Tcap) int32, -1 = empty: -> (out (B, Rn, H*D) in the rows' dtype, or fp32 with
+// out_fp32: the wire format of the cross-rank merge; lse (B, H, Rn)).  nsplit 0: plan_decode
+std::tuple<at::Tensor, at::Tensor> flash_decode(const at::Tensor& rows, const at::Tensor& qc, const at::Tensor& vc,
+                                                const at::Tensor& col_pos, int64_t pos0, int64_t window, int64_t H,
+                                                double scale, int64_t Hg, int64_t nsplit, bool out_fp32) {
+  Range rr_("xdot.flash_decode");
+  const char* op = "xdot.flash_decode: ";
+  TORCH_CHECK(rows.is_cuda() && qc.is_cuda() && vc.is_cuda() && col_pos.is_cuda() && qc.device() == rows.device() &&
+                  vc.device() == rows.device() && col_pos.device() == rows.device(),
+              op, "rows, qc, vc and col_pos must be tensors on one GPU");
+  TORCH_CHECK(rows.scalar_type() == at::kBFloat16 || rows.scalar_type() == at::kHalf, op, "bf16 / fp16 only, got ",
+              rows.scalar_type());
+  TORCH_CHECK(qc.scalar_type() == rows.scalar_type() && vc.scalar_type() == rows.scalar_type(), op,
+              "rows, qc and vc must have one dtype");
+  TORCH_CHECK(rows.dim() == 3 && rows.is_contiguous(), op, "rows must be a contiguous (B, Rn, H*D) tensor");
+  const int64_t B = rows.size(0), Rn = rows.size(1), C = rows.size(2), hg = Hg > 0 ? Hg : H;
+  TORCH_CHECK(H > 0 && C % H == 0 && hg <= H && H % hg == 0, op, "H = ", H, " must divide the row width ", C,
+              " and be a multiple of Hg = ", hg);
+  const int64_t D = C / H, G = H / hg;
+  TORCH_CHECK(D == 32 || D == 64 || D == 96 || D == 128, op, "head dim must be 32 / 64 / 96 / 128, got ", D);
+  TORCH_CHECK(B > 0 && Rn > 0 && decode_row_tiles(G, Rn) > 0, op, "G * Rn = ", G * Rn, " rows per gathered head, the kernel takes 1..",
+              DEC_MAX_ROWS);
+  TORCH_CHECK(qc.dim() == 3 && qc.size(0) == B && qc.size(2) == hg * D && vc.sizes() == qc.sizes() && qc.size(1) > 0,
+              op, "qc and vc must be (B, Tcap, Hg*D) = (", B, ", Tcap, ", hg * D, ")");
+  const int64_t Tcap = qc.size(1), ld = qc.stride(1);
+  for (const at::Tensor* t : {&qc, &vc}) {
+    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == ld && ld >= hg * D && ld % 8 == 0 && (B == 1 || t->stride(0) == Tcap * ld),
+                op, "qc and vc must be rows of unit inner stride with one row stride (a multiple of 8) and batch stride Tcap * row stride");
+    TORCH_CHECK((B - 1) * Tcap * ld + (Tcap - 1) * ld + hg * D <= avail_elems(*t), op, "cache view out of bounds");
+  }
+  TORCH_CHECK(aligned16(rows.data_ptr()) && aligned16(qc.data_ptr()) && aligned16(vc.data_ptr()), op, "16-byte alignment");
+  TORCH_CHECK(col_pos.scalar_type() == at::kInt && col_pos.dim() == 2 && col_pos.size(0) == B && col_pos.size(1) == Tcap &&
+                  col_pos.is_contiguous(),
+              op, "col_pos must be a contiguous int32 (B, Tcap) = (", B, ", ", Tcap, ") tensor, got ", col_pos.scalar_type(),
+              " ", col_pos.sizes());
+  TORCH_CHECK(pos0 >= 0 && pos0 + Rn < (1LL << 31) && window >= 0 && window < (1LL << 31), op,
+              "pos0 and window must be >= 0 and positions stay below 2^31");
+  TORCH_CHECK(Tcap < (1LL << 31) - DEC_TILE && B * Tcap * ld < (1LL << 40), op, "cache too large");
+  c10::DeviceGuard guard(rows.device());
+  const int64_t ntiles = (Tcap + DEC_TILE - 1) / DEC_TILE;
+  TORCH_CHECK(nsplit >= 0, op, "nsplit must be >= 0");
+  const int ns = nsplit > 0 ? (int)std::min(nsplit, ntiles) : plan_decode(B, hg, decode_row_tiles(G, Rn), Tcap, xdot_num_cus());
+  TORCH_CHECK((int64_t)ns * B * hg < (1LL << 31), op, "too many workgroups");
+  const auto f32 = rows.options().dtype(at::kFloat);
+  auto opart = at::empty({ns, B, Rn, C}, f32), lpart = at::empty({ns, B, H, Rn}, f32);
+  auto out = at::empty({B, Rn, C}, out_fp32 ? f32 : rows.options()), lse = at::empty({B, H, Rn}, f32);
+  DecodeArgs a{};
+  a.rows = rows.data_ptr(); a.qc = qc.data_ptr(); a.vc = vc.data_ptr(); a.col_pos = col_pos.data_ptr<int32_t>();
+  a.opart = opart.data_ptr<float>(); a.lpart = lpart.data_ptr<float>(); a.out = out.data_ptr(); a.lse = lse.data_ptr<float>();
+  a.B = (int)B; a.H = (int)H; a.Hg = (int)hg; a.Rn = (int)Rn; a.Tcap = (int)Tcap; a.ldkv = ld;
+  a.pos0 = (int)pos0; a.window = (int)window; a.scale = (float)scale;
+  a.nspan = ns; a.span_tiles = decode_span_tiles(Tcap, ns); a.out32 = out_fp32 ? 1 : 0;
+  launched(xdot_flash_decode_launch(&a, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "flash_decode");
+  return {out, lse};
+}
+
+// spans plan_decode gives this shape on the current device
+int64_t flash_decode_plan(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int64_t Tcap) {
+  const int nt = decode_row_tiles(G, Rn);
+  TORCH_CHECK(nt > 0 && B > 0 && Hg > 0 && Tcap > 0, "xdot.flash_decode_plan: shape");
+  return plan_decode(B, Hg, nt, Tcap, xdot_num_cus());
+}
+
 // ---- chunked launches (gather / reduce-scatter pipelining) ----------------------------
 // column splits the row-block kernels would use for (R rows, T columns) under the 16-bit model —
 // the partial / ring paths size their buffers with it
@@ -560,10 +625,12 @@ TORCH_LIBRARY_IMPL(xdot, CompositeExplicitAutograd, m) {
   m.impl("flash_fwd_plan", &flash_fwd_plan);
   m.impl("flash_cols_plan", &flash_cols_plan);
   m.impl("flash_rows_plan", &flash_rows_plan);
+  m.impl("flash_decode_plan", &flash_decode_plan);
 }
 
 TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("flash_fwd", &flash_fwd);
+  m.impl("flash_decode", &flash_decode);
   m.impl("flash_bwd_cols", &flash_bwd_cols);
   m.impl("flash_bwd_rows", &flash_bwd_rows);
   m.impl("flash_bwd_delta", &flash_bwd_delta);

@@ -144,5 +144,34 @@ inline bool head_heavy_plan(int64_t W, int64_t ntiles, int64_t S, int su, int* w
   return true;
 }
 
+// ---- decode (csrc/flash_decode.hip) --------------------------------------------------------------
+// The decode kernel sweeps the cache in tiles of DEC_TILE columns, one workgroup (4 waves, a tile each in
+// turn) per (column span, batch, gathered head), with the G * Rn rows of a gathered head packed into
+// 16-row MFMA tiles.
+constexpr int DEC_TILE = 32;
+constexpr int DEC_MAX_ROWS = 64;  // four row tiles
+// row tiles of a launch with G row heads per gathered head and Rn new rows; 0: more than the kernel takes
+inline int decode_row_tiles(int64_t G, int64_t Rn) {
+  const int64_t m = G * Rn;
+  return m >= 1 && m <= DEC_MAX_ROWS ? (int)((m + 15) / 16) : 0;
+}
+// tiles per span of a cache of Tcap slots cut into nspan spans
+inline int decode_span_tiles(int64_t Tcap, int nspan) {
+  const int64_t nt = (Tcap + DEC_TILE - 1) / DEC_TILE;
+  return (int)((nt + nspan - 1) / std::max(1, nspan));
+}
+// Column spans of a decode launch.  The kernel is bound by bandwidth and a workgroup keeps only 4 tiles
+// in flight, so the launch wants several resident workgroups on every CU (4 with one row tile, 3 with two,
+// 2 with more: the accumulators of a row tile cost registers), each span at least 8 tiles long (two per
+// wave: the per-workgroup merge and the partial slot are then a small share) and none of them empty.
+inline int plan_decode(int64_t B, int64_t Hg, int row_tiles, int64_t Tcap, int cus) {
+  const int64_t nt = (Tcap + DEC_TILE - 1) / DEC_TILE, heads = std::max<int64_t>(1, B * Hg);
+  const int64_t per_cu = row_tiles <= 1 ? 4 : row_tiles == 2 ? 3 : 2;
+  const int64_t want = (per_cu * std::max(1, cus) + heads - 1) / heads;
+  const int64_t s = std::max<int64_t>(1, std::min(want, nt / 8));
+  const int64_t len = (nt + s - 1) / s;
+  return (int)std::max<int64_t>(1, (nt + len - 1) / len);
+}
+
 }  // namespace fa
 }  // namespace xdot

@@ -123,6 +123,24 @@ struct BwdArgs {
   int G, gmul;
 };
 
+// decode (csrc/flash_decode.hip): Rn new rows at positions pos0, pos0 + 1, ... against one rank's cache
+struct DecodeArgs {
+  const void* rows;        // (B, Rn, H*D), not pre-scaled
+  const void* qc;          // cache (B, Tcap, ldkv), first Hg*D columns used
+  const void* vc;          // cache (B, Tcap, ldkv)
+  const int32_t* col_pos;  // (B, Tcap) global position of each slot, -1: empty
+  float* opart;            // (nspan, B, Rn, H*D) fp32 outputs normalised over their span
+  float* lpart;            // (nspan, B, H, Rn) natural-log LSE of the span, -inf: nothing visible
+  void* out;               // (B, Rn, H*D) in the rows' dtype, or fp32 with out32
+  float* lse;              // (B, H, Rn)
+  int B, H, Hg, Rn, Tcap;
+  int64_t ldkv;            // element stride between cache rows (Hg*D, or 2*Hg*D for a [q|v] buffer)
+  int pos0, window;        // window 0: none
+  float scale;             // softmax scale (not log2-scaled)
+  int nspan, span_tiles;   // column spans, and 32-column tiles per span (flash_plan.h)
+  int out32;
+};
+
 }  // namespace fa
 
 }  // namespace xdot
@@ -322,6 +340,9 @@ int xdot_mask_gen_launch(uint64_t* bits, uint64_t* bt, uint8_t* flags, const int
                          int causal, int64_t window, int64_t row_off, int B, int R, int T, const int* starts, int nstarts,
                          int64_t starts_stride, const int* rows, int nrows, hipStream_t st);
 int xdot_flash_fwd_launch(const xdot::fa::FwdArgs* a, int dt, int D, hipStream_t st);
+// decode: the span sweep into a->opart / a->lpart and their merge into a->out / a->lse (16-bit, D <= 128,
+// G * Rn <= 64: -1 otherwise)
+int xdot_flash_decode_launch(const xdot::fa::DecodeArgs* a, int dt, int D, hipStream_t st);
 // δ = rowsum(dO ⊙ O) (reads a->dout, a->B/R/H)
 int xdot_flash_bwd_delta_launch(const xdot::fa::BwdArgs* a, const void* out, float* delta, int dt, int D, hipStream_t st);
 // gathered-side grads; a->delta must hold δ

@@ -114,6 +114,7 @@ from ..parallel import attention as pa
 from ..parallel.autograd import FullMultiplication, RightTransposeMultiplication
 from ..parallel.ring import ring_attention_packed
 from ..parallel.layout import check_layout
+from ..parallel.decode import AttnCache, decode_attention
 from ..utils import comm as _comm
 from ..utils.env import FLAGS
 
@@ -416,6 +417,81 @@ class DistributedDotProductAttn(nn.Module):
                 b = self._w(_stacked_rows(self.queries.bias, self.values.bias))
             return linear(queries, w, b)
         return torch.cat([self._proj(self.queries, queries), self._proj(self.values, values)], dim=-1)
+
+    # ---- decode: generate against a cache (forward only, no autograd) -----------------------------
+    def _cdt(self, *xs: Tensor):
+        """The inputs in the compute dtype (one cast for an input passed twice)."""
+        cdt, cast = self.compute_dtype, {}
+        if cdt is None:
+            return xs
+        for x in xs:
+            if id(x) not in cast:
+                cast[id(x)] = x if x.dtype == cdt else x.to(cdt)
+        return tuple(cast[id(x)] for x in xs)
+
+    @staticmethod
+    def _pos_runs(pos, n: int):
+        """``pos`` (first position of ``n`` consecutive ones, or ``n`` positions) as the rotary table takes
+        it: an int, or row runs ``(local_start, length, global_start)``."""
+        if not isinstance(pos, Tensor):
+            return int(pos)
+        p = [int(x) for x in pos.reshape(-1).tolist()]
+        if len(p) != n:
+            raise ValueError(f"{len(p)} positions for {n} rows")
+        runs = []
+        for i, x in enumerate(p):
+            if runs and x == runs[-1][2] + runs[-1][1]:
+                runs[-1][1] += 1
+            else:
+                runs.append([i, 1, x])
+        return tuple(tuple(r) for r in runs)
+
+    def new_cache(self, batch: int, capacity: int, device=None) -> AttnCache:
+        """An empty :class:`xdot.AttnCache` of ``capacity`` slots for this rank's shard of this module's
+        gathered side: ``num_gathered_heads`` heads of the head dim, in the compute dtype."""
+        if self.value_dim // self.num_heads != self.dim:
+            raise ValueError("new_cache: the cache keeps [q | v] at one head dim; this module's value heads are "
+                             f"{self.value_dim // self.num_heads} wide, its key heads {self.dim}")
+        w = self.queries.weight
+        return AttnCache(batch, capacity, self.num_gathered_heads, self.dim, self.compute_dtype or w.dtype,
+                         w.device if device is None else device)
+
+    @torch.no_grad()
+    def cache_append(self, cache: AttnCache, queries: Tensor, values: Tensor, pos) -> None:
+        """Project ``queries`` / ``values`` (B, n, dim) to ``[q | v]``, norm and rotate ``q`` at ``pos`` (the
+        first of ``n`` consecutive global positions, or an ``(n,)`` tensor) and append the rows to ``cache``.
+        After a prefill forward: one call with this rank's rows and their first position (``rank * R``;
+        under ``layout='zigzag'`` two calls, one per run of :func:`xdot.parallel.layout.row_runs`).  While
+        generating: one call with the new token's row on the rank that owns it."""
+        with _ext.backend(self.backend):
+            queries, values = self._cdt(queries, values)
+            Hg = self.num_gathered_heads
+            qv = self._prep(self._project_qv(queries, values), Hg * self.dim, Hg, False, self._pos_runs(pos, queries.shape[1]))
+            cache.append(qv, pos)
+
+    @torch.no_grad()
+    def decode(self, keys: Tensor, cache: AttnCache, pos: int, window: Optional[int] = None) -> Tensor:
+        """The module's output (B, Rn, value_dim) for ``Rn`` new rows ``keys`` at global positions ``pos,
+        pos + 1, ...``, attending causally (and within ``window``) to what the ranks' caches hold: ``k``
+        projection, norm, rope at ``pos``, :func:`xdot.decode_attention` (sinks included), gate,
+        ``composition``.  Every rank passes the same ``keys`` and gets the same result; the rows themselves
+        must be in a cache to be attended, so their owner appends them first.  Which rank owns a token is
+        the caller's choice, e.g. round-robin::
+
+            for step in range(n_new):
+                if step % world_size == rank:
+                    module.cache_append(cache, x, x, T + step)
+                y = module.decode(x, cache, T + step)
+                x = next_input(y)
+        """
+        with _ext.backend(self.backend):
+            out_dt, H = keys.dtype, self.num_heads
+            (keys,) = self._cdt(keys)
+            comm = (self.comm or _comm.get_comm()) if self.distributed else _comm.LocalComm()
+            k = self._prep(self._proj(self.keys, keys), H * self.dim, H, True, int(pos))
+            o, _ = decode_attention(k, cache, int(pos), num_heads=H, scale=1.0 / math.sqrt(self.dim), window=window,
+                                    sinks=self.sinks, comm=comm)
+            return self._proj(self.composition, self._gated(o, keys)).to(out_dt)
 
     def _materialized(self, keys, queries, values, attn_mask, scale, comm, lay):
         H = self.num_heads

@@ -378,6 +378,83 @@ def fwd(rows: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, mk: Optional[Pac
                                 bool(prescaled), fm, sbuf, *_hg(Hg))
 
 
+# ---- decode: a few new rows against one rank's cache (csrc/flash_decode.hip) ----------------------
+DECODE_MAX_ROWS = 64   # G * Rn rows of one gathered head: four 16-row MFMA tiles
+_FWD_HEAD_DIMS = (32, 64, 96, 128, 160, 192, 256, 384)
+
+
+def decode_eligible(dtype: torch.dtype, D: int, Dv: int, G: int, Rn: int) -> bool:
+    """The decode kernel takes this call: 16-bit, one head dim of 32 / 64 / 96 / 128 for q and v, and at
+    most 64 rows (``G`` row heads x ``Rn`` new rows) per gathered head.  Everything else runs the
+    forward kernels over a dense mask (:func:`decode`).  Every eligible shape that was measured is
+    faster than that route (profiles/decode.md), so none is routed away."""
+    return (dtype in (torch.bfloat16, torch.float16) and D == Dv and D in (32, 64, 96, 128)
+            and 1 <= G * Rn <= DECODE_MAX_ROWS)
+
+
+def _pad_heads(x: torch.Tensor, h: int, Dp: int) -> torch.Tensor:
+    """(B, L, h*d) -> (B, L, h*Dp): every head zero-padded to ``Dp`` features (``x`` itself for d = Dp)."""
+    B, L, C = x.shape
+    if C // h == Dp:
+        return x
+    return torch.nn.functional.pad(x.reshape(B, L, h, C // h), (0, Dp - C // h)).reshape(B, L, h * Dp)
+
+
+def decode(rows: torch.Tensor, qc: torch.Tensor, vc: torch.Tensor, col_pos: torch.Tensor, pos0: int, H: int,
+           scale: float, window: int = 0, Hg: Optional[int] = None, nsplit: int = 0,
+           out_fp32: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Attention of ``Rn`` new rows over one rank's cache, forward only -> (out (B, Rn, H*Dv) in
+    ``rows.dtype``, lse (B, H, Rn) fp32 natural log).
+
+    ``rows`` (B, Rn, H*D): the new rows' ``k``, consecutive positions ``pos0, pos0 + 1, ...``, not
+    pre-scaled.  ``qc`` / ``vc`` (B, Tcap, Hg*D): the cache, unit inner stride, any common row stride
+    (the two halves of one ``[q|v]`` buffer).  ``col_pos`` (B, Tcap) int32: the global position of
+    each slot, -1 = empty.  Slot ``c`` is visible to row ``i`` iff ``0 <= col_pos[b, c] <= pos0 + i``
+    and (``window == 0`` or ``col_pos[b, c] > pos0 + i - window``): ``StructuredMask(causal=True,
+    window=window)`` for those rows, evaluated in the kernel, so the cache may be filled in any order
+    (contiguous, zigzag, round-robin appends) and no mask is built or packed.  Empty and invisible
+    slots must still hold finite values (their probability 0 multiplies them).  A row that sees
+    nothing comes out NaN with lse -inf, as from :func:`fwd`.
+
+    ``nsplit``: column spans (0: ``plan_decode`` of ``csrc/flash_plan.h``).  ``out_fp32``: ``out`` in
+    fp32, rounded once less (the wire format of :func:`xdot.decode_attention`'s cross-rank merge).
+
+    Calls the kernel does not take (:func:`decode_eligible`: fp32, D > 128, Dv != D, G * Rn > 64)
+    run :func:`fwd` over the dense mask of the same rule, packed per call, with grouped heads
+    repeated where :func:`fwd` has no grouped kernel and heads zero-padded to a common kernel width;
+    CPU tensors and ``backend='torch'`` run ``xdot.parallel._ref.decode``."""
+    B, Rn, C = rows.shape
+    hg = int(Hg) if Hg else int(H)
+    D, Dv, window = C // H, vc.shape[-1] // hg, int(window or 0)
+    if not _ext.use_hip(rows, qc, vc):
+        from ..parallel import _ref  # (xdot.parallel imports this module)
+
+        o, lse = _ref.decode(rows, qc, vc, col_pos, int(pos0), int(H), float(scale), window, Hg)
+        return (o if out_fp32 else o.to(rows.dtype)), lse
+    if decode_eligible(rows.dtype, D, Dv, H // hg, Rn):
+        return _ext.ops().flash_decode(rows.contiguous(), _kv(qc), _kv(vc), col_pos, int(pos0), window, int(H),
+                                       float(scale), hg, int(nsplit), bool(out_fp32))
+    from ..parallel._ref import decode_mask
+
+    Dp = next((d for d in _FWD_HEAD_DIMS if d >= max(D, Dv)), None)
+    if Dp is None:
+        raise ValueError(f"flash.decode: head dims ({D}, {Dv}) above the forward kernels' {_FWD_HEAD_DIMS[-1]}")
+    mk = prepare_mask(decode_mask(col_pos, int(pos0), Rn, window), B, Rn, qc.shape[1])
+    rows_p, qc, vc = _pad_heads(rows, H, Dp), _pad_heads(qc, hg, Dp), _pad_heads(vc, hg, Dp)
+    if hg != H and (rows.dtype == torch.float32 or Dp > 128):  # no grouped kernel there: heads repeated
+        qc, vc = (t.reshape(B, -1, hg, Dp).repeat_interleave(H // hg, dim=2).reshape(B, -1, H * Dp) for t in (qc, vc))
+        hg = H
+    o, lse = fwd(rows_p, qc, vc, mk, H, scale, Hg=hg if hg != H else None)
+    if Dp != Dv:
+        o = o.reshape(B, Rn, H, Dp)[..., :Dv].reshape(B, Rn, H * Dv)
+    return (o.float() if out_fp32 else o), lse
+
+
+def decode_plan(B: int, Hg: int, G: int, Rn: int, Tcap: int) -> int:
+    """Column spans an automatic :func:`decode` launch takes on the current device."""
+    return int(_ext.ops().flash_decode_plan(int(B), int(Hg), int(G), int(Rn), int(Tcap)))
+
+
 def bwd_delta(dout: torch.Tensor, out: torch.Tensor, H: int) -> torch.Tensor:
     """δ = rowsum(dO ⊙ O) per (b, h, row): fp32 (B, H, R)."""
     return _ext.ops().flash_bwd_delta(dout.contiguous(), out.contiguous(), int(H))

@@ -61,6 +61,23 @@ def block_fwd(k, kc, vc, mask, H: int, scale: float, Hg=None):
     return _merge(torch.matmul(p, gathered_heads(vc, H, Hg, cdt))), lse
 
 
+def decode_mask(col_pos, pos0: int, Rn: int, window: int = 0):
+    """The decode visibility rule as a dense mask (B, Rn, Tcap), True = masked: slot ``c`` of a cache whose
+    slot positions are ``col_pos`` (B, Tcap), -1 = empty, is visible to new row ``i`` at ``p_i = pos0 + i``
+    iff ``0 <= col_pos[c] <= p_i`` and (no ``window`` or ``col_pos[c] > p_i - window``):
+    ``StructuredMask(causal=True, window=window)`` for those rows, whatever order the cache was filled in."""
+    p = pos0 + torch.arange(Rn, device=col_pos.device, dtype=torch.int64).view(1, Rn, 1)
+    c = col_pos.to(torch.int64).unsqueeze(1)
+    m = (c < 0) | (c > p)
+    return m | (c <= p - int(window)) if window else m
+
+
+def decode(rows, qc, vc, col_pos, pos0: int, H: int, scale: float, window: int = 0, Hg=None):
+    """``Rn`` new rows against one cache shard -> (o (B, Rn, H*dv), lse (B, H, Rn)), compute dtype; a row
+    that sees nothing gets o = 0, lse = -inf."""
+    return block_fwd(rows, qc, vc, decode_mask(col_pos, pos0, rows.shape[1], window), H, scale, Hg)
+
+
 def combine(parts, dtype):
     """Merge segment partials [(o, lse)] -> (o in ``dtype``, lse); NaN for fully masked rows.  One
     part comes back bit for bit on its live rows (its weight is exactly 1)."""

@@ -1,0 +1,97 @@
+"""Decode: attention of a few new rows over a sequence-sharded ``q`` / ``v`` cache.
+
+In training the gathered side (``queries`` / ``values``) is sharded by rows and all-gathered every step.
+With a cache nothing is gathered: every rank keeps the ``(position, q, v)`` slots it owns, attends the
+new rows over its own shard (:func:`xdot.ops.flash.decode`, ``csrc/flash_decode.hip``), and only the
+fp32 ``(o, lse)`` cross the wire -- ``H*D + H`` floats per row -- to be merged like the column splits of
+a forward.  Softmax does not care about column order, so which rank holds which position, and in which
+slot, is free: contiguous or zigzag prefill shards, generated tokens appended round-robin.
+
+Forward only, no autograd.  Not covered: document masks at decode time, a device-side ``pos0`` (a
+captured generation loop), cache eviction."""
+from __future__ import annotations
+
+from typing import Optional, Tuple, Union
+
+import torch
+from torch import Tensor
+
+from .. import _ext
+from ..ops import flash
+from ..utils import comm as _comm
+from . import _ref
+
+__all__ = ["AttnCache", "decode_attention"]
+
+
+class AttnCache:
+    """One rank's shard of the gathered side: ``qv`` (B, capacity, 2*Hg*D), each slot ``[q | v]`` as the
+    module's packed projection lays it out (``q`` after norm and rope), ``pos`` (B, capacity) int32 the
+    global position of each slot (-1 = empty), and ``fill``, the slots taken, kept on the host."""
+
+    def __init__(self, batch: int, capacity: int, Hg: int, D: int, dtype: torch.dtype, device=None):
+        if min(int(batch), int(capacity), int(Hg), int(D)) < 1:
+            raise ValueError(f"AttnCache: batch, capacity, Hg and D must be positive, got {(batch, capacity, Hg, D)}")
+        self.Hg, self.D, self.capacity, self.fill = int(Hg), int(D), int(capacity), 0
+        # zeros: the kernels multiply empty slots' v by a probability of 0
+        self.qv = torch.zeros(int(batch), self.capacity, 2 * self.Hg * self.D, dtype=dtype, device=device)
+        self.pos = torch.full((int(batch), self.capacity), -1, dtype=torch.int32, device=device)
+
+    @property
+    def q(self) -> Tensor:
+        return self.qv[..., :self.Hg * self.D]
+
+    @property
+    def v(self) -> Tensor:
+        return self.qv[..., self.Hg * self.D:]
+
+    @torch.no_grad()
+    def append(self, qv: Tensor, positions: Union[int, Tensor]) -> None:
+        """Write ``qv`` (B, n, 2*Hg*D) into the next ``n`` free slots.  ``positions``: the global position
+        of the first of ``n`` consecutive ones (int), or an ``(n,)`` integer tensor."""
+        B, cap = self.pos.shape
+        if qv.dim() != 3 or qv.shape[0] != B or qv.shape[2] != self.qv.shape[2]:
+            raise ValueError(f"AttnCache.append: qv must be (B, n, 2*Hg*D) = ({B}, n, {self.qv.shape[2]}), got {tuple(qv.shape)}")
+        n, at = qv.shape[1], self.fill
+        if at + n > cap:
+            raise RuntimeError(f"AttnCache.append: {n} rows do not fit, {at} of {cap} slots are taken")
+        if isinstance(positions, Tensor):
+            if positions.numel() != n:
+                raise ValueError(f"AttnCache.append: {positions.numel()} positions for {n} rows")
+            p = positions.reshape(1, n).to(device=self.pos.device, dtype=torch.int32)
+        else:
+            p = torch.arange(int(positions), int(positions) + n, dtype=torch.int32, device=self.pos.device).view(1, n)
+        self.qv[:, at:at + n].copy_(qv)
+        self.pos[:, at:at + n] = p
+        self.fill = at + n
+
+
+@torch.no_grad()
+def decode_attention(rows: Tensor, cache: AttnCache, pos0: int, *, num_heads: int, scale: float,
+                     window: Optional[int] = None, sinks: Optional[Tensor] = None,
+                     comm: Optional[_comm.Communicator] = None) -> Tuple[Tensor, Tensor]:
+    """``rows`` (B, Rn, H*D), the new rows' ``k`` (after norm and rope) at positions ``pos0, pos0 + 1, ...``,
+    attended causally (and within ``window``) over the cache shards of all ranks -> (out (B, Rn, H*D) in
+    ``rows.dtype``, lse (B, H, Rn)).  All ranks pass the same ``rows`` and get the same result.
+
+    Each rank runs :func:`xdot.ops.flash.decode` over its own shard; with ``comm.world_size > 1`` one
+    all-gather of the fp32 ``[o | lse]`` and one merge over the ``N`` slots follow, then the sink fold
+    (``sinks`` (H,)), under which a row that sees nothing anywhere gives 0."""
+    comm = comm if comm is not None else _comm.get_comm()
+    H, n = int(num_heads), comm.world_size
+    o, lse = flash.decode(rows, cache.q, cache.v, cache.pos, int(pos0), H, scale, int(window or 0), Hg=cache.Hg,
+                          out_fp32=n > 1)
+    hip = _ext.use_hip(rows)
+    if n > 1:
+        no = o.numel()
+        wire = torch.cat([o.reshape(-1), lse.reshape(-1).to(o.dtype)])
+        got = torch.empty(n, wire.numel(), dtype=wire.dtype, device=wire.device)
+        comm.all_gather_into(got, wire)
+        opart, lpart = got[:, :no].reshape(n, *o.shape), got[:, no:].reshape(n, *lse.shape)
+        if hip:
+            o, lse = flash.fwd_combine(opart.contiguous(), lpart.contiguous(), H, rows)
+        else:
+            o, lse = _ref.combine([(opart[r], lpart[r]) for r in range(n)], rows.dtype)
+    if sinks is not None:
+        o, lse = (flash.sink_fold if hip else _ref.sink_fold)(o, lse, sinks, H)
+    return o, lse
