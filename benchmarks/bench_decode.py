@@ -6,6 +6,11 @@ the 10th / 90th percentiles.  Before timing, the two routes' outputs at the time
 the forward test bounds.  Also printed: the bytes the algorithm must read, ``B * Tcap * (2 * Hg * D * 2 +
 4)``, over the decode time, next to a device copy of as many bytes.  One JSON line per shape.
 
+Every shape also runs over an fp8 cache (csrc/flash_decode8.hip; ``decode_fp8``, in the same repetitions):
+the same values quantised by ``AttnCache.append``, its bytes ``B * Tcap * (2 * Hg * D + 8 * Hg + 4)``, and
+its output against the bf16-cache decode (the quantisation error of this input).  Last, ``cache_quant`` at
+n = 25000 and n = 1 rows beside a device copy of the bytes it reads.
+
     python benchmarks/bench_decode.py [--reps 40] [--warmup 10]
 """
 import argparse
@@ -48,6 +53,7 @@ def main():
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_decode: needs a GPU")
+    import xdot
     from xdot.ops import flash
     from xdot.parallel._ref import decode_mask
 
@@ -65,6 +71,9 @@ def main():
                 pos = torch.arange(Tcap, dtype=torch.int32, device=dev).repeat(B, 1)  # a full cache, in order
                 pos0 = Tcap - Rn
                 nbytes = B * Tcap * (2 * Hg * D * 2 + 4)
+                c8 = xdot.AttnCache(B, Tcap, Hg, D, dt, device=dev, cache_dtype="fp8")
+                c8.append(qv, 0)
+                nbytes8 = B * Tcap * (2 * Hg * D + 8 * Hg + 4)
                 src = torch.empty(nbytes, dtype=torch.uint8, device=dev)
                 dst = torch.empty_like(src)
 
@@ -73,12 +82,16 @@ def main():
 
                 mk = pack()
                 fns = {"decode": lambda: flash.decode(rows, qc, vc, pos, pos0, H, scale, Hg=Hg),
+                       "decode_fp8": lambda: flash.decode(rows, c8.q, c8.v, pos, pos0, H, scale, Hg=Hg, qscale=c8.qscale,
+                                                          vscale=c8.vscale),
                        "fwd": lambda: flash.fwd(rows, qc, vc, mk, H, scale, Hg=Hg if Hg != H else None),
                        "mask_pack": pack, "copy": lambda: dst.copy_(src)}
                 (o1, l1), (o2, l2) = fns["decode"](), fns["fwd"]()
                 fro = ((o1.float() - o2.float()).norm() / o2.float().norm()).item()
                 dl = (l1 - l2).abs().max().item()
                 assert fro <= 1e-2 and dl < 1e-2, f"routes disagree at Tcap={Tcap} Hg={Hg} Rn={Rn}: {fro:.3e}, {dl:.3e}"
+                o8, l8 = fns["decode_fp8"]()
+                q8 = ((o8.float() - o1.float()).norm() / o1.float().norm()).item()
                 t = {k: _stats(v) for k, v in _timed(fns, a.reps, a.warmup).items()}
                 print(json.dumps({
                     "Tcap": Tcap, "Hg": Hg, "Rn": Rn, "spans": flash.decode_plan(B, Hg, H // Hg, Rn, Tcap),
@@ -86,7 +99,21 @@ def main():
                     "speedup_vs_fwd": round(t["fwd"]["median_ms"] / t["decode"]["median_ms"], 2),
                     "speedup_vs_fwd_and_pack": round((t["fwd"]["median_ms"] + t["mask_pack"]["median_ms"]) / t["decode"]["median_ms"], 2),
                     "decode_TBps": round(nbytes / t["decode"]["median_ms"] / 1e9, 3),
+                    "spans_fp8": flash.decode_plan(B, Hg, H // Hg, Rn, Tcap, fp8_head_dim=D),
+                    "fp8_vs_bf16_cache_rel_fro": round(q8, 6), "fp8_vs_bf16_cache_lse_diff": round((l8 - l1).abs().max().item(), 6),
+                    "speedup_fp8_vs_bf16_cache": round(t["decode"]["median_ms"] / t["decode_fp8"]["median_ms"], 2),
+                    "decode_fp8_TBps": round(nbytes8 / t["decode_fp8"]["median_ms"] / 1e9, 3),
                     "copy_read_TBps": round(nbytes / t["copy"]["median_ms"] / 1e9, 3)}), flush=True)
+    Hg = 8
+    for n in (25000, 1):
+        x = torch.randn(B, n, 2 * Hg * D, generator=torch.Generator().manual_seed(n)).to(dev, dt)
+        c8 = xdot.AttnCache(B, n, Hg, D, dt, device=dev, cache_dtype="fp8")
+        dst = torch.empty_like(x)
+        t = {k: _stats(v) for k, v in _timed({"cache_quant": lambda: torch.ops.xdot.cache_quant(x, c8.qv, c8.scales, 0, Hg),
+                                              "copy": lambda: dst.copy_(x)}, a.reps, a.warmup).items()}
+        print(json.dumps({"cache_quant_rows": n, "Hg": Hg, "read_bytes": x.numel() * 2, **t,
+                          "cache_quant_read_TBps": round(x.numel() * 2 / t["cache_quant"]["median_ms"] / 1e9, 3),
+                          "copy_read_TBps": round(x.numel() * 2 / t["copy"]["median_ms"] / 1e9, 3)}), flush=True)
 
 
 if __name__ == "__main__":

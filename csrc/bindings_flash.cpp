@@ -456,18 +456,25 @@ at::Tensor flash_bwd_rows(const at::Tensor& dout, const at::Tensor& rows, const 
 // Rn new rows at positions pos0, pos0 + 1, ... against one rank's cache qc / vc (B, Tcap, Hg*D) whose slot
 // positions are col_pos (B, Tcap) int32, -1 = empty: -> (out (B, Rn, H*D) in the rows' dtype, or fp32 with
 // out_fp32: the wire format of the cross-rank merge; lse (B, H, Rn)).  nsplit 0: plan_decode
-std::tuple<at::Tensor, at::Tensor> flash_decode(const at::Tensor& rows, const at::Tensor& qc, const at::Tensor& vc,
-                                                const at::Tensor& col_pos, int64_t pos0, int64_t window, int64_t H,
-                                                double scale, int64_t Hg, int64_t nsplit, bool out_fp32) {
-  Range rr_("xdot.flash_decode");
-  const char* op = "xdot.flash_decode: ";
+// qscale / vscale set: the cache is fp8 (e4m3fn bytes, row stride in bytes) with fp32 (B, Hg, Tcap) scale
+// views (csrc/flash_decode8.hip); every other check is the 16-bit call's.
+std::tuple<at::Tensor, at::Tensor> decode_call(const char* op, const at::Tensor& rows, const at::Tensor& qc, const at::Tensor& vc,
+                                               const at::Tensor* qscale, const at::Tensor* vscale, const at::Tensor& col_pos,
+                                               int64_t pos0, int64_t window, int64_t H, double scale, int64_t Hg,
+                                               int64_t nsplit, bool out_fp32) {
+  const bool fp8 = qscale != nullptr;
   TORCH_CHECK(rows.is_cuda() && qc.is_cuda() && vc.is_cuda() && col_pos.is_cuda() && qc.device() == rows.device() &&
                   vc.device() == rows.device() && col_pos.device() == rows.device(),
               op, "rows, qc, vc and col_pos must be tensors on one GPU");
   TORCH_CHECK(rows.scalar_type() == at::kBFloat16 || rows.scalar_type() == at::kHalf, op, "bf16 / fp16 only, got ",
               rows.scalar_type());
-  TORCH_CHECK(qc.scalar_type() == rows.scalar_type() && vc.scalar_type() == rows.scalar_type(), op,
-              "rows, qc and vc must have one dtype");
+  if (fp8) {
+    TORCH_CHECK(qc.scalar_type() == at::kFloat8_e4m3fn && vc.scalar_type() == at::kFloat8_e4m3fn, op,
+                "qc and vc must be float8_e4m3fn, got ", qc.scalar_type(), " and ", vc.scalar_type());
+  } else {
+    TORCH_CHECK(qc.scalar_type() == rows.scalar_type() && vc.scalar_type() == rows.scalar_type(), op,
+                "rows, qc and vc must have one dtype");
+  }
   TORCH_CHECK(rows.dim() == 3 && rows.is_contiguous(), op, "rows must be a contiguous (B, Rn, H*D) tensor");
   const int64_t B = rows.size(0), Rn = rows.size(1), C = rows.size(2), hg = Hg > 0 ? Hg : H;
   TORCH_CHECK(H > 0 && C % H == 0 && hg <= H && H % hg == 0, op, "H = ", H, " must divide the row width ", C,
@@ -478,10 +485,11 @@ std::tuple<at::Tensor, at::Tensor> flash_decode(const at::Tensor& rows, const at
               DEC_MAX_ROWS);
   TORCH_CHECK(qc.dim() == 3 && qc.size(0) == B && qc.size(2) == hg * D && vc.sizes() == qc.sizes() && qc.size(1) > 0,
               op, "qc and vc must be (B, Tcap, Hg*D) = (", B, ", Tcap, ", hg * D, ")");
-  const int64_t Tcap = qc.size(1), ld = qc.stride(1);
+  const int64_t Tcap = qc.size(1), ld = qc.stride(1), ldq = fp8 ? 16 : 8;  // rows on the 16-byte grid
   for (const at::Tensor* t : {&qc, &vc}) {
-    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == ld && ld >= hg * D && ld % 8 == 0 && (B == 1 || t->stride(0) == Tcap * ld),
-                op, "qc and vc must be rows of unit inner stride with one row stride (a multiple of 8) and batch stride Tcap * row stride");
+    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == ld && ld >= hg * D && ld % ldq == 0 && (B == 1 || t->stride(0) == Tcap * ld),
+                op, "qc and vc must be rows of unit inner stride with one row stride (a multiple of ", ldq,
+                ") and batch stride Tcap * row stride");
     TORCH_CHECK((B - 1) * Tcap * ld + (Tcap - 1) * ld + hg * D <= avail_elems(*t), op, "cache view out of bounds");
   }
   TORCH_CHECK(aligned16(rows.data_ptr()) && aligned16(qc.data_ptr()) && aligned16(vc.data_ptr()), op, "16-byte alignment");
@@ -492,10 +500,22 @@ std::tuple<at::Tensor, at::Tensor> flash_decode(const at::Tensor& rows, const at
   TORCH_CHECK(pos0 >= 0 && pos0 + Rn < (1LL << 31) && window >= 0 && window < (1LL << 31), op,
               "pos0 and window must be >= 0 and positions stay below 2^31");
   TORCH_CHECK(Tcap < (1LL << 31) - DEC_TILE && B * Tcap * ld < (1LL << 40), op, "cache too large");
+  if (fp8) {
+    for (const at::Tensor* t : {qscale, vscale}) {
+      TORCH_CHECK(t->is_cuda() && t->device() == rows.device() && t->scalar_type() == at::kFloat && t->dim() == 3 &&
+                      t->size(0) == B && t->size(1) == hg && t->size(2) == Tcap && t->stride(2) == 1 &&
+                      t->strides() == qscale->strides() && t->stride(1) >= Tcap && (B == 1 || t->stride(0) >= hg * t->stride(1)),
+                  op, "qscale and vscale must be fp32 (B, Hg, Tcap) = (", B, ", ", hg, ", ", Tcap,
+                  ") views on the rows' GPU with unit inner stride and the same strides");
+      TORCH_CHECK((B - 1) * t->stride(0) + (hg - 1) * t->stride(1) + Tcap <= avail_elems(*t), op, "scale view out of bounds");
+    }
+  }
   c10::DeviceGuard guard(rows.device());
   const int64_t ntiles = (Tcap + DEC_TILE - 1) / DEC_TILE;
   TORCH_CHECK(nsplit >= 0, op, "nsplit must be >= 0");
-  const int ns = nsplit > 0 ? (int)std::min(nsplit, ntiles) : plan_decode(B, hg, decode_row_tiles(G, Rn), Tcap, xdot_num_cus());
+  const int nrt = decode_row_tiles(G, Rn), cus = xdot_num_cus();
+  const int ns = nsplit > 0 ? (int)std::min(nsplit, ntiles)
+                            : fp8 ? plan_decode_fp8(B, hg, nrt, (int)D, Tcap, cus) : plan_decode(B, hg, nrt, Tcap, cus);
   TORCH_CHECK((int64_t)ns * B * hg < (1LL << 31), op, "too many workgroups");
   const auto f32 = rows.options().dtype(at::kFloat);
   auto opart = at::empty({ns, B, Rn, C}, f32), lpart = at::empty({ns, B, H, Rn}, f32);
@@ -506,8 +526,59 @@ std::tuple<at::Tensor, at::Tensor> flash_decode(const at::Tensor& rows, const at
   a.B = (int)B; a.H = (int)H; a.Hg = (int)hg; a.Rn = (int)Rn; a.Tcap = (int)Tcap; a.ldkv = ld;
   a.pos0 = (int)pos0; a.window = (int)window; a.scale = (float)scale;
   a.nspan = ns; a.span_tiles = decode_span_tiles(Tcap, ns); a.out32 = out_fp32 ? 1 : 0;
-  launched(xdot_flash_decode_launch(&a, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "flash_decode");
+  if (fp8) {
+    a.qscale = qscale->data_ptr<float>(); a.vscale = vscale->data_ptr<float>();
+    a.sc_head = hg > 1 ? qscale->stride(1) : 0; a.sc_batch = B > 1 ? qscale->stride(0) : 0;
+    launched(xdot_flash_decode8_launch(&a, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "flash_decode_fp8");
+  } else {
+    launched(xdot_flash_decode_launch(&a, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "flash_decode");
+  }
   return {out, lse};
+}
+
+std::tuple<at::Tensor, at::Tensor> flash_decode(const at::Tensor& rows, const at::Tensor& qc, const at::Tensor& vc,
+                                                const at::Tensor& col_pos, int64_t pos0, int64_t window, int64_t H,
+                                                double scale, int64_t Hg, int64_t nsplit, bool out_fp32) {
+  Range rr_("xdot.flash_decode");
+  return decode_call("xdot.flash_decode: ", rows, qc, vc, nullptr, nullptr, col_pos, pos0, window, H, scale, Hg, nsplit, out_fp32);
+}
+
+std::tuple<at::Tensor, at::Tensor> flash_decode_fp8(const at::Tensor& rows, const at::Tensor& qc, const at::Tensor& vc,
+                                                    const at::Tensor& qscale, const at::Tensor& vscale, const at::Tensor& col_pos,
+                                                    int64_t pos0, int64_t window, int64_t H, double scale, int64_t Hg,
+                                                    int64_t nsplit, bool out_fp32) {
+  Range rr_("xdot.flash_decode_fp8");
+  return decode_call("xdot.flash_decode_fp8: ", rows, qc, vc, &qscale, &vscale, col_pos, pos0, window, H, scale, Hg, nsplit, out_fp32);
+}
+
+// rows (B, n, 2*Hg*D) 16-bit, a row view of row_view.h -> e4m3 bytes and per-chunk scales in slots
+// [at, at + n) of an fp8 cache: qv8 (B, cap, 2*Hg*D) float8_e4m3fn, scales (B, 2*Hg, cap) fp32, both contiguous
+void cache_quant(const at::Tensor& rows, at::Tensor& qv8, at::Tensor& scales, int64_t at_, int64_t Hg) {
+  Range rr_("xdot.cache_quant");
+  const char* op = "xdot.cache_quant: ";
+  TORCH_CHECK(rows.is_cuda() && rows.dim() == 3 && (rows.scalar_type() == at::kBFloat16 || rows.scalar_type() == at::kHalf), op,
+              "rows must be a bf16 / fp16 (B, n, 2*Hg*D) tensor on a GPU");
+  const int64_t B = rows.size(0), n = rows.size(1), C = rows.size(2);
+  TORCH_CHECK(Hg > 0 && C % (2 * Hg) == 0, op, "the row width ", C, " must be a multiple of 2*Hg = ", 2 * Hg);
+  const int64_t D = C / (2 * Hg);
+  TORCH_CHECK(D == 32 || D == 64 || D == 96 || D == 128, op, "head dim must be 32 / 64 / 96 / 128, got ", D);
+  const auto v = row_view(rows, B, n, C, rows, false, "cache_quant", "rows");
+  TORCH_CHECK(v.vec, op, "rows must start and step on 16-byte boundaries");
+  TORCH_CHECK(qv8.is_cuda() && qv8.device() == rows.device() && qv8.scalar_type() == at::kFloat8_e4m3fn && qv8.dim() == 3 &&
+                  qv8.size(0) == B && qv8.size(2) == C && qv8.is_contiguous() && aligned16(qv8.data_ptr()),
+              op, "qv8 must be a contiguous float8_e4m3fn (B, capacity, 2*Hg*D) = (", B, ", capacity, ", C, ") tensor on the rows' GPU");
+  const int64_t cap = qv8.size(1);
+  TORCH_CHECK(scales.is_cuda() && scales.device() == rows.device() && scales.scalar_type() == at::kFloat && scales.dim() == 3 &&
+                  scales.size(0) == B && scales.size(1) == 2 * Hg && scales.size(2) == cap && scales.is_contiguous(),
+              op, "scales must be a contiguous fp32 (B, 2*Hg, capacity) = (", B, ", ", 2 * Hg, ", ", cap, ") tensor on the rows' GPU");
+  TORCH_CHECK(at_ >= 0 && at_ + n <= cap, op, "slots [", at_, ", ", at_ + n, ") outside the capacity ", cap);
+  TORCH_CHECK(cap < (1LL << 31) && n < (1LL << 31) && B < (1LL << 31), op, "cache too large");
+  if (B == 0 || n == 0) return;
+  QuantArgs a{};
+  a.rows = rows.data_ptr(); a.qv8 = qv8.data_ptr(); a.scales = scales.data_ptr<float>();
+  a.sb = v.sb; a.sr = v.sr; a.B = (int)B; a.n = (int)n; a.chunks = (int)(2 * Hg); a.cap = (int)cap; a.at = (int)at_;
+  c10::DeviceGuard guard(rows.device());
+  launched(xdot_cache_quant_launch(&a, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "cache_quant");
 }
 
 // spans plan_decode gives this shape on the current device
@@ -515,6 +586,12 @@ int64_t flash_decode_plan(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int64_t 
   const int nt = decode_row_tiles(G, Rn);
   TORCH_CHECK(nt > 0 && B > 0 && Hg > 0 && Tcap > 0, "xdot.flash_decode_plan: shape");
   return plan_decode(B, Hg, nt, Tcap, xdot_num_cus());
+}
+// the same for an fp8 cache of head dim D (plan_decode_fp8)
+int64_t flash_decode_fp8_plan(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int64_t D, int64_t Tcap) {
+  const int nt = decode_row_tiles(G, Rn);
+  TORCH_CHECK(nt > 0 && B > 0 && Hg > 0 && Tcap > 0 && D > 0, "xdot.flash_decode_fp8_plan: shape");
+  return plan_decode_fp8(B, Hg, nt, (int)D, Tcap, xdot_num_cus());
 }
 
 // ---- chunked launches (gather / reduce-scatter pipelining) ----------------------------
@@ -626,11 +703,14 @@ TORCH_LIBRARY_IMPL(xdot, CompositeExplicitAutograd, m) {
   m.impl("flash_cols_plan", &flash_cols_plan);
   m.impl("flash_rows_plan", &flash_rows_plan);
   m.impl("flash_decode_plan", &flash_decode_plan);
+  m.impl("flash_decode_fp8_plan", &flash_decode_fp8_plan);
 }
 
 TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("flash_fwd", &flash_fwd);
   m.impl("flash_decode", &flash_decode);
+  m.impl("flash_decode_fp8", &flash_decode_fp8);
+  m.impl("cache_quant", &cache_quant);
   m.impl("flash_bwd_cols", &flash_bwd_cols);
   m.impl("flash_bwd_rows", &flash_bwd_rows);
   m.impl("flash_bwd_delta", &flash_bwd_delta);

@@ -24,40 +24,10 @@
 //              lane's own 8 probabilities (no cross-lane move) and V^T comes from the wave-private
 //              [column][feature] LDS image of the v tile through two ds_read_b64_tr_b16 per 16 features.
 //              The lane ends with row n and features 16 dn + 4 g .. + 3: the same row as its statistics.
-#include "flash_launch.h"
+#include "flash_decode.h"
 
 namespace xdot {
 namespace fa {
-
-template <int DT> struct mfma16;
-template <> struct mfma16<DT_BF16> {
-  static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <> struct mfma16<DT_F16> {
-  static __device__ __forceinline__ f32x4 run(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-};
-
-// LDS of one workgroup: the 4 waves' v tiles (rows of 2 D + 16 bytes), reused after the sweep as the
-// fp32 output image the waves add into ([row][D + 4]), then the per-wave and the merged (m, l)
-template <int D, int NT> struct DecCfg {
-  static constexpr int VROW = 2 * D + 16;
-  static constexpr int VTILE = DEC_TILE * VROW;
-  static constexpr int OROW = D + 4;  // floats
-  static constexpr int OIMG = NT * 16 * OROW * 4;
-  static constexpr int OFF_STAT = (4 * VTILE > OIMG ? 4 * VTILE : OIMG);
-  static constexpr int LDS = OFF_STAT + (2 * 4 + 2) * NT * 16 * 4;
-};
-
-// order this wave's LDS accesses (the tile image is written by some lanes and read by others)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <int DT, int D, int NT>
 __global__ __launch_bounds__(256) void flash_decode_kernel(DecodeArgs a) {
@@ -340,6 +310,17 @@ static int launch_decode(const DecodeArgs& a, hipStream_t st) {
 
 }  // namespace fa
 }  // namespace xdot
+
+// the merge of a->opart / a->lpart over the spans alone (the fp8 sweep of flash_decode8.hip feeds it)
+extern "C" int xdot_flash_decode_combine_launch(const xdot::fa::DecodeArgs* a, int dt, int D, hipStream_t st) {
+  using namespace xdot;
+  using namespace xdot::fa;
+  return for_dtype16_head_dim(dt, D, -1, [&](auto t, auto d) {
+    hipLaunchKernelGGL((flash_decode_combine<decltype(t)::value, decltype(d)::value>), dim3((unsigned)(a->B * a->Rn * a->H)),
+                       dim3(256), 0, st, *a);
+    return 0;
+  });
+}
 
 // the span sweep into a->opart / a->lpart, then the merge into a->out / a->lse; -1: no kernel for this
 // dtype / head dim / G * Rn

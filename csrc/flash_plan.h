@@ -172,6 +172,22 @@ inline int plan_decode(int64_t B, int64_t Hg, int row_tiles, int64_t Tcap, int c
   const int64_t len = (nt + s - 1) / s;
   return (int)std::max<int64_t>(1, (nt + len - 1) / len);
 }
+// The same for the fp8 sweep (csrc/flash_decode8.hip).  Its tile is half the bytes, so a workgroup has half
+// as much in flight and a second round of spans has nothing to hide behind: the launch asks for exactly the
+// workgroups that are resident at once, the occupancy the compiler reports for the instantiation
+// (profiles/decode_fp8.md; D = 32 / 64 / 96 / 128 by 1 / 2 / 4 row tiles), under the same span rules.
+inline int decode_fp8_wgs_per_cu(int D, int row_tiles) {
+  static constexpr int occ[4][3] = {{5, 4, 2}, {4, 3, 1}, {3, 2, 1}, {2, 2, 1}};
+  const int d = std::max(0, std::min(3, D / 32 - 1));
+  return occ[d][row_tiles <= 1 ? 0 : row_tiles == 2 ? 1 : 2];
+}
+inline int plan_decode_fp8(int64_t B, int64_t Hg, int row_tiles, int D, int64_t Tcap, int cus) {
+  const int64_t nt = (Tcap + DEC_TILE - 1) / DEC_TILE, heads = std::max<int64_t>(1, B * Hg);
+  const int64_t want = ((int64_t)decode_fp8_wgs_per_cu(D, row_tiles) * std::max(1, cus) + heads - 1) / heads;
+  const int64_t s = std::max<int64_t>(1, std::min(want, nt / 8));
+  const int64_t len = (nt + s - 1) / s;
+  return (int)std::max<int64_t>(1, (nt + len - 1) / len);
+}
 
 }  // namespace fa
 }  // namespace xdot

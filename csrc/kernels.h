@@ -139,6 +139,21 @@ struct DecodeArgs {
   float scale;             // softmax scale (not log2-scaled)
   int nspan, span_tiles;   // column spans, and 32-column tiles per span (flash_plan.h)
   int out32;
+  // fp8 cache (csrc/flash_decode8.hip): qc / vc hold e4m3 bytes (ldkv in bytes), one fp32 scale per
+  // (batch, gathered head, slot) for each of them; unset for a 16-bit cache
+  const float* qscale;
+  const float* vscale;
+  int64_t sc_head, sc_batch;  // strides of both scale views between gathered heads / batches (floats)
+};
+
+// cache_quant (csrc/flash_decode8.hip): n rows of a 16-bit (B, n, 2*Hg*D) view -> e4m3 bytes and one
+// fp32 scale per chunk (the D features of one head of q or v) in slots [at, at + n) of an fp8 cache
+struct QuantArgs {
+  const void* rows;  // batch / row strides sb / sr in elements
+  void* qv8;         // (B, cap, 2*Hg*D) bytes
+  float* scales;     // (B, 2*Hg, cap)
+  int64_t sb, sr;
+  int B, n, chunks, cap, at;  // chunks = 2*Hg per row
 };
 
 }  // namespace fa
@@ -343,6 +358,11 @@ int xdot_flash_fwd_launch(const xdot::fa::FwdArgs* a, int dt, int D, hipStream_t
 // decode: the span sweep into a->opart / a->lpart and their merge into a->out / a->lse (16-bit, D <= 128,
 // G * Rn <= 64: -1 otherwise)
 int xdot_flash_decode_launch(const xdot::fa::DecodeArgs* a, int dt, int D, hipStream_t st);
+// the same over an fp8 cache with per-slot scales (a->qscale / a->vscale; dt: the rows' 16-bit dtype), and
+// the spans' merge alone
+int xdot_flash_decode8_launch(const xdot::fa::DecodeArgs* a, int dt, int D, hipStream_t st);
+int xdot_flash_decode_combine_launch(const xdot::fa::DecodeArgs* a, int dt, int D, hipStream_t st);
+int xdot_cache_quant_launch(const xdot::fa::QuantArgs* a, int dt, int D, hipStream_t st);
 // δ = rowsum(dO ⊙ O) (reads a->dout, a->B/R/H)
 int xdot_flash_bwd_delta_launch(const xdot::fa::BwdArgs* a, const void* out, float* delta, int dt, int D, hipStream_t st);
 // gathered-side grads; a->delta must hold δ

@@ -446,15 +446,16 @@ class DistributedDotProductAttn(nn.Module):
                 runs.append([i, 1, x])
         return tuple(tuple(r) for r in runs)
 
-    def new_cache(self, batch: int, capacity: int, device=None) -> AttnCache:
+    def new_cache(self, batch: int, capacity: int, device=None, cache_dtype=None) -> AttnCache:
         """An empty :class:`xdot.AttnCache` of ``capacity`` slots for this rank's shard of this module's
-        gathered side: ``num_gathered_heads`` heads of the head dim, in the compute dtype."""
+        gathered side: ``num_gathered_heads`` heads of the head dim, in the compute dtype, or with
+        ``cache_dtype="fp8"`` in e4m3fn bytes with per-slot scales (about half the memory and cache traffic)."""
         if self.value_dim // self.num_heads != self.dim:
             raise ValueError("new_cache: the cache keeps [q | v] at one head dim; this module's value heads are "
                              f"{self.value_dim // self.num_heads} wide, its key heads {self.dim}")
         w = self.queries.weight
         return AttnCache(batch, capacity, self.num_gathered_heads, self.dim, self.compute_dtype or w.dtype,
-                         w.device if device is None else device)
+                         w.device if device is None else device, cache_dtype=cache_dtype)
 
     @torch.no_grad()
     def cache_append(self, cache: AttnCache, queries: Tensor, values: Tensor, pos) -> None:

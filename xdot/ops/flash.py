@@ -383,11 +383,15 @@ DECODE_MAX_ROWS = 64   # G * Rn rows of one gathered head: four 16-row MFMA tile
 _FWD_HEAD_DIMS = (32, 64, 96, 128, 160, 192, 256, 384)
 
 
-def decode_eligible(dtype: torch.dtype, D: int, Dv: int, G: int, Rn: int) -> bool:
+def decode_eligible(dtype: torch.dtype, D: int, Dv: int, G: int, Rn: int, cache_dtype=None) -> bool:
     """The decode kernel takes this call: 16-bit, one head dim of 32 / 64 / 96 / 128 for q and v, and at
     most 64 rows (``G`` row heads x ``Rn`` new rows) per gathered head.  Everything else runs the
     forward kernels over a dense mask (:func:`decode`).  Every eligible shape that was measured is
-    faster than that route (profiles/decode.md), so none is routed away."""
+    faster than that route (profiles/decode.md), so none is routed away.  ``dtype`` is the rows';
+    ``cache_dtype`` ``torch.float8_e4m3fn`` asks for the fp8-cache kernel (csrc/flash_decode8.hip), which
+    takes the same shapes and is the only kernel that reads such a cache."""
+    if cache_dtype not in (None, dtype, torch.float8_e4m3fn):
+        return False
     return (dtype in (torch.bfloat16, torch.float16) and D == Dv and D in (32, 64, 96, 128)
             and 1 <= G * Rn <= DECODE_MAX_ROWS)
 
@@ -402,7 +406,8 @@ def _pad_heads(x: torch.Tensor, h: int, Dp: int) -> torch.Tensor:
 
 def decode(rows: torch.Tensor, qc: torch.Tensor, vc: torch.Tensor, col_pos: torch.Tensor, pos0: int, H: int,
            scale: float, window: int = 0, Hg: Optional[int] = None, nsplit: int = 0,
-           out_fp32: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+           out_fp32: bool = False, qscale: Optional[torch.Tensor] = None,
+           vscale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Attention of ``Rn`` new rows over one rank's cache, forward only -> (out (B, Rn, H*Dv) in
     ``rows.dtype``, lse (B, H, Rn) fp32 natural log).
 
@@ -422,10 +427,33 @@ def decode(rows: torch.Tensor, qc: torch.Tensor, vc: torch.Tensor, col_pos: torc
     Calls the kernel does not take (:func:`decode_eligible`: fp32, D > 128, Dv != D, G * Rn > 64)
     run :func:`fwd` over the dense mask of the same rule, packed per call, with grouped heads
     repeated where :func:`fwd` has no grouped kernel and heads zero-padded to a common kernel width;
-    CPU tensors and ``backend='torch'`` run ``xdot.parallel._ref.decode``."""
+    CPU tensors and ``backend='torch'`` run ``xdot.parallel._ref.decode``.
+
+    ``qscale`` / ``vscale`` (B, Hg, Tcap) fp32, unit inner stride: ``qc`` / ``vc`` are ``float8_e4m3fn`` and
+    slot ``c`` of gathered head ``h`` stands for ``qscale[b, h, c] * qc[b, c, h*D:(h+1)*D]`` (and likewise
+    ``v``): the format of :class:`xdot.AttnCache` with ``cache_dtype="fp8"``.  Eligible calls run the fp8
+    sweep (csrc/flash_decode8.hip), which applies the scales per column and reads the bytes as they are.
+    Every other call is the slow path: it first dequantises the whole cache into fp32 and runs the fp32
+    route of the call (the forward kernels over a dense mask on the GPU)."""
     B, Rn, C = rows.shape
     hg = int(Hg) if Hg else int(H)
     D, Dv, window = C // H, vc.shape[-1] // hg, int(window or 0)
+    if qscale is not None:
+        if vscale is None or qc.dtype != torch.float8_e4m3fn or vc.dtype != torch.float8_e4m3fn:
+            raise ValueError("flash.decode: qscale and vscale go together, with float8_e4m3fn qc and vc")
+        if _ext.use_hip(rows, qc, vc) and decode_eligible(rows.dtype, D, Dv, H // hg, Rn, torch.float8_e4m3fn):
+            return _ext.ops().flash_decode_fp8(rows.contiguous(), _kv(qc), _kv(vc), qscale, vscale, col_pos, int(pos0),
+                                               window, int(H), float(scale), hg, int(nsplit), bool(out_fp32))
+        from ..parallel import _ref
+
+        # scale * byte does not fit a 16-bit value: a cache dequantised into rows.dtype would be rounded a
+        # second time (measured: 2e-2 in the LSE at |scores| ~ 20), so the slow path computes in fp32
+        cdt = _ref.compute_dtype(rows)
+        qc, vc = ((t.to(cdt).reshape(B, -1, hg, t.shape[-1] // hg) * sc.to(cdt).transpose(1, 2).unsqueeze(-1)).reshape(t.shape)
+                  for t, sc in ((qc, qscale), (vc, vscale)))
+        if _ext.use_hip(rows, qc, vc):
+            o, lse = decode(rows.to(cdt), qc, vc, col_pos, pos0, H, scale, window, Hg, nsplit, out_fp32=True)
+            return (o if out_fp32 else o.to(rows.dtype)), lse
     if not _ext.use_hip(rows, qc, vc):
         from ..parallel import _ref  # (xdot.parallel imports this module)
 
@@ -450,8 +478,11 @@ def decode(rows: torch.Tensor, qc: torch.Tensor, vc: torch.Tensor, col_pos: torc
     return (o.float() if out_fp32 else o), lse
 
 
-def decode_plan(B: int, Hg: int, G: int, Rn: int, Tcap: int) -> int:
-    """Column spans an automatic :func:`decode` launch takes on the current device."""
+def decode_plan(B: int, Hg: int, G: int, Rn: int, Tcap: int, fp8_head_dim: int = 0) -> int:
+    """Column spans an automatic :func:`decode` launch takes on the current device; ``fp8_head_dim``: over
+    an fp8 cache of that head dim (``plan_decode_fp8``)."""
+    if fp8_head_dim:
+        return int(_ext.ops().flash_decode_fp8_plan(int(B), int(Hg), int(G), int(Rn), int(fp8_head_dim), int(Tcap)))
     return int(_ext.ops().flash_decode_plan(int(B), int(Hg), int(G), int(Rn), int(Tcap)))
 
 

@@ -78,6 +78,25 @@ def decode(rows, qc, vc, col_pos, pos0: int, H: int, scale: float, window: int =
     return block_fwd(rows, qc, vc, decode_mask(col_pos, pos0, rows.shape[1], window), H, scale, Hg)
 
 
+def cache_quant(x, Hg: int):
+    """The fp8 cache format, literally: ``x`` (..., 2*Hg*D) 16-bit rows ``[q | v]`` -> (bytes (..., 2*Hg*D)
+    ``float8_e4m3fn``, scales (..., 2*Hg) fp32), one scale per chunk of ``D`` features (one head of ``q`` or
+    ``v``): ``s = amax * (1 / 448)`` in fp32 (1 for an all-zero chunk), ``bytes = rne(x / s)``.  ``|x / s|``
+    stays within ``448 (1 + 2^-23)``, which rounds to 448: nothing saturates."""
+    ch = x.float().reshape(*x.shape[:-1], 2 * Hg, -1)
+    amax = ch.abs().amax(-1)
+    s = torch.where(amax == 0, torch.ones_like(amax), amax * (torch.ones((), dtype=torch.float32, device=x.device) / 448))
+    return (ch / s.unsqueeze(-1)).to(torch.float8_e4m3fn).reshape(x.shape), s
+
+
+def cache_dequant(b8, scales, Hg: int, dtype):
+    """``scale * e4m3`` of :func:`cache_quant`'s pair -> (..., 2*Hg*D) in ``dtype`` (the product in fp64 for an
+    fp64 ``dtype``, else fp32, rounded once)."""
+    cdt = torch.float64 if dtype == torch.float64 else torch.float32
+    ch = b8.to(cdt).reshape(*b8.shape[:-1], 2 * Hg, -1) * scales.to(cdt).unsqueeze(-1)
+    return ch.reshape(b8.shape).to(dtype)
+
+
 def combine(parts, dtype):
     """Merge segment partials [(o, lse)] -> (o in ``dtype``, lse); NaN for fully masked rows.  One
     part comes back bit for bit on its live rows (its weight is exactly 1)."""

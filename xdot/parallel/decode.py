@@ -7,8 +7,13 @@ fp32 ``(o, lse)`` cross the wire -- ``H*D + H`` floats per row -- to be merged l
 a forward.  Softmax does not care about column order, so which rank holds which position, and in which
 slot, is free: contiguous or zigzag prefill shards, generated tokens appended round-robin.
 
+The cache holds the compute dtype, or fp8 (``cache_dtype="fp8"``): OCP e4m3fn bytes with one fp32 scale per
+(slot, gathered head) for each of ``q`` and ``v``, quantised once when a row is appended
+(``csrc/flash_decode8.hip``): ``2*Hg*D + 8*Hg + 4`` bytes per slot instead of ``4*Hg*D + 4``.
+
 Forward only, no autograd.  Not covered: document masks at decode time, a device-side ``pos0`` (a
-captured generation loop), cache eviction."""
+captured generation loop), cache eviction, per-channel scales, fp8 rows, and an fp8 kernel for the
+shapes the decode kernel does not take (they dequantise the whole cache per call)."""
 from __future__ import annotations
 
 from typing import Optional, Tuple, Union
@@ -27,14 +32,26 @@ __all__ = ["AttnCache", "decode_attention"]
 class AttnCache:
     """One rank's shard of the gathered side: ``qv`` (B, capacity, 2*Hg*D), each slot ``[q | v]`` as the
     module's packed projection lays it out (``q`` after norm and rope), ``pos`` (B, capacity) int32 the
-    global position of each slot (-1 = empty), and ``fill``, the slots taken, kept on the host."""
+    global position of each slot (-1 = empty), and ``fill``, the slots taken, kept on the host.
 
-    def __init__(self, batch: int, capacity: int, Hg: int, D: int, dtype: torch.dtype, device=None):
+    ``cache_dtype`` ``"fp8"`` / ``torch.float8_e4m3fn``: ``qv`` holds e4m3fn bytes and ``scales`` (B, 2*Hg,
+    capacity) fp32 one factor per slot and chunk (rows ``0..Hg-1`` the ``q`` heads, ``Hg..2*Hg-1`` the ``v``
+    heads): value = scale * byte.  A chunk (the D features of one head of ``q`` or ``v`` of one slot) is
+    quantised when it is appended: ``s = max|x| / 448``, bytes = ``x / s`` rounded to nearest even; a
+    non-finite input makes its chunk non-finite.  ``dtype`` stays the compute dtype: of the rows appended,
+    of :meth:`dequant` and of the decode output."""
+
+    def __init__(self, batch: int, capacity: int, Hg: int, D: int, dtype: torch.dtype, device=None, cache_dtype=None):
         if min(int(batch), int(capacity), int(Hg), int(D)) < 1:
             raise ValueError(f"AttnCache: batch, capacity, Hg and D must be positive, got {(batch, capacity, Hg, D)}")
-        self.Hg, self.D, self.capacity, self.fill = int(Hg), int(D), int(capacity), 0
-        # zeros: the kernels multiply empty slots' v by a probability of 0
-        self.qv = torch.zeros(int(batch), self.capacity, 2 * self.Hg * self.D, dtype=dtype, device=device)
+        if cache_dtype not in (None, "fp8", torch.float8_e4m3fn):
+            raise ValueError(f"AttnCache: cache_dtype must be None, 'fp8' or torch.float8_e4m3fn, got {cache_dtype!r}")
+        self.Hg, self.D, self.capacity, self.fill, self.dtype = int(Hg), int(D), int(capacity), 0, dtype
+        self.fp8 = cache_dtype is not None
+        # zeros (and scales of 1): the kernels multiply empty slots' v by a probability of 0 and a finite scale
+        self.qv = torch.zeros(int(batch), self.capacity, 2 * self.Hg * self.D, device=device,
+                              dtype=torch.float8_e4m3fn if self.fp8 else dtype)
+        self.scales = torch.ones(int(batch), 2 * self.Hg, self.capacity, dtype=torch.float32, device=device) if self.fp8 else None
         self.pos = torch.full((int(batch), self.capacity), -1, dtype=torch.int32, device=device)
 
     @property
@@ -44,6 +61,22 @@ class AttnCache:
     @property
     def v(self) -> Tensor:
         return self.qv[..., self.Hg * self.D:]
+
+    @property
+    def qscale(self) -> Optional[Tensor]:
+        """(B, Hg, capacity): the scales of :attr:`q` (None for a cache in the compute dtype)."""
+        return self.scales[:, :self.Hg] if self.fp8 else None
+
+    @property
+    def vscale(self) -> Optional[Tensor]:
+        return self.scales[:, self.Hg:] if self.fp8 else None
+
+    def dequant(self) -> Tuple[Tensor, Tensor]:
+        """``(q, v)`` (B, capacity, Hg*D) in the compute dtype: the stored halves, times their scales."""
+        if not self.fp8:
+            return self.q, self.v
+        qv = _ref.cache_dequant(self.qv, self.scales.transpose(1, 2), self.Hg, self.dtype)
+        return qv[..., :self.Hg * self.D], qv[..., self.Hg * self.D:]
 
     @torch.no_grad()
     def append(self, qv: Tensor, positions: Union[int, Tensor]) -> None:
@@ -61,7 +94,14 @@ class AttnCache:
             p = positions.reshape(1, n).to(device=self.pos.device, dtype=torch.int32)
         else:
             p = torch.arange(int(positions), int(positions) + n, dtype=torch.int32, device=self.pos.device).view(1, n)
-        self.qv[:, at:at + n].copy_(qv)
+        if not self.fp8:
+            self.qv[:, at:at + n].copy_(qv)
+        elif n and _ext.use_hip(qv) and qv.dtype in (torch.bfloat16, torch.float16) and self.D in (32, 64, 96, 128):
+            _ext.ops().cache_quant(qv, self.qv, self.scales, at, self.Hg)  # straight into the slots
+        elif n:
+            b8, s = _ref.cache_quant(qv, self.Hg)
+            self.qv[:, at:at + n].copy_(b8)
+            self.scales[:, :, at:at + n].copy_(s.transpose(1, 2))
         self.pos[:, at:at + n] = p
         self.fill = at + n
 
@@ -80,7 +120,7 @@ def decode_attention(rows: Tensor, cache: AttnCache, pos0: int, *, num_heads: in
     comm = comm if comm is not None else _comm.get_comm()
     H, n = int(num_heads), comm.world_size
     o, lse = flash.decode(rows, cache.q, cache.v, cache.pos, int(pos0), H, scale, int(window or 0), Hg=cache.Hg,
-                          out_fp32=n > 1)
+                          out_fp32=n > 1, qscale=cache.qscale, vscale=cache.vscale)
     hip = _ext.use_hip(rows)
     if n > 1:
         no = o.numel()
