@@ -461,7 +461,7 @@ at::Tensor flash_bwd_rows(const at::Tensor& dout, const at::Tensor& rows, const 
 std::tuple<at::Tensor, at::Tensor> decode_call(const char* op, const at::Tensor& rows, const at::Tensor& qc, const at::Tensor& vc,
                                                const at::Tensor* qscale, const at::Tensor* vscale, const at::Tensor& col_pos,
                                                int64_t pos0, int64_t window, int64_t H, double scale, int64_t Hg,
-                                               int64_t nsplit, bool out_fp32) {
+                                               int64_t nsplit, bool out_fp32, bool extend = false) {
   const bool fp8 = qscale != nullptr;
   TORCH_CHECK(rows.is_cuda() && qc.is_cuda() && vc.is_cuda() && col_pos.is_cuda() && qc.device() == rows.device() &&
                   vc.device() == rows.device() && col_pos.device() == rows.device(),
@@ -481,8 +481,13 @@ std::tuple<at::Tensor, at::Tensor> decode_call(const char* op, const at::Tensor&
               " and be a multiple of Hg = ", hg);
   const int64_t D = C / H, G = H / hg;
   TORCH_CHECK(D == 32 || D == 64 || D == 96 || D == 128, op, "head dim must be 32 / 64 / 96 / 128, got ", D);
-  TORCH_CHECK(B > 0 && Rn > 0 && decode_row_tiles(G, Rn) > 0, op, "G * Rn = ", G * Rn, " rows per gathered head, the kernel takes 1..",
-              DEC_MAX_ROWS);
+  if (extend) {
+    TORCH_CHECK(B > 0 && Rn > 0 && G * Rn > DEC_MAX_ROWS && G <= EXT_MAX_GROUP, op, "G * Rn = ", G * Rn,
+                " rows per gathered head with G = ", G, ", the kernel takes more than ", DEC_MAX_ROWS, " with G <= ", EXT_MAX_GROUP);
+  } else {
+    TORCH_CHECK(B > 0 && Rn > 0 && decode_row_tiles(G, Rn) > 0, op, "G * Rn = ", G * Rn, " rows per gathered head, the kernel takes 1..",
+                DEC_MAX_ROWS);
+  }
   TORCH_CHECK(qc.dim() == 3 && qc.size(0) == B && qc.size(2) == hg * D && vc.sizes() == qc.sizes() && qc.size(1) > 0,
               op, "qc and vc must be (B, Tcap, Hg*D) = (", B, ", Tcap, ", hg * D, ")");
   const int64_t Tcap = qc.size(1), ld = qc.stride(1), ldq = fp8 ? 16 : 8;  // rows on the 16-byte grid
@@ -514,19 +519,29 @@ std::tuple<at::Tensor, at::Tensor> decode_call(const char* op, const at::Tensor&
   const int64_t ntiles = (Tcap + DEC_TILE - 1) / DEC_TILE;
   TORCH_CHECK(nsplit >= 0, op, "nsplit must be >= 0");
   const int nrt = decode_row_tiles(G, Rn), cus = xdot_num_cus();
+  const int rb = extend ? extend_block_rows(G, (int)D) : 0;
+  const int64_t nblk = extend ? (Rn + rb - 1) / rb : 1;
   const int ns = nsplit > 0 ? (int)std::min(nsplit, ntiles)
-                            : fp8 ? plan_decode_fp8(B, hg, nrt, (int)D, Tcap, cus) : plan_decode(B, hg, nrt, Tcap, cus);
-  TORCH_CHECK((int64_t)ns * B * hg < (1LL << 31), op, "too many workgroups");
+                 : extend   ? plan_extend(B, hg, G, Rn, (int)D, Tcap, cus)
+                 : fp8      ? plan_decode_fp8(B, hg, nrt, (int)D, Tcap, cus)
+                            : plan_decode(B, hg, nrt, Tcap, cus);
+  TORCH_CHECK((int64_t)ns * nblk * B * hg < (1LL << 31), op, "too many workgroups");
   const auto f32 = rows.options().dtype(at::kFloat);
-  auto opart = at::empty({ns, B, Rn, C}, f32), lpart = at::empty({ns, B, H, Rn}, f32);
+  const bool parts = !extend || ns > 1;  // one span of the row-blocked sweep writes out / lse itself
+  at::Tensor opart, lpart;
+  if (parts) opart = at::empty({ns, B, Rn, C}, f32), lpart = at::empty({ns, B, H, Rn}, f32);
   auto out = at::empty({B, Rn, C}, out_fp32 ? f32 : rows.options()), lse = at::empty({B, H, Rn}, f32);
   DecodeArgs a{};
   a.rows = rows.data_ptr(); a.qc = qc.data_ptr(); a.vc = vc.data_ptr(); a.col_pos = col_pos.data_ptr<int32_t>();
-  a.opart = opart.data_ptr<float>(); a.lpart = lpart.data_ptr<float>(); a.out = out.data_ptr(); a.lse = lse.data_ptr<float>();
+  a.opart = parts ? opart.data_ptr<float>() : nullptr; a.lpart = parts ? lpart.data_ptr<float>() : nullptr;
+  a.out = out.data_ptr(); a.lse = lse.data_ptr<float>();
   a.B = (int)B; a.H = (int)H; a.Hg = (int)hg; a.Rn = (int)Rn; a.Tcap = (int)Tcap; a.ldkv = ld;
   a.pos0 = (int)pos0; a.window = (int)window; a.scale = (float)scale;
   a.nspan = ns; a.span_tiles = decode_span_tiles(Tcap, ns); a.out32 = out_fp32 ? 1 : 0;
-  if (fp8) {
+  if (extend) {
+    ExtendArgs ea{a, rb, (int)nblk};
+    launched(xdot_flash_extend_launch(&ea, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "flash_extend");
+  } else if (fp8) {
     a.qscale = qscale->data_ptr<float>(); a.vscale = vscale->data_ptr<float>();
     a.sc_head = hg > 1 ? qscale->stride(1) : 0; a.sc_batch = B > 1 ? qscale->stride(0) : 0;
     launched(xdot_flash_decode8_launch(&a, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "flash_decode_fp8");
@@ -549,6 +564,16 @@ std::tuple<at::Tensor, at::Tensor> flash_decode_fp8(const at::Tensor& rows, cons
                                                     int64_t nsplit, bool out_fp32) {
   Range rr_("xdot.flash_decode_fp8");
   return decode_call("xdot.flash_decode_fp8: ", rows, qc, vc, &qscale, &vscale, col_pos, pos0, window, H, scale, Hg, nsplit, out_fp32);
+}
+
+// the same call with G * Rn > 64 rows per gathered head: the row-blocked sweep (csrc/flash_extend.hip), a
+// 16-bit cache only; nsplit 0: plan_extend
+std::tuple<at::Tensor, at::Tensor> flash_extend(const at::Tensor& rows, const at::Tensor& qc, const at::Tensor& vc,
+                                                const at::Tensor& col_pos, int64_t pos0, int64_t window, int64_t H,
+                                                double scale, int64_t Hg, int64_t nsplit, bool out_fp32) {
+  Range rr_("xdot.flash_extend");
+  return decode_call("xdot.flash_extend: ", rows, qc, vc, nullptr, nullptr, col_pos, pos0, window, H, scale, Hg, nsplit, out_fp32,
+                     true);
 }
 
 // rows (B, n, 2*Hg*D) 16-bit, a row view of row_view.h -> e4m3 bytes and per-chunk scales in slots
@@ -592,6 +617,11 @@ int64_t flash_decode_fp8_plan(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int6
   const int nt = decode_row_tiles(G, Rn);
   TORCH_CHECK(nt > 0 && B > 0 && Hg > 0 && Tcap > 0 && D > 0, "xdot.flash_decode_fp8_plan: shape");
   return plan_decode_fp8(B, Hg, nt, (int)D, Tcap, xdot_num_cus());
+}
+// spans plan_extend gives this shape (head dim D) on the current device
+int64_t flash_extend_plan(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int64_t D, int64_t Tcap) {
+  TORCH_CHECK(B > 0 && Hg > 0 && Rn > 0 && Tcap > 0 && D > 0 && extend_block_rows(G, (int)D) > 0, "xdot.flash_extend_plan: shape");
+  return plan_extend(B, Hg, G, Rn, (int)D, Tcap, xdot_num_cus());
 }
 
 // ---- chunked launches (gather / reduce-scatter pipelining) ----------------------------
@@ -704,12 +734,14 @@ TORCH_LIBRARY_IMPL(xdot, CompositeExplicitAutograd, m) {
   m.impl("flash_rows_plan", &flash_rows_plan);
   m.impl("flash_decode_plan", &flash_decode_plan);
   m.impl("flash_decode_fp8_plan", &flash_decode_fp8_plan);
+  m.impl("flash_extend_plan", &flash_extend_plan);
 }
 
 TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("flash_fwd", &flash_fwd);
   m.impl("flash_decode", &flash_decode);
   m.impl("flash_decode_fp8", &flash_decode_fp8);
+  m.impl("flash_extend", &flash_extend);
   m.impl("cache_quant", &cache_quant);
   m.impl("flash_bwd_cols", &flash_bwd_cols);
   m.impl("flash_bwd_rows", &flash_bwd_rows);

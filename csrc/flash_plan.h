@@ -189,5 +189,36 @@ inline int plan_decode_fp8(int64_t B, int64_t Hg, int row_tiles, int D, int64_t 
   return (int)std::max<int64_t>(1, (nt + len - 1) / len);
 }
 
+// ---- chunked prefill (csrc/flash_extend.hip) -------------------------------------------------------
+// More than DEC_MAX_ROWS rows per gathered head: one workgroup per (column span, row block, batch, gathered
+// head), a row block being rb consecutive new rows x the G row heads of the group packed into the 4 waves'
+// NT 16-row tiles each.  NT and the resident workgroups per CU are the compiler's figures for the
+// instantiation (profiles/extend.md; D = 32 / 64 / 96 / 128): NT = 2 wherever that puts more workgroups on
+// a CU than NT = 4 (4 / 2 / 2 against 2 / 1 / 1: one runs MFMAs while another is in its softmax or at its
+// barrier; measured at D = 96, 1.46x), NT = 4 at D = 128, where either gives one workgroup.
+constexpr int extend_row_tiles(int D) { return D <= 96 ? 2 : 4; }
+constexpr int EXT_MAX_GROUP = 128;  // row heads per gathered head: one new row of a group fits every block
+inline int extend_wgs_per_cu(int D) {
+  static constexpr int occ[4] = {4, 2, 2, 1};
+  return occ[std::max(0, std::min(3, D / 32 - 1))];
+}
+// new rows per row block; 0: the group is wider than a block
+inline int extend_block_rows(int64_t G, int D) {
+  return G >= 1 && G <= 64 * extend_row_tiles(D) ? (int)(64 * extend_row_tiles(D) / G) : 0;
+}
+// Column spans of a launch.  The kernel is bound by the MFMAs and every workgroup reads its whole span, so
+// a span is worth its partial slots only where the row blocks alone leave resident slots empty: one span
+// (no partials, no merge) when row blocks x B * Hg fill them, else spans under plan_decode's rules (at
+// least 8 tiles each, none empty).
+inline int plan_extend(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int D, int64_t Tcap, int cus) {
+  const int64_t rb = std::max(1, extend_block_rows(G, D));
+  const int64_t nt = (Tcap + DEC_TILE - 1) / DEC_TILE, wgs = std::max<int64_t>(1, B * Hg * ((Rn + rb - 1) / rb));
+  const int64_t slots = (int64_t)extend_wgs_per_cu(D) * std::max(1, cus);
+  if (wgs >= slots) return 1;
+  const int64_t s = std::max<int64_t>(1, std::min((slots + wgs - 1) / wgs, nt / 8));
+  const int64_t len = (nt + s - 1) / s;
+  return (int)std::max<int64_t>(1, (nt + len - 1) / len);
+}
+
 }  // namespace fa
 }  // namespace xdot

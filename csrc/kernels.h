@@ -146,6 +146,14 @@ struct DecodeArgs {
   int64_t sc_head, sc_batch;  // strides of both scale views between gathered heads / batches (floats)
 };
 
+// chunked prefill (csrc/flash_extend.hip): the decode call with G * Rn > 64 rows per gathered head, cut into
+// nblk blocks of rb consecutive new rows (x the G row heads of a group); d.opart / d.lpart are used with
+// d.nspan > 1 only
+struct ExtendArgs {
+  DecodeArgs d;
+  int rb, nblk;
+};
+
 // cache_quant (csrc/flash_decode8.hip): n rows of a 16-bit (B, n, 2*Hg*D) view -> e4m3 bytes and one
 // fp32 scale per chunk (the D features of one head of q or v) in slots [at, at + n) of an fp8 cache
 struct QuantArgs {
@@ -362,6 +370,9 @@ int xdot_flash_decode_launch(const xdot::fa::DecodeArgs* a, int dt, int D, hipSt
 // the spans' merge alone
 int xdot_flash_decode8_launch(const xdot::fa::DecodeArgs* a, int dt, int D, hipStream_t st);
 int xdot_flash_decode_combine_launch(const xdot::fa::DecodeArgs* a, int dt, int D, hipStream_t st);
+// chunked prefill: the row-blocked sweep of the same call for G * Rn > 64 (16-bit, D <= 128; -1 otherwise,
+// or where a->rb rows x G heads exceed the kernel's row block); merges the spans itself when a->d.nspan > 1
+int xdot_flash_extend_launch(const xdot::fa::ExtendArgs* a, int dt, int D, hipStream_t st);
 int xdot_cache_quant_launch(const xdot::fa::QuantArgs* a, int dt, int D, hipStream_t st);
 // δ = rowsum(dO ⊙ O) (reads a->dout, a->B/R/H)
 int xdot_flash_bwd_delta_launch(const xdot::fa::BwdArgs* a, const void* out, float* delta, int dt, int D, hipStream_t st);

@@ -385,8 +385,8 @@ _FWD_HEAD_DIMS = (32, 64, 96, 128, 160, 192, 256, 384)
 
 def decode_eligible(dtype: torch.dtype, D: int, Dv: int, G: int, Rn: int, cache_dtype=None) -> bool:
     """The decode kernel takes this call: 16-bit, one head dim of 32 / 64 / 96 / 128 for q and v, and at
-    most 64 rows (``G`` row heads x ``Rn`` new rows) per gathered head.  Everything else runs the
-    forward kernels over a dense mask (:func:`decode`).  Every eligible shape that was measured is
+    most 64 rows (``G`` row heads x ``Rn`` new rows) per gathered head.  More rows go to the row-blocked
+    kernel (:func:`extend_eligible`), everything else to the forward kernels over a dense mask (:func:`decode`).  Every eligible shape that was measured is
     faster than that route (profiles/decode.md), so none is routed away.  ``dtype`` is the rows';
     ``cache_dtype`` ``torch.float8_e4m3fn`` asks for the fp8-cache kernel (csrc/flash_decode8.hip), which
     takes the same shapes and is the only kernel that reads such a cache."""
@@ -424,7 +424,9 @@ def decode(rows: torch.Tensor, qc: torch.Tensor, vc: torch.Tensor, col_pos: torc
     ``nsplit``: column spans (0: ``plan_decode`` of ``csrc/flash_plan.h``).  ``out_fp32``: ``out`` in
     fp32, rounded once less (the wire format of :func:`xdot.decode_attention`'s cross-rank merge).
 
-    Calls the kernel does not take (:func:`decode_eligible`: fp32, D > 128, Dv != D, G * Rn > 64)
+    16-bit calls with more than 64 rows per gathered head (chunked prefill, a long user turn, a long
+    draft: :func:`extend_eligible`) run the row-blocked sweep of :func:`extend` under the same contract.
+    Calls neither kernel takes (fp32, D > 128, Dv != D, more than 128 row heads per gathered head)
     run :func:`fwd` over the dense mask of the same rule, packed per call, with grouped heads
     repeated where :func:`fwd` has no grouped kernel and heads zero-padded to a common kernel width;
     CPU tensors and ``backend='torch'`` run ``xdot.parallel._ref.decode``.
@@ -462,6 +464,8 @@ def decode(rows: torch.Tensor, qc: torch.Tensor, vc: torch.Tensor, col_pos: torc
     if decode_eligible(rows.dtype, D, Dv, H // hg, Rn):
         return _ext.ops().flash_decode(rows.contiguous(), _kv(qc), _kv(vc), col_pos, int(pos0), window, int(H),
                                        float(scale), hg, int(nsplit), bool(out_fp32))
+    if extend_eligible(rows.dtype, D, Dv, H // hg, Rn, qc.dtype):
+        return extend(rows, qc, vc, col_pos, pos0, H, scale, window, Hg, nsplit, out_fp32)
     from ..parallel._ref import decode_mask
 
     Dp = next((d for d in _FWD_HEAD_DIMS if d >= max(D, Dv)), None)
@@ -484,6 +488,48 @@ def decode_plan(B: int, Hg: int, G: int, Rn: int, Tcap: int, fp8_head_dim: int =
     if fp8_head_dim:
         return int(_ext.ops().flash_decode_fp8_plan(int(B), int(Hg), int(G), int(Rn), int(fp8_head_dim), int(Tcap)))
     return int(_ext.ops().flash_decode_plan(int(B), int(Hg), int(G), int(Rn), int(Tcap)))
+
+
+# ---- chunked prefill: many new rows against one rank's cache (csrc/flash_extend.hip) ---------------
+EXTEND_MAX_GROUP = 128   # row heads per gathered head: one new row of a group fits the smallest row block
+_EXTEND_MAX_NEW_ROWS = {96: 128}   # head dim -> the most new rows the kernel won the A/B at (profiles/extend.md)
+
+
+def extend_eligible(dtype: torch.dtype, D: int, Dv: int, G: int, Rn: int, cache_dtype=None) -> bool:
+    """The row-blocked kernel takes this call: 16-bit, one head dim of 32 / 64 / 96 / 128 for q and v, more
+    than 64 rows (``G`` row heads x ``Rn`` new rows) per gathered head, where :func:`decode_eligible` ends,
+    at most 128 row heads per gathered head, and a cache in the rows' dtype (``cache_dtype`` ``None``: the
+    same).  An fp8 cache with that many rows stays on :func:`decode`'s slow path.  Routed away: D = 96 with
+    more than 128 new rows, where the forward kernels over an already packed mask were measured faster
+    (profiles/extend.md; the other head dims were not measured and keep the kernel)."""
+    if cache_dtype not in (None, dtype):
+        return False
+    return (dtype in (torch.bfloat16, torch.float16) and D == Dv and D in (32, 64, 96, 128)
+            and G * Rn > DECODE_MAX_ROWS and 1 <= G <= EXTEND_MAX_GROUP and Rn <= _EXTEND_MAX_NEW_ROWS.get(D, Rn))
+
+
+def extend(rows: torch.Tensor, qc: torch.Tensor, vc: torch.Tensor, col_pos: torch.Tensor, pos0: int, H: int,
+           scale: float, window: int = 0, Hg: Optional[int] = None, nsplit: int = 0,
+           out_fp32: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`decode` for more than 64 rows per gathered head, on the kernel alone: same arguments, same
+    visibility rule from ``col_pos``, same outputs (a row that sees nothing: NaN, lse -inf), no mask and no
+    ``Rn x Tcap`` tensor.  Workgroups take blocks of consecutive new rows (x the ``G`` row heads of a group)
+    and sweep the cache through LDS, skipping tiles no row of the block can see.  ``nsplit``: column spans
+    (0: ``plan_extend`` of ``csrc/flash_plan.h``; one span writes ``out`` directly).  Raises on a call
+    that is not :func:`extend_eligible` or not on the GPU."""
+    B, Rn, C = rows.shape
+    hg = int(Hg) if Hg else int(H)
+    D, Dv = C // H, vc.shape[-1] // hg
+    if not (_ext.use_hip(rows, qc, vc) and extend_eligible(rows.dtype, D, Dv, H // hg, Rn, qc.dtype)):
+        raise ValueError(f"flash.extend: not a call of the kernel (dtype {rows.dtype}, cache {qc.dtype}, head dims "
+                         f"({D}, {Dv}), G = {H // hg}, Rn = {Rn}, device {rows.device}); flash.decode routes it")
+    return _ext.ops().flash_extend(rows.contiguous(), _kv(qc), _kv(vc), col_pos, int(pos0), int(window or 0), int(H),
+                                   float(scale), hg, int(nsplit), bool(out_fp32))
+
+
+def extend_plan(B: int, Hg: int, G: int, Rn: int, D: int, Tcap: int) -> int:
+    """Column spans an automatic :func:`extend` launch of head dim ``D`` takes on the current device."""
+    return int(_ext.ops().flash_extend_plan(int(B), int(Hg), int(G), int(Rn), int(D), int(Tcap)))
 
 
 def bwd_delta(dout: torch.Tensor, out: torch.Tensor, H: int) -> torch.Tensor:

@@ -13,7 +13,13 @@ The cache holds the compute dtype, or fp8 (``cache_dtype="fp8"``): OCP e4m3fn by
 
 Forward only, no autograd.  Not covered: document masks at decode time, a device-side ``pos0`` (a
 captured generation loop), cache eviction, per-channel scales, fp8 rows, and an fp8 kernel for the
-shapes the decode kernel does not take (they dequantise the whole cache per call)."""
+shapes the decode kernel does not take, more than 64 rows per gathered head among them (they dequantise
+the whole cache per call).
+
+More than 64 rows per gathered head over a 16-bit cache (chunked prefill, a long user turn or draft) run
+the row-blocked kernel of ``csrc/flash_extend.hip`` under the same contract, through the same calls;
+D = 96 calls with more than 128 new rows still take the forward kernels over a dense mask
+(:func:`xdot.ops.flash.extend_eligible`, ``profiles/extend.md``)."""
 from __future__ import annotations
 
 from typing import Optional, Tuple, Union
