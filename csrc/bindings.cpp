@@ -436,6 +436,9 @@ TORCH_LIBRARY(xdot, m) {
   m.def("flash_extend(Tensor rows, Tensor qc, Tensor vc, Tensor col_pos, int pos0, int window, int H, float scale, "
         "int Hg=0, int nsplit=0, bool out_fp32=False) -> (Tensor, Tensor)");
   m.def("flash_extend_plan(int B, int Hg, int G, int Rn, int D, int Tcap) -> int");
+  m.def("flash_extend_fp8(Tensor rows, Tensor qc, Tensor vc, Tensor qscale, Tensor vscale, Tensor col_pos, int pos0, "
+        "int window, int H, float scale, int Hg=0, int nsplit=0, bool out_fp32=False) -> (Tensor, Tensor)");
+  m.def("flash_extend_fp8_plan(int B, int Hg, int G, int Rn, int D, int Tcap) -> int");
   m.def("cache_quant(Tensor rows, Tensor(a!) qv8, Tensor(b!) scales, int at, int Hg) -> ()");
   m.def("flash_splits(int B, int R, int T, int H, bool rows_kernel) -> int");
   m.def("flash_fwd_plan(int B, int R, int T, int H, int D, ScalarType dtype, int fp32_mode, bool sbuf, int nsplit) -> int[]");

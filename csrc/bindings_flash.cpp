@@ -457,7 +457,7 @@ at::Tensor flash_bwd_rows(const at::Tensor& dout, const at::Tensor& rows, const 
 // positions are col_pos (B, Tcap) int32, -1 = empty: -> (out (B, Rn, H*D) in the rows' dtype, or fp32 with
 // out_fp32: the wire format of the cross-rank merge; lse (B, H, Rn)).  nsplit 0: plan_decode
 // qscale / vscale set: the cache is fp8 (e4m3fn bytes, row stride in bytes) with fp32 (B, Hg, Tcap) scale
-// views (csrc/flash_decode8.hip); every other check is the 16-bit call's.
+// views (csrc/flash_decode8.hip; with `extend`, csrc/flash_extend8.hip); every other check is the 16-bit call's.
 std::tuple<at::Tensor, at::Tensor> decode_call(const char* op, const at::Tensor& rows, const at::Tensor& qc, const at::Tensor& vc,
                                                const at::Tensor* qscale, const at::Tensor* vscale, const at::Tensor& col_pos,
                                                int64_t pos0, int64_t window, int64_t H, double scale, int64_t Hg,
@@ -522,7 +522,7 @@ std::tuple<at::Tensor, at::Tensor> decode_call(const char* op, const at::Tensor&
   const int rb = extend ? extend_block_rows(G, (int)D) : 0;
   const int64_t nblk = extend ? (Rn + rb - 1) / rb : 1;
   const int ns = nsplit > 0 ? (int)std::min(nsplit, ntiles)
-                 : extend   ? plan_extend(B, hg, G, Rn, (int)D, Tcap, cus)
+                 : extend   ? (fp8 ? plan_extend_fp8(B, hg, G, Rn, (int)D, Tcap, cus) : plan_extend(B, hg, G, Rn, (int)D, Tcap, cus))
                  : fp8      ? plan_decode_fp8(B, hg, nrt, (int)D, Tcap, cus)
                             : plan_decode(B, hg, nrt, Tcap, cus);
   TORCH_CHECK((int64_t)ns * nblk * B * hg < (1LL << 31), op, "too many workgroups");
@@ -538,12 +538,15 @@ std::tuple<at::Tensor, at::Tensor> decode_call(const char* op, const at::Tensor&
   a.B = (int)B; a.H = (int)H; a.Hg = (int)hg; a.Rn = (int)Rn; a.Tcap = (int)Tcap; a.ldkv = ld;
   a.pos0 = (int)pos0; a.window = (int)window; a.scale = (float)scale;
   a.nspan = ns; a.span_tiles = decode_span_tiles(Tcap, ns); a.out32 = out_fp32 ? 1 : 0;
-  if (extend) {
-    ExtendArgs ea{a, rb, (int)nblk};
-    launched(xdot_flash_extend_launch(&ea, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "flash_extend");
-  } else if (fp8) {
+  if (fp8) {
     a.qscale = qscale->data_ptr<float>(); a.vscale = vscale->data_ptr<float>();
     a.sc_head = hg > 1 ? qscale->stride(1) : 0; a.sc_batch = B > 1 ? qscale->stride(0) : 0;
+  }
+  if (extend) {
+    ExtendArgs ea{a, rb, (int)nblk};
+    if (fp8) launched(xdot_flash_extend8_launch(&ea, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "flash_extend_fp8");
+    else launched(xdot_flash_extend_launch(&ea, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "flash_extend");
+  } else if (fp8) {
     launched(xdot_flash_decode8_launch(&a, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "flash_decode_fp8");
   } else {
     launched(xdot_flash_decode_launch(&a, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "flash_decode");
@@ -567,12 +570,22 @@ std::tuple<at::Tensor, at::Tensor> flash_decode_fp8(const at::Tensor& rows, cons
 }
 
 // the same call with G * Rn > 64 rows per gathered head: the row-blocked sweep (csrc/flash_extend.hip), a
-// 16-bit cache only; nsplit 0: plan_extend
+// 16-bit cache; nsplit 0: plan_extend
 std::tuple<at::Tensor, at::Tensor> flash_extend(const at::Tensor& rows, const at::Tensor& qc, const at::Tensor& vc,
                                                 const at::Tensor& col_pos, int64_t pos0, int64_t window, int64_t H,
                                                 double scale, int64_t Hg, int64_t nsplit, bool out_fp32) {
   Range rr_("xdot.flash_extend");
   return decode_call("xdot.flash_extend: ", rows, qc, vc, nullptr, nullptr, col_pos, pos0, window, H, scale, Hg, nsplit, out_fp32,
+                     true);
+}
+
+// the same over an fp8 cache with (B, Hg, Tcap) scale views (csrc/flash_extend8.hip); nsplit 0: plan_extend_fp8
+std::tuple<at::Tensor, at::Tensor> flash_extend_fp8(const at::Tensor& rows, const at::Tensor& qc, const at::Tensor& vc,
+                                                    const at::Tensor& qscale, const at::Tensor& vscale, const at::Tensor& col_pos,
+                                                    int64_t pos0, int64_t window, int64_t H, double scale, int64_t Hg,
+                                                    int64_t nsplit, bool out_fp32) {
+  Range rr_("xdot.flash_extend_fp8");
+  return decode_call("xdot.flash_extend_fp8: ", rows, qc, vc, &qscale, &vscale, col_pos, pos0, window, H, scale, Hg, nsplit, out_fp32,
                      true);
 }
 
@@ -622,6 +635,11 @@ int64_t flash_decode_fp8_plan(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int6
 int64_t flash_extend_plan(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int64_t D, int64_t Tcap) {
   TORCH_CHECK(B > 0 && Hg > 0 && Rn > 0 && Tcap > 0 && D > 0 && extend_block_rows(G, (int)D) > 0, "xdot.flash_extend_plan: shape");
   return plan_extend(B, Hg, G, Rn, (int)D, Tcap, xdot_num_cus());
+}
+// the same over an fp8 cache (plan_extend_fp8)
+int64_t flash_extend_fp8_plan(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int64_t D, int64_t Tcap) {
+  TORCH_CHECK(B > 0 && Hg > 0 && Rn > 0 && Tcap > 0 && D > 0 && extend_block_rows(G, (int)D) > 0, "xdot.flash_extend_fp8_plan: shape");
+  return plan_extend_fp8(B, Hg, G, Rn, (int)D, Tcap, xdot_num_cus());
 }
 
 // ---- chunked launches (gather / reduce-scatter pipelining) ----------------------------
@@ -735,6 +753,7 @@ TORCH_LIBRARY_IMPL(xdot, CompositeExplicitAutograd, m) {
   m.impl("flash_decode_plan", &flash_decode_plan);
   m.impl("flash_decode_fp8_plan", &flash_decode_fp8_plan);
   m.impl("flash_extend_plan", &flash_extend_plan);
+  m.impl("flash_extend_fp8_plan", &flash_extend_fp8_plan);
 }
 
 TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
@@ -742,6 +761,7 @@ TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("flash_decode", &flash_decode);
   m.impl("flash_decode_fp8", &flash_decode_fp8);
   m.impl("flash_extend", &flash_extend);
+  m.impl("flash_extend_fp8", &flash_extend_fp8);
   m.impl("cache_quant", &cache_quant);
   m.impl("flash_bwd_cols", &flash_bwd_cols);
   m.impl("flash_bwd_rows", &flash_bwd_rows);

@@ -19,6 +19,22 @@ template <> struct mfma16<DT_F16> {
   }
 };
 
+// fp8 caches (csrc/flash_decode8.hip, csrc/flash_extend8.hip): 4 e4m3 bytes -> 4 values of the rows' dtype
+// (exact: v_cvt_scalef32_pk_{bf16,f16}_fp8 at scale 1.0), and 8 bytes -> one 16-byte MFMA operand chunk
+template <int DT> __device__ __forceinline__ u32x2 widen4(uint32_t w);
+template <> __device__ __forceinline__ u32x2 widen4<DT_BF16>(uint32_t w) {
+  return u32x2{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false)),
+               __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))};
+}
+template <> __device__ __forceinline__ u32x2 widen4<DT_F16>(uint32_t w) {
+  return u32x2{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false)),
+               __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true))};
+}
+template <int DT> __device__ __forceinline__ u32x4 widen8(uint32_t lo, uint32_t hi) {
+  const u32x2 a = widen4<DT>(lo), b = widen4<DT>(hi);
+  return u32x4{a[0], a[1], b[0], b[1]};
+}
+
 // LDS of one workgroup: the 4 waves' v tiles (rows of 2 D + 16 bytes), reused after the sweep as the
 // fp32 output image the waves add into ([row][D + 4]), then the per-wave and the merged (m, l)
 template <int D, int NT> struct DecCfg {

@@ -42,21 +42,6 @@
 namespace xdot {
 namespace fa {
 
-// 4 e4m3 bytes -> 4 values of the rows' dtype (exact)
-template <int DT> __device__ __forceinline__ u32x2 widen4(uint32_t w);
-template <> __device__ __forceinline__ u32x2 widen4<DT_BF16>(uint32_t w) {
-  return u32x2{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false)),
-               __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))};
-}
-template <> __device__ __forceinline__ u32x2 widen4<DT_F16>(uint32_t w) {
-  return u32x2{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, false)),
-               __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, true))};
-}
-template <int DT> __device__ __forceinline__ u32x4 widen8(uint32_t lo, uint32_t hi) {
-  const u32x2 a = widen4<DT>(lo), b = widen4<DT>(hi);
-  return u32x4{a[0], a[1], b[0], b[1]};
-}
-
 template <int DT, int D, int NT>
 __global__ __launch_bounds__(256) void flash_decode8_kernel(DecodeArgs a) {
   using Cfg = DecCfg<D, NT>;

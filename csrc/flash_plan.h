@@ -210,14 +210,27 @@ inline int extend_block_rows(int64_t G, int D) {
 // a span is worth its partial slots only where the row blocks alone leave resident slots empty: one span
 // (no partials, no merge) when row blocks x B * Hg fill them, else spans under plan_decode's rules (at
 // least 8 tiles each, none empty).
-inline int plan_extend(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int D, int64_t Tcap, int cus) {
+inline int extend_spans(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int D, int64_t Tcap, int64_t slots) {
   const int64_t rb = std::max(1, extend_block_rows(G, D));
   const int64_t nt = (Tcap + DEC_TILE - 1) / DEC_TILE, wgs = std::max<int64_t>(1, B * Hg * ((Rn + rb - 1) / rb));
-  const int64_t slots = (int64_t)extend_wgs_per_cu(D) * std::max(1, cus);
   if (wgs >= slots) return 1;
   const int64_t s = std::max<int64_t>(1, std::min((slots + wgs - 1) / wgs, nt / 8));
   const int64_t len = (nt + s - 1) / s;
   return (int)std::max<int64_t>(1, (nt + len - 1) / len);
+}
+inline int plan_extend(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int D, int64_t Tcap, int cus) {
+  return extend_spans(B, Hg, G, Rn, D, Tcap, (int64_t)extend_wgs_per_cu(D) * std::max(1, cus));
+}
+
+// The same over an fp8 cache (csrc/flash_extend8.hip): the row blocks and NT of the 16-bit kernel, the
+// resident workgroups per CU the compiler reports for its own instantiations (profiles/extend_fp8.md; D =
+// 32 / 64 / 96 / 128), and plan_extend's span rules over them.
+inline int extend_fp8_wgs_per_cu(int D) {
+  static constexpr int occ[4] = {4, 2, 2, 1};
+  return occ[std::max(0, std::min(3, D / 32 - 1))];
+}
+inline int plan_extend_fp8(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int D, int64_t Tcap, int cus) {
+  return extend_spans(B, Hg, G, Rn, D, Tcap, (int64_t)extend_fp8_wgs_per_cu(D) * std::max(1, cus));
 }
 
 }  // namespace fa

@@ -373,6 +373,9 @@ int xdot_flash_decode_combine_launch(const xdot::fa::DecodeArgs* a, int dt, int 
 // chunked prefill: the row-blocked sweep of the same call for G * Rn > 64 (16-bit, D <= 128; -1 otherwise,
 // or where a->rb rows x G heads exceed the kernel's row block); merges the spans itself when a->d.nspan > 1
 int xdot_flash_extend_launch(const xdot::fa::ExtendArgs* a, int dt, int D, hipStream_t st);
+// the same over an fp8 cache with per-slot scales (csrc/flash_extend8.hip; a->d.qscale / vscale set, a->d.ldkv
+// in bytes; dt: the rows' 16-bit dtype)
+int xdot_flash_extend8_launch(const xdot::fa::ExtendArgs* a, int dt, int D, hipStream_t st);
 int xdot_cache_quant_launch(const xdot::fa::QuantArgs* a, int dt, int D, hipStream_t st);
 // δ = rowsum(dO ⊙ O) (reads a->dout, a->B/R/H)
 int xdot_flash_bwd_delta_launch(const xdot::fa::BwdArgs* a, const void* out, float* delta, int dt, int D, hipStream_t st);

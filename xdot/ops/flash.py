@@ -389,7 +389,7 @@ def decode_eligible(dtype: torch.dtype, D: int, Dv: int, G: int, Rn: int, cache_
     kernel (:func:`extend_eligible`), everything else to the forward kernels over a dense mask (:func:`decode`).  Every eligible shape that was measured is
     faster than that route (profiles/decode.md), so none is routed away.  ``dtype`` is the rows';
     ``cache_dtype`` ``torch.float8_e4m3fn`` asks for the fp8-cache kernel (csrc/flash_decode8.hip), which
-    takes the same shapes and is the only kernel that reads such a cache."""
+    takes the same shapes; more rows over such a cache go to :func:`extend_fp8_eligible`."""
     if cache_dtype not in (None, dtype, torch.float8_e4m3fn):
         return False
     return (dtype in (torch.bfloat16, torch.float16) and D == Dv and D in (32, 64, 96, 128)
@@ -434,9 +434,11 @@ def decode(rows: torch.Tensor, qc: torch.Tensor, vc: torch.Tensor, col_pos: torc
     ``qscale`` / ``vscale`` (B, Hg, Tcap) fp32, unit inner stride: ``qc`` / ``vc`` are ``float8_e4m3fn`` and
     slot ``c`` of gathered head ``h`` stands for ``qscale[b, h, c] * qc[b, c, h*D:(h+1)*D]`` (and likewise
     ``v``): the format of :class:`xdot.AttnCache` with ``cache_dtype="fp8"``.  Eligible calls run the fp8
-    sweep (csrc/flash_decode8.hip), which applies the scales per column and reads the bytes as they are.
-    Every other call is the slow path: it first dequantises the whole cache into fp32 and runs the fp32
-    route of the call (the forward kernels over a dense mask on the GPU)."""
+    sweep (csrc/flash_decode8.hip), which applies the scales per column and reads the bytes as they are, and
+    with more than 64 rows per gathered head (:func:`extend_fp8_eligible`) its row-blocked form
+    (csrc/flash_extend8.hip, :func:`extend`).  Only calls neither kernel takes (fp32 rows, D > 128, Dv != D,
+    more than 128 row heads per gathered head) are the slow path: it first dequantises the whole cache into
+    fp32 and runs the fp32 route of the call (the forward kernels over a dense mask on the GPU)."""
     B, Rn, C = rows.shape
     hg = int(Hg) if Hg else int(H)
     D, Dv, window = C // H, vc.shape[-1] // hg, int(window or 0)
@@ -446,6 +448,8 @@ def decode(rows: torch.Tensor, qc: torch.Tensor, vc: torch.Tensor, col_pos: torc
         if _ext.use_hip(rows, qc, vc) and decode_eligible(rows.dtype, D, Dv, H // hg, Rn, torch.float8_e4m3fn):
             return _ext.ops().flash_decode_fp8(rows.contiguous(), _kv(qc), _kv(vc), qscale, vscale, col_pos, int(pos0),
                                                window, int(H), float(scale), hg, int(nsplit), bool(out_fp32))
+        if _ext.use_hip(rows, qc, vc) and extend_fp8_eligible(rows.dtype, D, Dv, H // hg, Rn):
+            return extend(rows, qc, vc, col_pos, pos0, H, scale, window, Hg, nsplit, out_fp32, qscale, vscale)
         from ..parallel import _ref
 
         # scale * byte does not fit a 16-bit value: a cache dequantised into rows.dtype would be rounded a
@@ -499,27 +503,50 @@ def extend_eligible(dtype: torch.dtype, D: int, Dv: int, G: int, Rn: int, cache_
     """The row-blocked kernel takes this call: 16-bit, one head dim of 32 / 64 / 96 / 128 for q and v, more
     than 64 rows (``G`` row heads x ``Rn`` new rows) per gathered head, where :func:`decode_eligible` ends,
     at most 128 row heads per gathered head, and a cache in the rows' dtype (``cache_dtype`` ``None``: the
-    same).  An fp8 cache with that many rows stays on :func:`decode`'s slow path.  Routed away: D = 96 with
-    more than 128 new rows, where the forward kernels over an already packed mask were measured faster
-    (profiles/extend.md; the other head dims were not measured and keep the kernel)."""
+    same).  An fp8 cache with that many rows has a kernel of its own (:func:`extend_fp8_eligible`).  Routed
+    away: D = 96 with more than 128 new rows, where the forward kernels over an already packed mask were
+    measured faster (profiles/extend.md; the other head dims were not measured and keep the kernel)."""
     if cache_dtype not in (None, dtype):
         return False
     return (dtype in (torch.bfloat16, torch.float16) and D == Dv and D in (32, 64, 96, 128)
             and G * Rn > DECODE_MAX_ROWS and 1 <= G <= EXTEND_MAX_GROUP and Rn <= _EXTEND_MAX_NEW_ROWS.get(D, Rn))
 
 
+def extend_fp8_eligible(dtype: torch.dtype, D: int, Dv: int, G: int, Rn: int) -> bool:
+    """The row-blocked fp8-cache kernel (csrc/flash_extend8.hip) takes this call: 16-bit rows over a
+    ``float8_e4m3fn`` cache with per-slot scales, one head dim of 32 / 64 / 96 / 128 for q and v, more than 64
+    rows (``G`` row heads x ``Rn`` new rows) per gathered head, where :func:`decode_eligible` ends, and at most
+    128 row heads per gathered head.  The route it replaces dequantises the whole cache into fp32 per call;
+    the kernel was 3.6x-12x faster than it at every measured shape (D = 96, 72 to 1024 new rows,
+    profiles/extend_fp8.md), so no row count is routed away: the 16-bit kernel's D = 96 limit was set against
+    the 16-bit forward kernels and does not carry over."""
+    return (dtype in (torch.bfloat16, torch.float16) and D == Dv and D in (32, 64, 96, 128)
+            and G * Rn > DECODE_MAX_ROWS and 1 <= G <= EXTEND_MAX_GROUP)
+
+
 def extend(rows: torch.Tensor, qc: torch.Tensor, vc: torch.Tensor, col_pos: torch.Tensor, pos0: int, H: int,
            scale: float, window: int = 0, Hg: Optional[int] = None, nsplit: int = 0,
-           out_fp32: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+           out_fp32: bool = False, qscale: Optional[torch.Tensor] = None,
+           vscale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """:func:`decode` for more than 64 rows per gathered head, on the kernel alone: same arguments, same
     visibility rule from ``col_pos``, same outputs (a row that sees nothing: NaN, lse -inf), no mask and no
     ``Rn x Tcap`` tensor.  Workgroups take blocks of consecutive new rows (x the ``G`` row heads of a group)
     and sweep the cache through LDS, skipping tiles no row of the block can see.  ``nsplit``: column spans
-    (0: ``plan_extend`` of ``csrc/flash_plan.h``; one span writes ``out`` directly).  Raises on a call
-    that is not :func:`extend_eligible` or not on the GPU."""
+    (0: ``plan_extend`` of ``csrc/flash_plan.h``; one span writes ``out`` directly).  ``qscale`` / ``vscale``
+    (B, Hg, Tcap) fp32: ``qc`` / ``vc`` are ``float8_e4m3fn`` in :func:`decode`'s fp8 format and the call is
+    the fp8 kernel's (csrc/flash_extend8.hip, :func:`extend_fp8_eligible`).  Raises on a call that is not
+    eligible for its kernel or not on the GPU."""
     B, Rn, C = rows.shape
     hg = int(Hg) if Hg else int(H)
     D, Dv = C // H, vc.shape[-1] // hg
+    if qscale is not None or vscale is not None:
+        if not (qscale is not None and vscale is not None and qc.dtype == vc.dtype == torch.float8_e4m3fn
+                and _ext.use_hip(rows, qc, vc) and extend_fp8_eligible(rows.dtype, D, Dv, H // hg, Rn)):
+            raise ValueError(f"flash.extend: not a call of the fp8 kernel (dtype {rows.dtype}, cache {qc.dtype} / {vc.dtype} "
+                             f"with both scales, head dims ({D}, {Dv}), G = {H // hg}, Rn = {Rn}, device {rows.device}); "
+                             "flash.decode routes it")
+        return _ext.ops().flash_extend_fp8(rows.contiguous(), _kv(qc), _kv(vc), qscale, vscale, col_pos, int(pos0),
+                                           int(window or 0), int(H), float(scale), hg, int(nsplit), bool(out_fp32))
     if not (_ext.use_hip(rows, qc, vc) and extend_eligible(rows.dtype, D, Dv, H // hg, Rn, qc.dtype)):
         raise ValueError(f"flash.extend: not a call of the kernel (dtype {rows.dtype}, cache {qc.dtype}, head dims "
                          f"({D}, {Dv}), G = {H // hg}, Rn = {Rn}, device {rows.device}); flash.decode routes it")
@@ -527,8 +554,11 @@ def extend(rows: torch.Tensor, qc: torch.Tensor, vc: torch.Tensor, col_pos: torc
                                    float(scale), hg, int(nsplit), bool(out_fp32))
 
 
-def extend_plan(B: int, Hg: int, G: int, Rn: int, D: int, Tcap: int) -> int:
-    """Column spans an automatic :func:`extend` launch of head dim ``D`` takes on the current device."""
+def extend_plan(B: int, Hg: int, G: int, Rn: int, D: int, Tcap: int, fp8: bool = False) -> int:
+    """Column spans an automatic :func:`extend` launch of head dim ``D`` takes on the current device; ``fp8``:
+    over an fp8 cache (``plan_extend_fp8``)."""
+    if fp8:
+        return int(_ext.ops().flash_extend_fp8_plan(int(B), int(Hg), int(G), int(Rn), int(D), int(Tcap)))
     return int(_ext.ops().flash_extend_plan(int(B), int(Hg), int(G), int(Rn), int(D), int(Tcap)))
 
 

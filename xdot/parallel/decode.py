@@ -13,13 +13,14 @@ The cache holds the compute dtype, or fp8 (``cache_dtype="fp8"``): OCP e4m3fn by
 
 Forward only, no autograd.  Not covered: document masks at decode time, a device-side ``pos0`` (a
 captured generation loop), cache eviction, per-channel scales, fp8 rows, and an fp8 kernel for the
-shapes the decode kernel does not take, more than 64 rows per gathered head among them (they dequantise
-the whole cache per call).
+shapes neither fp8 kernel takes (fp32 rows, D > 128, Dv != D, more than 128 row heads per gathered head:
+they dequantise the whole cache per call).
 
-More than 64 rows per gathered head over a 16-bit cache (chunked prefill, a long user turn or draft) run
-the row-blocked kernel of ``csrc/flash_extend.hip`` under the same contract, through the same calls;
-D = 96 calls with more than 128 new rows still take the forward kernels over a dense mask
-(:func:`xdot.ops.flash.extend_eligible`, ``profiles/extend.md``)."""
+More than 64 rows per gathered head (chunked prefill, a long user turn or draft) run a row-blocked kernel
+under the same contract, through the same calls: ``csrc/flash_extend.hip`` over a 16-bit cache, where D = 96
+calls with more than 128 new rows still take the forward kernels over a dense mask
+(:func:`xdot.ops.flash.extend_eligible`, ``profiles/extend.md``), and ``csrc/flash_extend8.hip`` over an fp8
+cache at every row count (:func:`xdot.ops.flash.extend_fp8_eligible`, ``profiles/extend_fp8.md``)."""
 from __future__ import annotations
 
 from typing import Optional, Tuple, Union
