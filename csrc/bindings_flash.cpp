@@ -589,6 +589,95 @@ std::tuple<at::Tensor, at::Tensor> flash_extend_fp8(const at::Tensor& rows, cons
                      true);
 }
 
+// ---- paged decode (csrc/flash_paged.hip) ---------------------------------------------------------
+// The decode call for a ragged batch over a pool of pages: qpool / vpool (P, S, Hg*D) the two halves of the
+// pool's slots, pool_pos (P, S) int32 their positions, table (B, maxp) int32 the page of each logical block
+// (-1: a hole), npages (B,) int32 the entries in use, pos0 (B,) int32 the position of each sequence's first
+// new row (negative: inactive).  The three last are read by the kernel: nothing here waits for the device.
+// max_pages: the most pages any sequence holds, if the caller knows better than maxp (it only sizes the grid).
+struct PagedGeom {
+  int64_t B, Rn, C, hg, D, G, P, S, maxp, ld;
+};
+
+PagedGeom paged_check(const char* op, const at::Tensor& rows, const at::Tensor& qpool, const at::Tensor& vpool,
+                      const at::Tensor& pool_pos, const at::Tensor& table, const at::Tensor& npages, const at::Tensor& pos0,
+                      int64_t window, int64_t H, int64_t Hg) {
+  for (const at::Tensor* t : {&rows, &qpool, &vpool, &pool_pos, &table, &npages, &pos0})
+    TORCH_CHECK(t->is_cuda() && t->device() == rows.device(), op, "every tensor must be on the rows' GPU");
+  TORCH_CHECK(rows.scalar_type() == at::kBFloat16 || rows.scalar_type() == at::kHalf, op, "bf16 / fp16 only, got ",
+              rows.scalar_type());
+  TORCH_CHECK(qpool.scalar_type() == rows.scalar_type() && vpool.scalar_type() == rows.scalar_type(), op,
+              "rows, qpool and vpool must have one dtype");
+  TORCH_CHECK(rows.dim() == 3 && rows.is_contiguous(), op, "rows must be a contiguous (B, Rn, H*D) tensor");
+  PagedGeom g{};
+  g.B = rows.size(0); g.Rn = rows.size(1); g.C = rows.size(2); g.hg = Hg > 0 ? Hg : H;
+  TORCH_CHECK(H > 0 && g.C % H == 0 && g.hg <= H && H % g.hg == 0, op, "H = ", H, " must divide the row width ", g.C,
+              " and be a multiple of Hg = ", g.hg);
+  g.D = g.C / H; g.G = H / g.hg;
+  TORCH_CHECK(g.D == 32 || g.D == 64 || g.D == 96 || g.D == 128, op, "head dim must be 32 / 64 / 96 / 128, got ", g.D);
+  TORCH_CHECK(g.B > 0 && g.Rn > 0 && decode_row_tiles(g.G, g.Rn) > 0, op, "G * Rn = ", g.G * g.Rn,
+              " rows per gathered head, the kernel takes 1..", DEC_MAX_ROWS);
+  TORCH_CHECK(qpool.dim() == 3 && qpool.size(0) > 0 && qpool.size(2) == g.hg * g.D && vpool.sizes() == qpool.sizes(), op,
+              "qpool and vpool must be (P, S, Hg*D) = (P, S, ", g.hg * g.D, ")");
+  g.P = qpool.size(0); g.S = qpool.size(1); g.ld = qpool.stride(1);
+  TORCH_CHECK(paged_page_size_ok(g.S), op, "the page size must be 32, 64, 128 or 256 slots, got ", g.S);
+  for (const at::Tensor* t : {&qpool, &vpool}) {
+    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == g.ld && g.ld >= g.hg * g.D && g.ld % 8 == 0 && (g.P == 1 || t->stride(0) == g.S * g.ld),
+                op, "qpool and vpool must be slots of unit inner stride with one slot stride (a multiple of 8) and page stride "
+                    "S * slot stride");
+    TORCH_CHECK((g.P * g.S - 1) * g.ld + g.hg * g.D <= avail_elems(*t), op, "pool view out of bounds");
+  }
+  TORCH_CHECK(aligned16(rows.data_ptr()) && aligned16(qpool.data_ptr()) && aligned16(vpool.data_ptr()), op, "16-byte alignment");
+  TORCH_CHECK(g.P * g.S < (1LL << 31) && g.P * g.S * g.ld < (1LL << 40), op, "pool too large");
+  TORCH_CHECK(pool_pos.scalar_type() == at::kInt && pool_pos.dim() == 2 && pool_pos.size(0) == g.P && pool_pos.size(1) == g.S &&
+                  pool_pos.is_contiguous(),
+              op, "pool_pos must be a contiguous int32 (P, S) = (", g.P, ", ", g.S, ") tensor, got ", pool_pos.scalar_type(), " ",
+              pool_pos.sizes());
+  TORCH_CHECK(table.scalar_type() == at::kInt && table.dim() == 2 && table.size(0) == g.B && table.size(1) > 0 && table.is_contiguous(),
+              op, "table must be a contiguous int32 (B, maxp) = (", g.B, ", maxp) tensor, got ", table.scalar_type(), " ", table.sizes());
+  g.maxp = table.size(1);
+  TORCH_CHECK(g.maxp * g.S < (1LL << 31), op, "table too wide");
+  for (const at::Tensor* t : {&npages, &pos0})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1 && t->size(0) == g.B && t->is_contiguous(), op,
+                "npages and pos0 must be contiguous int32 (B,) = (", g.B, ",) tensors, got ", t->scalar_type(), " ", t->sizes());
+  TORCH_CHECK(window >= 0 && window < (1LL << 31), op, "window must be >= 0 and below 2^31");
+  return g;
+}
+
+std::tuple<at::Tensor, at::Tensor> flash_decode_paged(const at::Tensor& rows, const at::Tensor& qpool, const at::Tensor& vpool,
+                                                      const at::Tensor& pool_pos, const at::Tensor& table, const at::Tensor& npages,
+                                                      const at::Tensor& pos0, int64_t window, int64_t H, double scale, int64_t Hg,
+                                                      int64_t nsplit, bool out_fp32, int64_t max_pages) {
+  Range rr_("xdot.flash_decode_paged");
+  const char* op = "xdot.flash_decode_paged: ";
+  const PagedGeom g = paged_check(op, rows, qpool, vpool, pool_pos, table, npages, pos0, window, H, Hg);
+  TORCH_CHECK(nsplit >= 0 && max_pages >= 0, op, "nsplit and max_pages must be >= 0");
+  c10::DeviceGuard guard(rows.device());
+  const int64_t mp = max_pages > 0 ? std::min(max_pages, g.maxp) : g.maxp, ntiles = mp * (g.S / DEC_TILE);
+  const int ns = nsplit > 0 ? (int)std::min(nsplit, ntiles)
+                            : plan_decode_paged(g.B, g.hg, decode_row_tiles(g.G, g.Rn), mp, g.S, xdot_num_cus());
+  TORCH_CHECK((int64_t)ns * g.B * g.hg < (1LL << 31), op, "too many workgroups");
+  const auto f32 = rows.options().dtype(at::kFloat);
+  auto opart = at::empty({ns, g.B, g.Rn, g.C}, f32), lpart = at::empty({ns, g.B, H, g.Rn}, f32);
+  auto out = at::empty({g.B, g.Rn, g.C}, out_fp32 ? f32 : rows.options()), lse = at::empty({g.B, H, g.Rn}, f32);
+  PagedArgs a{};
+  a.d.rows = rows.data_ptr(); a.d.qc = qpool.data_ptr(); a.d.vc = vpool.data_ptr(); a.d.col_pos = pool_pos.data_ptr<int32_t>();
+  a.d.opart = opart.data_ptr<float>(); a.d.lpart = lpart.data_ptr<float>(); a.d.out = out.data_ptr(); a.d.lse = lse.data_ptr<float>();
+  a.d.B = (int)g.B; a.d.H = (int)H; a.d.Hg = (int)g.hg; a.d.Rn = (int)g.Rn; a.d.ldkv = g.ld;
+  a.d.window = (int)window; a.d.scale = (float)scale; a.d.nspan = ns; a.d.out32 = out_fp32 ? 1 : 0;
+  a.table = table.data_ptr<int32_t>(); a.npages = npages.data_ptr<int32_t>(); a.pos0v = pos0.data_ptr<int32_t>();
+  a.P = (int)g.P; a.S = (int)g.S; a.maxp = (int)g.maxp;
+  launched(xdot_flash_paged_launch(&a, dt_code(rows.scalar_type()), (int)g.D, cur_stream(rows)), "flash_decode_paged");
+  return {out, lse};
+}
+
+// spans plan_decode_paged gives this shape on the current device
+int64_t flash_decode_paged_plan(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int64_t max_pages, int64_t S) {
+  const int nt = decode_row_tiles(G, Rn);
+  TORCH_CHECK(nt > 0 && B > 0 && Hg > 0 && max_pages > 0 && paged_page_size_ok(S), "xdot.flash_decode_paged_plan: shape");
+  return plan_decode_paged(B, Hg, nt, max_pages, S, xdot_num_cus());
+}
+
 // rows (B, n, 2*Hg*D) 16-bit, a row view of row_view.h -> e4m3 bytes and per-chunk scales in slots
 // [at, at + n) of an fp8 cache: qv8 (B, cap, 2*Hg*D) float8_e4m3fn, scales (B, 2*Hg, cap) fp32, both contiguous
 void cache_quant(const at::Tensor& rows, at::Tensor& qv8, at::Tensor& scales, int64_t at_, int64_t Hg) {
@@ -752,6 +841,7 @@ TORCH_LIBRARY_IMPL(xdot, CompositeExplicitAutograd, m) {
   m.impl("flash_rows_plan", &flash_rows_plan);
   m.impl("flash_decode_plan", &flash_decode_plan);
   m.impl("flash_decode_fp8_plan", &flash_decode_fp8_plan);
+  m.impl("flash_decode_paged_plan", &flash_decode_paged_plan);
   m.impl("flash_extend_plan", &flash_extend_plan);
   m.impl("flash_extend_fp8_plan", &flash_extend_fp8_plan);
 }
@@ -760,6 +850,7 @@ TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("flash_fwd", &flash_fwd);
   m.impl("flash_decode", &flash_decode);
   m.impl("flash_decode_fp8", &flash_decode_fp8);
+  m.impl("flash_decode_paged", &flash_decode_paged);
   m.impl("flash_extend", &flash_extend);
   m.impl("flash_extend_fp8", &flash_extend_fp8);
   m.impl("cache_quant", &cache_quant);

@@ -189,6 +189,26 @@ inline int plan_decode_fp8(int64_t B, int64_t Hg, int row_tiles, int D, int64_t 
   return (int)std::max<int64_t>(1, (nt + len - 1) / len);
 }
 
+// ---- paged decode (csrc/flash_paged.hip) -----------------------------------------------------------
+// A page is S slots, a multiple of DEC_TILE, so a tile never straddles two pages.
+inline bool paged_page_size_ok(int64_t S) { return S == 32 || S == 64 || S == 128 || S == 256; }
+// Column spans of a launch.  The lengths of the sequences live on the device, and the host plans without
+// waiting for them: plan_decode over the most slots a sequence can hold, max_pages pages (the width of the
+// block table, or a tighter bound the caller knows).  The kernel runs the dense sweep's body, so the dense
+// sweep's residency targets stand (profiles/paged.md).
+inline int plan_decode_paged(int64_t B, int64_t Hg, int row_tiles, int64_t max_pages, int64_t S, int cus) {
+  return plan_decode(B, Hg, row_tiles, std::max<int64_t>(1, max_pages) * S, cus);
+}
+// What the kernel does with that grid for a sequence of nt tiles: tiles per span (at least 8, as plan_decode
+// asks), and how many of the nspan workgroups sweep one; the others write an empty partial.
+inline int paged_span_tiles(int64_t nt, int nspan) {
+  return (int)std::max<int64_t>(8, (nt + std::max(1, nspan) - 1) / std::max(1, nspan));
+}
+inline int paged_live_spans(int64_t nt, int nspan) {
+  const int64_t len = paged_span_tiles(nt, nspan);
+  return (int)std::min<int64_t>(std::max(1, nspan), (nt + len - 1) / len);
+}
+
 // ---- chunked prefill (csrc/flash_extend.hip) -------------------------------------------------------
 // More than DEC_MAX_ROWS rows per gathered head: one workgroup per (column span, row block, batch, gathered
 // head), a row block being rb consecutive new rows x the G row heads of the group packed into the 4 waves'

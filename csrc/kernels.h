@@ -154,6 +154,18 @@ struct ExtendArgs {
   int rb, nblk;
 };
 
+// paged decode (csrc/flash_paged.hip): the decode call over a pool of pages reached through a block table,
+// with every per-sequence quantity on the device.  Of d: qc / vc are the pool's two halves ((P, S, ldkv)
+// rows), col_pos is pool_pos (P, S); d.Tcap, d.pos0 and d.span_tiles are unused (the kernel cuts its spans
+// from npages)
+struct PagedArgs {
+  DecodeArgs d;
+  const int32_t* table;   // (B, maxp) page of each logical block, -1: a hole
+  const int32_t* npages;  // (B,) table entries in use
+  const int32_t* pos0v;   // (B,) position of the first new row, negative: the sequence is inactive
+  int P, S, maxp;         // pages of the pool, slots per page (32 / 64 / 128 / 256), table width
+};
+
 // cache_quant (csrc/flash_decode8.hip): n rows of a 16-bit (B, n, 2*Hg*D) view -> e4m3 bytes and one
 // fp32 scale per chunk (the D features of one head of q or v) in slots [at, at + n) of an fp8 cache
 struct QuantArgs {
@@ -370,6 +382,9 @@ int xdot_flash_decode_launch(const xdot::fa::DecodeArgs* a, int dt, int D, hipSt
 // the spans' merge alone
 int xdot_flash_decode8_launch(const xdot::fa::DecodeArgs* a, int dt, int D, hipStream_t st);
 int xdot_flash_decode_combine_launch(const xdot::fa::DecodeArgs* a, int dt, int D, hipStream_t st);
+// decode over a paged pool: table, npages and pos0 are read on the device (16-bit, D <= 128, G * Rn <= 64, a
+// page size paged_page_size_ok takes: -1 otherwise)
+int xdot_flash_paged_launch(const xdot::fa::PagedArgs* a, int dt, int D, hipStream_t st);
 // chunked prefill: the row-blocked sweep of the same call for G * Rn > 64 (16-bit, D <= 128; -1 otherwise,
 // or where a->rb rows x G heads exceed the kernel's row block); merges the spans itself when a->d.nspan > 1
 int xdot_flash_extend_launch(const xdot::fa::ExtendArgs* a, int dt, int D, hipStream_t st);

@@ -14,7 +14,7 @@ from .parallel import (distributed_matmul_nt, distributed_matmul_all, distribute
                        distributed_matmul_block, RightTransposeMultiplication, FullMultiplication,
                        LeftTransposeMultiplication, seq_parallel_attention, broadcast_parameters,
                        allreduce_gradients, GradSync, gather_sequence, shard_rows, unshard_rows,
-                       AttnCache, decode_attention)
+                       AttnCache, PagedAttnCache, decode_attention)
 from .models import DistributedDotProductAttn  # noqa: E402,F401
 from .ops import (scale_mask_softmax, linear, FusedAdamW, MSELoss, mse_loss, StructuredMask,  # noqa: E402,F401
                   Rotary, rope, HeadRMSNorm, head_rms_norm, sigmoid_gate)

@@ -96,7 +96,7 @@ Keyword-only knobs (each mirrors an environment flag, the argument
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 import torch.nn as nn
@@ -114,7 +114,7 @@ from ..parallel import attention as pa
 from ..parallel.autograd import FullMultiplication, RightTransposeMultiplication
 from ..parallel.ring import ring_attention_packed
 from ..parallel.layout import check_layout
-from ..parallel.decode import AttnCache, decode_attention
+from ..parallel.decode import AttnCache, PagedAttnCache, decode_attention
 from ..utils import comm as _comm
 from ..utils.env import FLAGS
 
@@ -457,21 +457,51 @@ class DistributedDotProductAttn(nn.Module):
         return AttnCache(batch, capacity, self.num_gathered_heads, self.dim, self.compute_dtype or w.dtype,
                          w.device if device is None else device, cache_dtype=cache_dtype)
 
+    def new_paged_cache(self, batch: int, num_pages: int, page_size: int = 128, device=None) -> PagedAttnCache:
+        """An empty :class:`xdot.PagedAttnCache` for this rank's shard of a ragged batch of ``batch`` sequences:
+        ``num_pages`` pages of ``page_size`` slots, shared by the sequences, in the compute dtype."""
+        if self.value_dim // self.num_heads != self.dim:
+            raise ValueError("new_paged_cache: the cache keeps [q | v] at one head dim; this module's value heads are "
+                             f"{self.value_dim // self.num_heads} wide, its key heads {self.dim}")
+        w = self.queries.weight
+        return PagedAttnCache(batch, num_pages, page_size, self.num_gathered_heads, self.dim, self.compute_dtype or w.dtype,
+                              w.device if device is None else device)
+
+    def _prep_ragged(self, x: Tensor, ncols: int, heads: int, row_side: bool, pos) -> Tensor:
+        """:meth:`_prep` of ``x`` (B, n, C) with sequence ``b``'s rows at ``pos[b], pos[b] + 1, ...``: the batch
+        seen as one sequence of ``B`` row runs."""
+        B, n, C = x.shape
+        runs = tuple((b * n, n, int(p)) for b, p in enumerate(pos))
+        if len(runs) != B:
+            raise ValueError(f"{len(runs)} positions for {B} sequences")
+        return self._prep(x.reshape(1, B * n, C), ncols, heads, row_side, runs).reshape(B, n, C)
+
     @torch.no_grad()
-    def cache_append(self, cache: AttnCache, queries: Tensor, values: Tensor, pos) -> None:
+    def cache_append(self, cache: Union[AttnCache, PagedAttnCache], queries: Tensor, values: Tensor, pos,
+                     seq: Optional[int] = None) -> None:
         """Project ``queries`` / ``values`` (B, n, dim) to ``[q | v]``, norm and rotate ``q`` at ``pos`` (the
         first of ``n`` consecutive global positions, or an ``(n,)`` tensor) and append the rows to ``cache``.
         After a prefill forward: one call with this rank's rows and their first position (``rank * R``;
         under ``layout='zigzag'`` two calls, one per run of :func:`xdot.parallel.layout.row_runs`).  While
-        generating: one call with the new token's row on the rank that owns it."""
+        generating: one call with the new token's row on the rank that owns it.
+
+        A :class:`xdot.PagedAttnCache` takes ``pos`` as an int or a list of ``B`` ints, one first position per
+        sequence; with ``seq=b`` the rows (1, n, dim) go to sequence ``b`` alone (a ragged prefill)."""
         with _ext.backend(self.backend):
             queries, values = self._cdt(queries, values)
             Hg = self.num_gathered_heads
+            if isinstance(cache, PagedAttnCache) and seq is None:
+                pos = [int(p) for p in pos] if isinstance(pos, (list, tuple)) else [int(pos)] * queries.shape[0]
+                cache.append(self._prep_ragged(self._project_qv(queries, values), Hg * self.dim, Hg, False, pos), pos)
+                return
             qv = self._prep(self._project_qv(queries, values), Hg * self.dim, Hg, False, self._pos_runs(pos, queries.shape[1]))
-            cache.append(qv, pos)
+            if isinstance(cache, PagedAttnCache):
+                cache.append_seq(seq, qv, pos)
+            else:
+                cache.append(qv, pos)
 
     @torch.no_grad()
-    def decode(self, keys: Tensor, cache: AttnCache, pos: int, window: Optional[int] = None) -> Tensor:
+    def decode(self, keys: Tensor, cache: Union[AttnCache, PagedAttnCache], pos, window: Optional[int] = None) -> Tensor:
         """The module's output (B, Rn, value_dim) for ``Rn`` new rows ``keys`` at global positions ``pos,
         pos + 1, ...``, attending causally (and within ``window``) to what the ranks' caches hold: ``k``
         projection, norm, rope at ``pos``, :func:`xdot.decode_attention` (sinks included), gate,
@@ -484,13 +514,21 @@ class DistributedDotProductAttn(nn.Module):
                     module.cache_append(cache, x, x, T + step)
                 y = module.decode(x, cache, T + step)
                 x = next_input(y)
+
+        With a :class:`xdot.PagedAttnCache` the batch is ragged: ``pos`` is an int or a list of ``B`` ints,
+        sequence ``b``'s rows sit at ``pos[b], pos[b] + 1, ...`` and attend to its own pages.
         """
         with _ext.backend(self.backend):
             out_dt, H = keys.dtype, self.num_heads
             (keys,) = self._cdt(keys)
             comm = (self.comm or _comm.get_comm()) if self.distributed else _comm.LocalComm()
-            k = self._prep(self._proj(self.keys, keys), H * self.dim, H, True, int(pos))
-            o, _ = decode_attention(k, cache, int(pos), num_heads=H, scale=1.0 / math.sqrt(self.dim), window=window,
+            if isinstance(cache, PagedAttnCache):
+                pos = [int(p) for p in pos] if isinstance(pos, (list, tuple)) else [int(pos)] * keys.shape[0]
+                k = self._prep_ragged(self._proj(self.keys, keys), H * self.dim, H, True, pos)
+            else:
+                pos = int(pos)
+                k = self._prep(self._proj(self.keys, keys), H * self.dim, H, True, pos)
+            o, _ = decode_attention(k, cache, pos, num_heads=H, scale=1.0 / math.sqrt(self.dim), window=window,
                                     sinks=self.sinks, comm=comm)
             return self._proj(self.composition, self._gated(o, keys)).to(out_dt)
 

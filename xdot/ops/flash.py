@@ -494,6 +494,76 @@ def decode_plan(B: int, Hg: int, G: int, Rn: int, Tcap: int, fp8_head_dim: int =
     return int(_ext.ops().flash_decode_plan(int(B), int(Hg), int(G), int(Rn), int(Tcap)))
 
 
+# ---- paged decode: a ragged batch against a pool of pages (csrc/flash_paged.hip) --------------------
+PAGE_SIZES = (32, 64, 128, 256)
+_POS_SHIFT = 1 << 30   # positions are documented to stay below this
+
+
+def decode_paged_eligible(dtype: torch.dtype, D: int, Dv: int, G: int, Rn: int, page_size: int) -> bool:
+    """The paged decode kernel takes this call: :func:`decode_eligible`'s shapes (16-bit, one head dim of
+    32 / 64 / 96 / 128, at most 64 rows per gathered head) over pages of 32, 64, 128 or 256 slots."""
+    return decode_eligible(dtype, D, Dv, G, Rn) and int(page_size) in PAGE_SIZES
+
+
+def decode_paged(rows: torch.Tensor, qpool: torch.Tensor, vpool: torch.Tensor, pool_pos: torch.Tensor,
+                 table: torch.Tensor, npages: torch.Tensor, pos0: torch.Tensor, H: int, scale: float, window: int = 0,
+                 Hg: Optional[int] = None, nsplit: int = 0, out_fp32: bool = False,
+                 max_pages: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """:func:`decode` for a ragged batch over a paged cache -> (out (B, Rn, H*D) in ``rows.dtype``, lse
+    (B, H, Rn) fp32 natural log).
+
+    ``rows`` (B, Rn, H*D): ``Rn`` new rows of each of ``B`` sequences.  ``qpool`` / ``vpool`` (P, S, Hg*D): a
+    pool of ``P`` pages of ``S`` slots, unit inner stride and one slot stride (the two halves of one ``[q|v]``
+    pool).  ``pool_pos`` (P, S) int32: the global position of each slot, -1 = empty.  ``table`` (B, maxp)
+    int32: the page of each logical block of each sequence, -1 = a hole.  ``npages`` (B,) int32: the table
+    entries in use.  ``pos0`` (B,) int32: the position of each sequence's first new row; negative = the
+    sequence is inactive and its rows see nothing.  Positions stay below ``2**30``.
+
+    A slot of one of sequence ``b``'s pages is visible to its row ``i`` iff ``0 <= pos <= pos0[b] + i`` and
+    (``window == 0`` or ``pos > pos0[b] + i - window``): :func:`decode`'s rule per sequence.  Slot and page order
+    are free.  A row that sees nothing (an inactive sequence, one without pages) comes out NaN with lse -inf.
+
+    ``table``, ``npages`` and ``pos0`` are read by the kernel, on the device: the call never waits for them,
+    and a captured launch serves the next step once they are updated in place.  A table entry outside
+    ``[0, P)`` that is not -1 gives an unspecified result for its sequence, never an access outside the pool.
+    ``nsplit``: column spans (0: ``plan_decode_paged`` of ``csrc/flash_plan.h``, over ``max_pages`` pages per
+    sequence: the table's width, or a tighter bound the caller knows; it sizes the grid only).
+
+    Calls the kernel does not take (:func:`decode_paged_eligible`: fp32 rows, D > 128, Dv != D, more than 64
+    rows per gathered head, another page size) stay on the device without a kernel of their own: the pages are
+    gathered into a dense (B, maxp*S, .) cache, every sequence's positions are shifted by ``2**30 - pos0[b]``
+    (visibility depends on ``pos - pos0[b]`` only) and :func:`decode` runs at ``pos0 = 2**30``.  CPU tensors and
+    ``backend='torch'`` run ``xdot.parallel._ref.decode_paged``."""
+    from ..parallel import _ref  # (xdot.parallel imports this module)
+
+    B, Rn, C = rows.shape
+    hg = int(Hg) if Hg else int(H)
+    D, Dv, window = C // H, vpool.shape[-1] // hg, int(window or 0)
+    if not _ext.use_hip(rows, qpool, vpool):
+        o, lse = _ref.decode_paged(rows, qpool, vpool, pool_pos, table, npages, pos0, int(H), float(scale), window, Hg)
+        return (o if out_fp32 else o.to(rows.dtype)), lse
+    if decode_paged_eligible(rows.dtype, D, Dv, H // hg, Rn, qpool.shape[1]):
+        return _ext.ops().flash_decode_paged(rows.contiguous(), qpool, vpool, pool_pos, table, npages, pos0, window, int(H),
+                                             float(scale), hg, int(nsplit), bool(out_fp32), int(max_pages or 0))
+    return _decode_paged_gathered(rows, qpool, vpool, pool_pos, table, npages, pos0, H, scale, window, Hg, nsplit, out_fp32)
+
+
+def _decode_paged_gathered(rows, qpool, vpool, pool_pos, table, npages, pos0, H, scale, window=0, Hg=None, nsplit=0,
+                           out_fp32=False):
+    """:func:`decode_paged` without its kernel: gather to a dense cache, shift the positions, :func:`decode`."""
+    from ..parallel import _ref
+
+    qc, vc, pos = _ref.paged_gather(qpool, vpool, pool_pos, table, npages)
+    p0 = pos0.to(torch.int64).view(-1, 1)
+    pos = torch.where((pos >= 0) & (p0 >= 0), pos + (_POS_SHIFT - p0), pos.new_full((), -1)).to(torch.int32)
+    return decode(rows, qc, vc, pos, _POS_SHIFT, H, scale, window, Hg, nsplit, out_fp32)
+
+
+def decode_paged_plan(B: int, Hg: int, G: int, Rn: int, max_pages: int, page_size: int) -> int:
+    """Column spans an automatic :func:`decode_paged` launch takes on the current device."""
+    return int(_ext.ops().flash_decode_paged_plan(int(B), int(Hg), int(G), int(Rn), int(max_pages), int(page_size)))
+
+
 # ---- chunked prefill: many new rows against one rank's cache (csrc/flash_extend.hip) ---------------
 EXTEND_MAX_GROUP = 128   # row heads per gathered head: one new row of a group fits the smallest row block
 _EXTEND_MAX_NEW_ROWS = {96: 128}   # head dim -> the most new rows the kernel won the A/B at (profiles/extend.md)

@@ -7,4 +7,4 @@ from .attention import seq_parallel_attention, SeqParallelAttention  # noqa: F40
 from .data_parallel import broadcast_parameters, allreduce_gradients, GradSync  # noqa: F401
 from .schedule import plan_chunks, auto_offset  # noqa: F401
 from .layout import shard_rows, unshard_rows  # noqa: F401
-from .decode import AttnCache, decode_attention  # noqa: F401
+from .decode import AttnCache, PagedAttnCache, decode_attention  # noqa: F401

@@ -78,6 +78,31 @@ def decode(rows, qc, vc, col_pos, pos0: int, H: int, scale: float, window: int =
     return block_fwd(rows, qc, vc, decode_mask(col_pos, pos0, rows.shape[1], window), H, scale, Hg)
 
 
+def paged_gather(qpool, vpool, pool_pos, table, npages):
+    """A paged cache as the dense one every sequence would have: ``qpool`` / ``vpool`` (P, S, Hg*d) and
+    ``pool_pos`` (P, S) gathered by ``table`` (B, maxp) -> (qc, vc (B, maxp*S, Hg*d), col_pos (B, maxp*S) int64);
+    the slots of a hole (-1), of an entry outside the pool and of the entries at or past ``npages[b]`` are empty
+    (-1).  No host synchronisation."""
+    (B, maxp), (P, S) = table.shape, pool_pos.shape
+    t = table.to(torch.int64)
+    live = (t >= 0) & (t < P) & (torch.arange(maxp, device=table.device).unsqueeze(0) < npages.to(torch.int64).unsqueeze(1))
+    idx = t.clamp(0, P - 1).reshape(-1)
+    qc, vc = (x.index_select(0, idx).reshape(B, maxp * S, x.shape[-1]) for x in (qpool, vpool))
+    pos = pool_pos.index_select(0, idx).reshape(B, maxp, S).to(torch.int64)
+    return qc, vc, torch.where(live.unsqueeze(-1), pos, pos.new_full((), -1)).reshape(B, maxp * S)
+
+
+def decode_paged(rows, qpool, vpool, pool_pos, table, npages, pos0, H: int, scale: float, window: int = 0, Hg=None):
+    """:func:`decode` per sequence of a ragged batch over a paged cache (:func:`paged_gather`), sequence ``b``'s
+    rows at ``pos0[b], pos0[b] + 1, ...``; a sequence with a negative ``pos0`` sees nothing."""
+    qc, vc, pos = paged_gather(qpool, vpool, pool_pos, table, npages)
+    outs = []
+    for b, p0 in enumerate(int(p) for p in pos0.tolist()):
+        cp = pos[b:b + 1] if p0 >= 0 else torch.full_like(pos[b:b + 1], -1)
+        outs.append(decode(rows[b:b + 1], qc[b:b + 1], vc[b:b + 1], cp, max(p0, 0), H, scale, window, Hg))
+    return torch.cat([o for o, _ in outs]), torch.cat([l for _, l in outs])
+
+
 def cache_quant(x, Hg: int):
     """The fp8 cache format, literally: ``x`` (..., 2*Hg*D) 16-bit rows ``[q | v]`` -> (bytes (..., 2*Hg*D)
     ``float8_e4m3fn``, scales (..., 2*Hg) fp32), one scale per chunk of ``D`` features (one head of ``q`` or

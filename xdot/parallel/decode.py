@@ -11,8 +11,16 @@ The cache holds the compute dtype, or fp8 (``cache_dtype="fp8"``): OCP e4m3fn by
 (slot, gathered head) for each of ``q`` and ``v``, quantised once when a row is appended
 (``csrc/flash_decode8.hip``): ``2*Hg*D + 8*Hg + 4`` bytes per slot instead of ``4*Hg*D + 4``.
 
-Forward only, no autograd.  Not covered: document masks at decode time, a device-side ``pos0`` (a
-captured generation loop), cache eviction, per-channel scales, fp8 rows, and an fp8 kernel for the
+A ragged batch (sequences of different lengths that come and go) keeps its slots in pages
+(:class:`PagedAttnCache`): one pool shared by the sequences, reached through a block table, with every
+sequence's length and row position on the device (:func:`xdot.ops.flash.decode_paged`,
+``csrc/flash_paged.hip``).  A sequence that ends gives its pages to the next one, and a generation step is
+one launch whose arguments do not change, so it can be captured.
+
+Forward only, no autograd.  Not covered: document masks at decode time, eviction of single slots (a
+sequence frees all its pages or none), an fp8 paged pool, a paged chunked-prefill kernel (more than 64 rows
+per gathered head over pages gather them into a dense cache per call), a device-side ``pos0`` for the dense
+:class:`AttnCache`, per-channel scales, fp8 rows, and an fp8 kernel for the
 shapes neither fp8 kernel takes (fp32 rows, D > 128, Dv != D, more than 128 row heads per gathered head:
 they dequantise the whole cache per call).
 
@@ -33,7 +41,7 @@ from ..ops import flash
 from ..utils import comm as _comm
 from . import _ref
 
-__all__ = ["AttnCache", "decode_attention"]
+__all__ = ["AttnCache", "PagedAttnCache", "decode_attention"]
 
 
 class AttnCache:
@@ -113,8 +121,108 @@ class AttnCache:
         self.fill = at + n
 
 
+class PagedAttnCache:
+    """One rank's shard of the gathered side of a ragged batch, in pages: ``qv`` (num_pages, page_size,
+    2*Hg*D) a pool of slots ``[q | v]`` shared by the ``batch`` sequences, ``pos`` (num_pages, page_size)
+    int32 the global position of each slot (-1 = empty), ``table`` (batch, num_pages) int32 the page of each
+    logical block of each sequence (-1 past its pages) and ``npages`` (batch,) int32 the entries in use: the
+    format of :func:`xdot.ops.flash.decode_paged`, which reads the last three on the device.  The free list and
+    the sequences' lengths are kept on the host, so appending and freeing never wait for the device.  A
+    sequence takes a page when its last one is full and gives all of them back with :meth:`free`."""
+
+    def __init__(self, batch: int, num_pages: int, page_size: int, Hg: int, D: int, dtype: torch.dtype, device=None):
+        if min(int(batch), int(num_pages), int(Hg), int(D)) < 1 or int(page_size) not in flash.PAGE_SIZES:
+            raise ValueError("PagedAttnCache: batch, num_pages, Hg and D must be positive and page_size one of "
+                             f"{flash.PAGE_SIZES}, got {(batch, num_pages, page_size, Hg, D)}")
+        self.Hg, self.D, self.page_size, self.num_pages, self.dtype = int(Hg), int(D), int(page_size), int(num_pages), dtype
+        # zeros: the kernel multiplies empty slots' v by a probability of 0
+        self.qv = torch.zeros(self.num_pages, self.page_size, 2 * self.Hg * self.D, device=device, dtype=dtype)
+        self.pos = torch.full((self.num_pages, self.page_size), -1, dtype=torch.int32, device=device)
+        self.table = torch.full((int(batch), self.num_pages), -1, dtype=torch.int32, device=device)
+        self.npages = torch.zeros(int(batch), dtype=torch.int32, device=device)
+        self.free_pages = list(range(self.num_pages - 1, -1, -1))  # taken from the end: page 0 first
+        self.pages = [[] for _ in range(int(batch))]                # of each sequence, in logical order
+        self.lens = [0] * int(batch)                                # slots taken by each sequence
+
+    @property
+    def q(self) -> Tensor:
+        return self.qv[..., :self.Hg * self.D]
+
+    @property
+    def v(self) -> Tensor:
+        return self.qv[..., self.Hg * self.D:]
+
+    def _take(self, seqs, n: int) -> Tensor:
+        """Give each sequence of ``seqs`` the pages its next ``n`` rows need (all of them or, on a full pool,
+        none) -> the rows' flat slot indices (len(seqs) * n,) int64 on the host."""
+        S = self.page_size
+        need = [(self.lens[b] + n + S - 1) // S - len(self.pages[b]) for b in seqs]
+        if sum(need) > len(self.free_pages):
+            raise RuntimeError(f"PagedAttnCache: {n} rows for {len(seqs)} sequence(s) need {sum(need)} pages, "
+                               f"{len(self.free_pages)} of {self.num_pages} are free")
+        slots = []
+        for b, k in zip(seqs, need):
+            if k > 0:
+                new = [self.free_pages.pop() for _ in range(k)]
+                at = len(self.pages[b])
+                self.pages[b] += new
+                self.table[b, at:at + k] = torch.tensor(new, dtype=torch.int32)
+            i = torch.arange(self.lens[b], self.lens[b] + n)
+            slots.append(torch.tensor(self.pages[b], dtype=torch.int64)[i // S] * S + i % S)
+            self.lens[b] += n
+        if any(k > 0 for k in need):
+            self.npages.copy_(torch.tensor([len(p) for p in self.pages], dtype=torch.int32))
+        return torch.cat(slots)
+
+    def _write(self, seqs, rows: Tensor, first) -> None:
+        """``rows`` (len(seqs) * n, 2*Hg*D) into the next slots of ``seqs``, at the positions ``first`` (per
+        sequence: the first of ``n`` consecutive ones, or ``n`` of them)."""
+        n = rows.shape[0] // len(seqs)
+        if n == 0:
+            return
+        p = torch.stack([f.reshape(n).to("cpu", torch.int64) if isinstance(f, Tensor) else torch.arange(int(f), int(f) + n)
+                         for f in first]).reshape(-1)
+        at = torch.stack([self._take(seqs, n), p]).to(self.qv.device)  # one copy to the device
+        self.qv.view(-1, self.qv.shape[-1]).index_copy_(0, at[0], rows.to(self.dtype))
+        self.pos.view(-1).index_copy_(0, at[0], at[1].to(torch.int32))
+
+    def _rows(self, qv: Tensor, B: int, who: str) -> Tensor:
+        if qv.dim() != 3 or qv.shape[0] != B or qv.shape[2] != self.qv.shape[2]:
+            raise ValueError(f"PagedAttnCache.{who}: qv must be ({B}, n, 2*Hg*D = {self.qv.shape[2]}), got {tuple(qv.shape)}")
+        return qv.reshape(-1, qv.shape[2])
+
+    @torch.no_grad()
+    def append(self, qv: Tensor, positions) -> None:
+        """Append ``qv`` (B, n, 2*Hg*D): ``n`` rows to every sequence.  ``positions``: the global position of
+        the first of the ``n`` consecutive ones, an int for all sequences or a list of ``B`` ints."""
+        B = len(self.pages)
+        first = [int(p) for p in positions] if isinstance(positions, (list, tuple)) else [int(positions)] * B
+        if len(first) != B:
+            raise ValueError(f"PagedAttnCache.append: {len(first)} positions for {B} sequences")
+        self._write(list(range(B)), self._rows(qv, B, "append"), first)
+
+    @torch.no_grad()
+    def append_seq(self, b: int, qv: Tensor, position) -> None:
+        """Append ``qv`` (1, n, 2*Hg*D) to sequence ``b`` alone (a ragged prefill).  ``position``: the first of
+        ``n`` consecutive global positions (int), or an ``(n,)`` integer tensor."""
+        if not 0 <= int(b) < len(self.pages):
+            raise IndexError(f"PagedAttnCache.append_seq: sequence {b} of {len(self.pages)}")
+        self._write([int(b)], self._rows(qv, 1, "append_seq"), [position])
+
+    @torch.no_grad()
+    def free(self, b: int) -> None:
+        """Empty sequence ``b``: its slots' positions become -1 and its pages return to the free list."""
+        pages = self.pages[b]
+        if pages:
+            self.pos.index_fill_(0, torch.tensor(pages, dtype=torch.int64).to(self.pos.device), -1)
+            self.table[b, :len(pages)] = -1
+            self.npages[b] = 0
+            self.free_pages += reversed(pages)
+        self.pages[b], self.lens[b] = [], 0
+
+
 @torch.no_grad()
-def decode_attention(rows: Tensor, cache: AttnCache, pos0: int, *, num_heads: int, scale: float,
+def decode_attention(rows: Tensor, cache: Union[AttnCache, PagedAttnCache], pos0, *, num_heads: int, scale: float,
                      window: Optional[int] = None, sinks: Optional[Tensor] = None,
                      comm: Optional[_comm.Communicator] = None) -> Tuple[Tensor, Tensor]:
     """``rows`` (B, Rn, H*D), the new rows' ``k`` (after norm and rope) at positions ``pos0, pos0 + 1, ...``,
@@ -123,11 +231,20 @@ def decode_attention(rows: Tensor, cache: AttnCache, pos0: int, *, num_heads: in
 
     Each rank runs :func:`xdot.ops.flash.decode` over its own shard; with ``comm.world_size > 1`` one
     all-gather of the fp32 ``[o | lse]`` and one merge over the ``N`` slots follow, then the sink fold
-    (``sinks`` (H,)), under which a row that sees nothing anywhere gives 0."""
+    (``sinks`` (H,)), under which a row that sees nothing anywhere gives 0.
+
+    With a :class:`PagedAttnCache` the batch is ragged: ``pos0`` is a list of ``B`` ints or a ``(B,)`` int32
+    tensor on the rows' device (negative: the sequence is inactive), and each rank runs
+    :func:`xdot.ops.flash.decode_paged` over its pool."""
     comm = comm if comm is not None else _comm.get_comm()
     H, n = int(num_heads), comm.world_size
-    o, lse = flash.decode(rows, cache.q, cache.v, cache.pos, int(pos0), H, scale, int(window or 0), Hg=cache.Hg,
-                          out_fp32=n > 1, qscale=cache.qscale, vscale=cache.vscale)
+    if isinstance(cache, PagedAttnCache):
+        p0 = pos0 if isinstance(pos0, Tensor) else torch.tensor([int(p) for p in pos0], dtype=torch.int32).to(rows.device)
+        o, lse = flash.decode_paged(rows, cache.q, cache.v, cache.pos, cache.table, cache.npages, p0, H, scale,
+                                    int(window or 0), Hg=cache.Hg, out_fp32=n > 1)
+    else:
+        o, lse = flash.decode(rows, cache.q, cache.v, cache.pos, int(pos0), H, scale, int(window or 0), Hg=cache.Hg,
+                              out_fp32=n > 1, qscale=cache.qscale, vscale=cache.vscale)
     hip = _ext.use_hip(rows)
     if n > 1:
         no = o.numel()
