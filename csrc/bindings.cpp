@@ -436,6 +436,12 @@ TORCH_LIBRARY(xdot, m) {
   m.def("flash_decode_paged(Tensor rows, Tensor qpool, Tensor vpool, Tensor pool_pos, Tensor table, Tensor npages, "
         "Tensor pos0, int window, int H, float scale, int Hg=0, int nsplit=0, bool out_fp32=False, int max_pages=0) -> (Tensor, Tensor)");
   m.def("flash_decode_paged_plan(int B, int Hg, int G, int Rn, int max_pages, int S) -> int");
+  m.def("flash_decode_paged_fp8(Tensor rows, Tensor qpool, Tensor vpool, Tensor qscale, Tensor vscale, Tensor pool_pos, "
+        "Tensor table, Tensor npages, Tensor pos0, int window, int H, float scale, int Hg=0, int nsplit=0, bool out_fp32=False, "
+        "int max_pages=0) -> (Tensor, Tensor)");
+  m.def("flash_decode_paged_fp8_plan(int B, int Hg, int G, int Rn, int D, int max_pages, int S) -> int");
+  m.def("cache_quant_paged(Tensor rows, Tensor(a!) qv8, Tensor(b!) scales, Tensor(c!) pool_pos, Tensor slots, Tensor positions, "
+        "int Hg) -> ()");
   m.def("flash_extend(Tensor rows, Tensor qc, Tensor vc, Tensor col_pos, int pos0, int window, int H, float scale, "
         "int Hg=0, int nsplit=0, bool out_fp32=False) -> (Tensor, Tensor)");
   m.def("flash_extend_plan(int B, int Hg, int G, int Rn, int D, int Tcap) -> int");

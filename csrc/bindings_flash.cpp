@@ -601,13 +601,18 @@ struct PagedGeom {
 
 PagedGeom paged_check(const char* op, const at::Tensor& rows, const at::Tensor& qpool, const at::Tensor& vpool,
                       const at::Tensor& pool_pos, const at::Tensor& table, const at::Tensor& npages, const at::Tensor& pos0,
-                      int64_t window, int64_t H, int64_t Hg) {
+                      int64_t window, int64_t H, int64_t Hg, bool fp8 = false) {
   for (const at::Tensor* t : {&rows, &qpool, &vpool, &pool_pos, &table, &npages, &pos0})
     TORCH_CHECK(t->is_cuda() && t->device() == rows.device(), op, "every tensor must be on the rows' GPU");
   TORCH_CHECK(rows.scalar_type() == at::kBFloat16 || rows.scalar_type() == at::kHalf, op, "bf16 / fp16 only, got ",
               rows.scalar_type());
-  TORCH_CHECK(qpool.scalar_type() == rows.scalar_type() && vpool.scalar_type() == rows.scalar_type(), op,
-              "rows, qpool and vpool must have one dtype");
+  if (fp8) {
+    TORCH_CHECK(qpool.scalar_type() == at::kFloat8_e4m3fn && vpool.scalar_type() == at::kFloat8_e4m3fn, op,
+                "qpool and vpool must be float8_e4m3fn, got ", qpool.scalar_type(), " and ", vpool.scalar_type());
+  } else {
+    TORCH_CHECK(qpool.scalar_type() == rows.scalar_type() && vpool.scalar_type() == rows.scalar_type(), op,
+                "rows, qpool and vpool must have one dtype");
+  }
   TORCH_CHECK(rows.dim() == 3 && rows.is_contiguous(), op, "rows must be a contiguous (B, Rn, H*D) tensor");
   PagedGeom g{};
   g.B = rows.size(0); g.Rn = rows.size(1); g.C = rows.size(2); g.hg = Hg > 0 ? Hg : H;
@@ -621,10 +626,11 @@ PagedGeom paged_check(const char* op, const at::Tensor& rows, const at::Tensor& 
               "qpool and vpool must be (P, S, Hg*D) = (P, S, ", g.hg * g.D, ")");
   g.P = qpool.size(0); g.S = qpool.size(1); g.ld = qpool.stride(1);
   TORCH_CHECK(paged_page_size_ok(g.S), op, "the page size must be 32, 64, 128 or 256 slots, got ", g.S);
+  const int64_t ldq = fp8 ? 16 : 8;  // slots on the 16-byte grid
   for (const at::Tensor* t : {&qpool, &vpool}) {
-    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == g.ld && g.ld >= g.hg * g.D && g.ld % 8 == 0 && (g.P == 1 || t->stride(0) == g.S * g.ld),
-                op, "qpool and vpool must be slots of unit inner stride with one slot stride (a multiple of 8) and page stride "
-                    "S * slot stride");
+    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == g.ld && g.ld >= g.hg * g.D && g.ld % ldq == 0 && (g.P == 1 || t->stride(0) == g.S * g.ld),
+                op, "qpool and vpool must be slots of unit inner stride with one slot stride (a multiple of ", ldq,
+                ") and page stride S * slot stride");
     TORCH_CHECK((g.P * g.S - 1) * g.ld + g.hg * g.D <= avail_elems(*t), op, "pool view out of bounds");
   }
   TORCH_CHECK(aligned16(rows.data_ptr()) && aligned16(qpool.data_ptr()) && aligned16(vpool.data_ptr()), op, "16-byte alignment");
@@ -644,18 +650,34 @@ PagedGeom paged_check(const char* op, const at::Tensor& rows, const at::Tensor& 
   return g;
 }
 
-std::tuple<at::Tensor, at::Tensor> flash_decode_paged(const at::Tensor& rows, const at::Tensor& qpool, const at::Tensor& vpool,
-                                                      const at::Tensor& pool_pos, const at::Tensor& table, const at::Tensor& npages,
-                                                      const at::Tensor& pos0, int64_t window, int64_t H, double scale, int64_t Hg,
-                                                      int64_t nsplit, bool out_fp32, int64_t max_pages) {
-  Range rr_("xdot.flash_decode_paged");
-  const char* op = "xdot.flash_decode_paged: ";
-  const PagedGeom g = paged_check(op, rows, qpool, vpool, pool_pos, table, npages, pos0, window, H, Hg);
+// qscale / vscale set: the pool is fp8 (e4m3fn bytes, slot stride in bytes) with fp32 (P, Hg, S) scale views, the
+// two halves of one (P, 2*Hg, S) buffer (csrc/flash_paged8.hip); every other check is the 16-bit call's.
+std::tuple<at::Tensor, at::Tensor> paged_call(const char* op, const char* what, const at::Tensor& rows, const at::Tensor& qpool,
+                                              const at::Tensor& vpool, const at::Tensor* qscale, const at::Tensor* vscale,
+                                              const at::Tensor& pool_pos, const at::Tensor& table, const at::Tensor& npages,
+                                              const at::Tensor& pos0, int64_t window, int64_t H, double scale, int64_t Hg,
+                                              int64_t nsplit, bool out_fp32, int64_t max_pages) {
+  const bool fp8 = qscale != nullptr;
+  const PagedGeom g = paged_check(op, rows, qpool, vpool, pool_pos, table, npages, pos0, window, H, Hg, fp8);
   TORCH_CHECK(nsplit >= 0 && max_pages >= 0, op, "nsplit and max_pages must be >= 0");
+  if (fp8) {
+    for (const at::Tensor* t : {qscale, vscale}) {
+      TORCH_CHECK(t->is_cuda() && t->device() == rows.device() && t->scalar_type() == at::kFloat && t->dim() == 3 &&
+                      t->size(0) == g.P && t->size(1) == g.hg && t->size(2) == g.S && t->stride(2) == 1 && t->stride(1) == g.S &&
+                      t->strides() == qscale->strides() && t->stride(0) >= g.hg * g.S && t->stride(0) % 4 == 0 &&
+                      aligned16(t->data_ptr()),
+                  op, "qscale and vscale must be fp32 (P, Hg, S) = (", g.P, ", ", g.hg, ", ", g.S,
+                  ") views on the rows' GPU with unit inner stride, head stride S, one 16-byte aligned page stride");
+      TORCH_CHECK((g.P - 1) * t->stride(0) + g.hg * g.S <= avail_elems(*t), op, "scale view out of bounds");
+    }
+    TORCH_CHECK(g.P * qscale->stride(0) < (1LL << 40), op, "pool too large");
+  }
   c10::DeviceGuard guard(rows.device());
   const int64_t mp = max_pages > 0 ? std::min(max_pages, g.maxp) : g.maxp, ntiles = mp * (g.S / DEC_TILE);
+  const int nrt = decode_row_tiles(g.G, g.Rn), cus = xdot_num_cus();
   const int ns = nsplit > 0 ? (int)std::min(nsplit, ntiles)
-                            : plan_decode_paged(g.B, g.hg, decode_row_tiles(g.G, g.Rn), mp, g.S, xdot_num_cus());
+                 : fp8      ? plan_decode_paged_fp8(g.B, g.hg, nrt, (int)g.D, mp, g.S, cus)
+                            : plan_decode_paged(g.B, g.hg, nrt, mp, g.S, cus);
   TORCH_CHECK((int64_t)ns * g.B * g.hg < (1LL << 31), op, "too many workgroups");
   const auto f32 = rows.options().dtype(at::kFloat);
   auto opart = at::empty({ns, g.B, g.Rn, g.C}, f32), lpart = at::empty({ns, g.B, H, g.Rn}, f32);
@@ -667,8 +689,34 @@ std::tuple<at::Tensor, at::Tensor> flash_decode_paged(const at::Tensor& rows, co
   a.d.window = (int)window; a.d.scale = (float)scale; a.d.nspan = ns; a.d.out32 = out_fp32 ? 1 : 0;
   a.table = table.data_ptr<int32_t>(); a.npages = npages.data_ptr<int32_t>(); a.pos0v = pos0.data_ptr<int32_t>();
   a.P = (int)g.P; a.S = (int)g.S; a.maxp = (int)g.maxp;
-  launched(xdot_flash_paged_launch(&a, dt_code(rows.scalar_type()), (int)g.D, cur_stream(rows)), "flash_decode_paged");
+  if (fp8) {
+    a.d.qscale = qscale->data_ptr<float>(); a.d.vscale = vscale->data_ptr<float>();
+    a.d.sc_head = g.S; a.d.sc_batch = qscale->stride(0);
+    launched(xdot_flash_paged8_launch(&a, dt_code(rows.scalar_type()), (int)g.D, cur_stream(rows)), what);
+  } else {
+    launched(xdot_flash_paged_launch(&a, dt_code(rows.scalar_type()), (int)g.D, cur_stream(rows)), what);
+  }
   return {out, lse};
+}
+
+std::tuple<at::Tensor, at::Tensor> flash_decode_paged(const at::Tensor& rows, const at::Tensor& qpool, const at::Tensor& vpool,
+                                                      const at::Tensor& pool_pos, const at::Tensor& table, const at::Tensor& npages,
+                                                      const at::Tensor& pos0, int64_t window, int64_t H, double scale, int64_t Hg,
+                                                      int64_t nsplit, bool out_fp32, int64_t max_pages) {
+  Range rr_("xdot.flash_decode_paged");
+  return paged_call("xdot.flash_decode_paged: ", "flash_decode_paged", rows, qpool, vpool, nullptr, nullptr, pool_pos, table, npages,
+                    pos0, window, H, scale, Hg, nsplit, out_fp32, max_pages);
+}
+
+std::tuple<at::Tensor, at::Tensor> flash_decode_paged_fp8(const at::Tensor& rows, const at::Tensor& qpool, const at::Tensor& vpool,
+                                                          const at::Tensor& qscale, const at::Tensor& vscale,
+                                                          const at::Tensor& pool_pos, const at::Tensor& table,
+                                                          const at::Tensor& npages, const at::Tensor& pos0, int64_t window,
+                                                          int64_t H, double scale, int64_t Hg, int64_t nsplit, bool out_fp32,
+                                                          int64_t max_pages) {
+  Range rr_("xdot.flash_decode_paged_fp8");
+  return paged_call("xdot.flash_decode_paged_fp8: ", "flash_decode_paged_fp8", rows, qpool, vpool, &qscale, &vscale, pool_pos, table,
+                    npages, pos0, window, H, scale, Hg, nsplit, out_fp32, max_pages);
 }
 
 // spans plan_decode_paged gives this shape on the current device
@@ -676,6 +724,13 @@ int64_t flash_decode_paged_plan(int64_t B, int64_t Hg, int64_t G, int64_t Rn, in
   const int nt = decode_row_tiles(G, Rn);
   TORCH_CHECK(nt > 0 && B > 0 && Hg > 0 && max_pages > 0 && paged_page_size_ok(S), "xdot.flash_decode_paged_plan: shape");
   return plan_decode_paged(B, Hg, nt, max_pages, S, xdot_num_cus());
+}
+
+// the same for an fp8 pool of head dim D (plan_decode_paged_fp8)
+int64_t flash_decode_paged_fp8_plan(int64_t B, int64_t Hg, int64_t G, int64_t Rn, int64_t D, int64_t max_pages, int64_t S) {
+  const int nt = decode_row_tiles(G, Rn);
+  TORCH_CHECK(nt > 0 && B > 0 && Hg > 0 && D > 0 && max_pages > 0 && paged_page_size_ok(S), "xdot.flash_decode_paged_fp8_plan: shape");
+  return plan_decode_paged_fp8(B, Hg, nt, (int)D, max_pages, S, xdot_num_cus());
 }
 
 // rows (B, n, 2*Hg*D) 16-bit, a row view of row_view.h -> e4m3 bytes and per-chunk scales in slots
@@ -706,6 +761,47 @@ void cache_quant(const at::Tensor& rows, at::Tensor& qv8, at::Tensor& scales, in
   a.sb = v.sb; a.sr = v.sr; a.B = (int)B; a.n = (int)n; a.chunks = (int)(2 * Hg); a.cap = (int)cap; a.at = (int)at_;
   c10::DeviceGuard guard(rows.device());
   launched(xdot_cache_quant_launch(&a, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "cache_quant");
+}
+
+// rows (N, 2*Hg*D) 16-bit of unit inner stride, starting and stepping on 16-byte boundaries -> e4m3 bytes, per-chunk
+// scales and positions at the flat slots `slots` (N,) int32 (page * S + slot; outside the pool: skipped) of an fp8
+// pool: qv8 (P, S, 2*Hg*D) float8_e4m3fn, scales (P, 2*Hg, S) fp32, pool_pos (P, S) int32, all contiguous;
+// positions (N,) int32
+void cache_quant_paged(const at::Tensor& rows, at::Tensor& qv8, at::Tensor& scales, at::Tensor& pool_pos, const at::Tensor& slots,
+                       const at::Tensor& positions, int64_t Hg) {
+  Range rr_("xdot.cache_quant_paged");
+  const char* op = "xdot.cache_quant_paged: ";
+  TORCH_CHECK(rows.is_cuda() && rows.dim() == 2 && (rows.scalar_type() == at::kBFloat16 || rows.scalar_type() == at::kHalf), op,
+              "rows must be a bf16 / fp16 (N, 2*Hg*D) tensor on a GPU");
+  const int64_t N = rows.size(0), C = rows.size(1);
+  TORCH_CHECK(Hg > 0 && C % (2 * Hg) == 0, op, "the row width ", C, " must be a multiple of 2*Hg = ", 2 * Hg);
+  const int64_t D = C / (2 * Hg);
+  TORCH_CHECK(D == 32 || D == 64 || D == 96 || D == 128, op, "head dim must be 32 / 64 / 96 / 128, got ", D);
+  TORCH_CHECK(N <= 1 || (rows.stride(0) >= C && rows.stride(0) % 8 == 0), op, "rows must step on 16-byte boundaries without overlap");
+  TORCH_CHECK(rows.stride(1) == 1 && aligned16(rows.data_ptr()), op, "rows must have unit inner stride and start on a 16-byte boundary");
+  const int64_t sr = N > 1 ? rows.stride(0) : C;
+  TORCH_CHECK(N == 0 || (N - 1) * sr + C <= avail_elems(rows), op, "row view out of bounds");
+  for (const at::Tensor* t : {(const at::Tensor*)&qv8, (const at::Tensor*)&scales, (const at::Tensor*)&pool_pos, &slots, &positions})
+    TORCH_CHECK(t->is_cuda() && t->device() == rows.device() && t->is_contiguous(), op, "every tensor must be contiguous on the rows' GPU");
+  TORCH_CHECK(qv8.scalar_type() == at::kFloat8_e4m3fn && qv8.dim() == 3 && qv8.size(0) > 0 && qv8.size(2) == C && aligned16(qv8.data_ptr()),
+              op, "qv8 must be a float8_e4m3fn (P, S, 2*Hg*D) = (P, S, ", C, ") tensor");
+  const int64_t P = qv8.size(0), S = qv8.size(1);
+  TORCH_CHECK(paged_page_size_ok(S), op, "the page size must be 32, 64, 128 or 256 slots, got ", S);
+  TORCH_CHECK(scales.scalar_type() == at::kFloat && scales.dim() == 3 && scales.size(0) == P && scales.size(1) == 2 * Hg && scales.size(2) == S,
+              op, "scales must be an fp32 (P, 2*Hg, S) = (", P, ", ", 2 * Hg, ", ", S, ") tensor");
+  TORCH_CHECK(pool_pos.scalar_type() == at::kInt && pool_pos.dim() == 2 && pool_pos.size(0) == P && pool_pos.size(1) == S, op,
+              "pool_pos must be an int32 (P, S) = (", P, ", ", S, ") tensor");
+  for (const at::Tensor* t : {&slots, &positions})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1 && t->size(0) == N, op, "slots and positions must be int32 (N,) = (", N,
+                ",) tensors, got ", t->scalar_type(), " ", t->sizes());
+  TORCH_CHECK(P * S < (1LL << 31) && N < (1LL << 31), op, "pool too large");
+  if (N == 0) return;
+  QuantPagedArgs a{};
+  a.rows = rows.data_ptr(); a.qv8 = qv8.data_ptr(); a.scales = scales.data_ptr<float>(); a.pool_pos = pool_pos.data_ptr<int32_t>();
+  a.slots = slots.data_ptr<int32_t>(); a.positions = positions.data_ptr<int32_t>();
+  a.sr = sr; a.N = (int)N; a.chunks = (int)(2 * Hg); a.S = (int)S; a.nslots = (int)(P * S);
+  c10::DeviceGuard guard(rows.device());
+  launched(xdot_cache_quant_paged_launch(&a, dt_code(rows.scalar_type()), (int)D, cur_stream(rows)), "cache_quant_paged");
 }
 
 // spans plan_decode gives this shape on the current device
@@ -842,6 +938,7 @@ TORCH_LIBRARY_IMPL(xdot, CompositeExplicitAutograd, m) {
   m.impl("flash_decode_plan", &flash_decode_plan);
   m.impl("flash_decode_fp8_plan", &flash_decode_fp8_plan);
   m.impl("flash_decode_paged_plan", &flash_decode_paged_plan);
+  m.impl("flash_decode_paged_fp8_plan", &flash_decode_paged_fp8_plan);
   m.impl("flash_extend_plan", &flash_extend_plan);
   m.impl("flash_extend_fp8_plan", &flash_extend_fp8_plan);
 }
@@ -851,9 +948,11 @@ TORCH_LIBRARY_IMPL(xdot, CUDA, m) {
   m.impl("flash_decode", &flash_decode);
   m.impl("flash_decode_fp8", &flash_decode_fp8);
   m.impl("flash_decode_paged", &flash_decode_paged);
+  m.impl("flash_decode_paged_fp8", &flash_decode_paged_fp8);
   m.impl("flash_extend", &flash_extend);
   m.impl("flash_extend_fp8", &flash_extend_fp8);
   m.impl("cache_quant", &cache_quant);
+  m.impl("cache_quant_paged", &cache_quant_paged);
   m.impl("flash_bwd_cols", &flash_bwd_cols);
   m.impl("flash_bwd_rows", &flash_bwd_rows);
   m.impl("flash_bwd_delta", &flash_bwd_delta);

@@ -199,6 +199,23 @@ inline bool paged_page_size_ok(int64_t S) { return S == 32 || S == 64 || S == 12
 inline int plan_decode_paged(int64_t B, int64_t Hg, int row_tiles, int64_t max_pages, int64_t S, int cus) {
   return plan_decode(B, Hg, row_tiles, std::max<int64_t>(1, max_pages) * S, cus);
 }
+// The same over an fp8 pool (csrc/flash_paged8.hip): plan_decode_fp8's rule (exactly the workgroups that are
+// resident at once, spans of at least 8 tiles) over max_pages pages.  The residency is the compiler's
+// occupancy for the paged fp8 instantiations themselves (profiles/paged_fp8.md; D = 32 / 64 / 96 / 128 by 1 /
+// 2 / 4 row tiles): the table chain and the 16-byte scale loads cost registers, so it is below
+// decode_fp8_wgs_per_cu at D = 32 and 64 with one row tile, D = 64 and 128 with two.
+inline int paged_fp8_wgs_per_cu(int D, int row_tiles) {
+  static constexpr int occ[4][3] = {{4, 4, 2}, {3, 2, 1}, {3, 2, 1}, {2, 1, 1}};
+  const int d = std::max(0, std::min(3, D / 32 - 1));
+  return occ[d][row_tiles <= 1 ? 0 : row_tiles == 2 ? 1 : 2];
+}
+inline int plan_decode_paged_fp8(int64_t B, int64_t Hg, int row_tiles, int D, int64_t max_pages, int64_t S, int cus) {
+  const int64_t nt = std::max<int64_t>(1, max_pages) * S / DEC_TILE, heads = std::max<int64_t>(1, B * Hg);
+  const int64_t want = ((int64_t)paged_fp8_wgs_per_cu(D, row_tiles) * std::max(1, cus) + heads - 1) / heads;
+  const int64_t s = std::max<int64_t>(1, std::min(want, nt / 8));
+  const int64_t len = (nt + s - 1) / s;
+  return (int)std::max<int64_t>(1, (nt + len - 1) / len);
+}
 // What the kernel does with that grid for a sequence of nt tiles: tiles per span (at least 8, as plan_decode
 // asks), and how many of the nspan workgroups sweep one; the others write an empty partial.
 inline int paged_span_tiles(int64_t nt, int nspan) {

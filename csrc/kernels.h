@@ -157,7 +157,9 @@ struct ExtendArgs {
 // paged decode (csrc/flash_paged.hip): the decode call over a pool of pages reached through a block table,
 // with every per-sequence quantity on the device.  Of d: qc / vc are the pool's two halves ((P, S, ldkv)
 // rows), col_pos is pool_pos (P, S); d.Tcap, d.pos0 and d.span_tiles are unused (the kernel cuts its spans
-// from npages)
+// from npages).  An fp8 pool (csrc/flash_paged8.hip): qc / vc hold e4m3 bytes (d.ldkv in bytes) and d.qscale /
+// d.vscale are the two halves of the pool's (P, 2*Hg, S) scales: d.sc_head = S between gathered heads, d.sc_batch
+// = 2*Hg*S between PAGES
 struct PagedArgs {
   DecodeArgs d;
   const int32_t* table;   // (B, maxp) page of each logical block, -1: a hole
@@ -174,6 +176,19 @@ struct QuantArgs {
   float* scales;     // (B, 2*Hg, cap)
   int64_t sb, sr;
   int B, n, chunks, cap, at;  // chunks = 2*Hg per row
+};
+
+// cache_quant_paged (csrc/flash_paged8.hip): N rows of a 16-bit (N, 2*Hg*D) view quantised as cache_quant does
+// and scattered into an fp8 pool: row i to the flat slot slots[i] = page * S + slot (outside [0, nslots): skipped)
+struct QuantPagedArgs {
+  const void* rows;          // row stride sr in elements
+  void* qv8;                 // (P, S, 2*Hg*D) bytes
+  float* scales;             // (P, 2*Hg, S)
+  int32_t* pool_pos;         // (P, S), gets positions[i]
+  const int32_t* slots;      // (N,)
+  const int32_t* positions;  // (N,)
+  int64_t sr;
+  int N, chunks, S, nslots;  // chunks = 2*Hg per row, nslots = P * S
 };
 
 }  // namespace fa
@@ -385,6 +400,10 @@ int xdot_flash_decode_combine_launch(const xdot::fa::DecodeArgs* a, int dt, int 
 // decode over a paged pool: table, npages and pos0 are read on the device (16-bit, D <= 128, G * Rn <= 64, a
 // page size paged_page_size_ok takes: -1 otherwise)
 int xdot_flash_paged_launch(const xdot::fa::PagedArgs* a, int dt, int D, hipStream_t st);
+// the same over an fp8 pool with per-slot scales (csrc/flash_paged8.hip; a->d.qscale / vscale set, a->d.ldkv in
+// bytes; dt: the rows' 16-bit dtype), and the quantising scatter append that fills such a pool
+int xdot_flash_paged8_launch(const xdot::fa::PagedArgs* a, int dt, int D, hipStream_t st);
+int xdot_cache_quant_paged_launch(const xdot::fa::QuantPagedArgs* a, int dt, int D, hipStream_t st);
 // chunked prefill: the row-blocked sweep of the same call for G * Rn > 64 (16-bit, D <= 128; -1 otherwise,
 // or where a->rb rows x G heads exceed the kernel's row block); merges the spans itself when a->d.nspan > 1
 int xdot_flash_extend_launch(const xdot::fa::ExtendArgs* a, int dt, int D, hipStream_t st);

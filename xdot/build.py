@@ -64,7 +64,8 @@ def _flags() -> list:
 # all (device code only: the host pass does not know the feature and says so, harmlessly).
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"flash_x6.hip": _NO_PK_F32, "flash_decode.hip": _NO_PK_F32, "flash_decode8.hip": _NO_PK_F32,
-              "flash_extend.hip": _NO_PK_F32, "flash_extend8.hip": _NO_PK_F32, "flash_paged.hip": _NO_PK_F32}
+              "flash_extend.hip": _NO_PK_F32, "flash_extend8.hip": _NO_PK_F32, "flash_paged.hip": _NO_PK_F32,
+              "flash_paged8.hip": _NO_PK_F32}
 
 
 def tree_hash(csrc: str = CSRC, extra=None) -> str:

@@ -457,15 +457,16 @@ class DistributedDotProductAttn(nn.Module):
         return AttnCache(batch, capacity, self.num_gathered_heads, self.dim, self.compute_dtype or w.dtype,
                          w.device if device is None else device, cache_dtype=cache_dtype)
 
-    def new_paged_cache(self, batch: int, num_pages: int, page_size: int = 128, device=None) -> PagedAttnCache:
+    def new_paged_cache(self, batch: int, num_pages: int, page_size: int = 128, device=None, cache_dtype=None) -> PagedAttnCache:
         """An empty :class:`xdot.PagedAttnCache` for this rank's shard of a ragged batch of ``batch`` sequences:
-        ``num_pages`` pages of ``page_size`` slots, shared by the sequences, in the compute dtype."""
+        ``num_pages`` pages of ``page_size`` slots, shared by the sequences, in the compute dtype, or with
+        ``cache_dtype="fp8"`` in e4m3fn bytes with per-slot scales."""
         if self.value_dim // self.num_heads != self.dim:
             raise ValueError("new_paged_cache: the cache keeps [q | v] at one head dim; this module's value heads are "
                              f"{self.value_dim // self.num_heads} wide, its key heads {self.dim}")
         w = self.queries.weight
         return PagedAttnCache(batch, num_pages, page_size, self.num_gathered_heads, self.dim, self.compute_dtype or w.dtype,
-                              w.device if device is None else device)
+                              w.device if device is None else device, cache_dtype=cache_dtype)
 
     def _prep_ragged(self, x: Tensor, ncols: int, heads: int, row_side: bool, pos) -> Tensor:
         """:meth:`_prep` of ``x`` (B, n, C) with sequence ``b``'s rows at ``pos[b], pos[b] + 1, ...``: the batch

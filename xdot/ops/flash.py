@@ -494,21 +494,24 @@ def decode_plan(B: int, Hg: int, G: int, Rn: int, Tcap: int, fp8_head_dim: int =
     return int(_ext.ops().flash_decode_plan(int(B), int(Hg), int(G), int(Rn), int(Tcap)))
 
 
-# ---- paged decode: a ragged batch against a pool of pages (csrc/flash_paged.hip) --------------------
+# ---- paged decode: a ragged batch against a pool of pages (csrc/flash_paged.hip, flash_paged8.hip) ---
 PAGE_SIZES = (32, 64, 128, 256)
 _POS_SHIFT = 1 << 30   # positions are documented to stay below this
 
 
-def decode_paged_eligible(dtype: torch.dtype, D: int, Dv: int, G: int, Rn: int, page_size: int) -> bool:
+def decode_paged_eligible(dtype: torch.dtype, D: int, Dv: int, G: int, Rn: int, page_size: int, cache_dtype=None) -> bool:
     """The paged decode kernel takes this call: :func:`decode_eligible`'s shapes (16-bit, one head dim of
-    32 / 64 / 96 / 128, at most 64 rows per gathered head) over pages of 32, 64, 128 or 256 slots."""
-    return decode_eligible(dtype, D, Dv, G, Rn) and int(page_size) in PAGE_SIZES
+    32 / 64 / 96 / 128, at most 64 rows per gathered head) over pages of 32, 64, 128 or 256 slots.  ``dtype`` is
+    the rows'; ``cache_dtype`` ``torch.float8_e4m3fn`` asks for the fp8-pool kernel (csrc/flash_paged8.hip),
+    which takes the same shapes."""
+    return decode_eligible(dtype, D, Dv, G, Rn, cache_dtype) and int(page_size) in PAGE_SIZES
 
 
 def decode_paged(rows: torch.Tensor, qpool: torch.Tensor, vpool: torch.Tensor, pool_pos: torch.Tensor,
                  table: torch.Tensor, npages: torch.Tensor, pos0: torch.Tensor, H: int, scale: float, window: int = 0,
                  Hg: Optional[int] = None, nsplit: int = 0, out_fp32: bool = False,
-                 max_pages: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                 max_pages: Optional[int] = None, qscale: Optional[torch.Tensor] = None,
+                 vscale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """:func:`decode` for a ragged batch over a paged cache -> (out (B, Rn, H*D) in ``rows.dtype``, lse
     (B, H, Rn) fp32 natural log).
 
@@ -529,38 +532,58 @@ def decode_paged(rows: torch.Tensor, qpool: torch.Tensor, vpool: torch.Tensor, p
     ``nsplit``: column spans (0: ``plan_decode_paged`` of ``csrc/flash_plan.h``, over ``max_pages`` pages per
     sequence: the table's width, or a tighter bound the caller knows; it sizes the grid only).
 
+    ``qscale`` / ``vscale`` (P, Hg, S) fp32, the two halves of one (P, 2*Hg, S) buffer: ``qpool`` / ``vpool`` are
+    ``float8_e4m3fn`` and slot ``c`` of page ``p``, gathered head ``h`` stands for ``qscale[p, h, c] * qpool[p, c,
+    h*D:(h+1)*D]`` (and likewise ``v``): the format of :class:`xdot.PagedAttnCache` with ``cache_dtype="fp8"``.
+    Eligible calls run the paged fp8 sweep (csrc/flash_paged8.hip; ``plan_decode_paged_fp8``).
+
     Calls the kernel does not take (:func:`decode_paged_eligible`: fp32 rows, D > 128, Dv != D, more than 64
-    rows per gathered head, another page size) stay on the device without a kernel of their own: the pages are
-    gathered into a dense (B, maxp*S, .) cache, every sequence's positions are shifted by ``2**30 - pos0[b]``
-    (visibility depends on ``pos - pos0[b]`` only) and :func:`decode` runs at ``pos0 = 2**30``.  CPU tensors and
-    ``backend='torch'`` run ``xdot.parallel._ref.decode_paged``."""
+    rows per gathered head, another page size) stay on the device without a kernel of their own: the pages (and
+    an fp8 pool's scales) are gathered into a dense (B, maxp*S, .) cache, every sequence's positions are shifted
+    by ``2**30 - pos0[b]`` (visibility depends on ``pos - pos0[b]`` only) and :func:`decode` runs at ``pos0 =
+    2**30``: over an fp8 pool that is its fp8 route, so more than 64 rows per gathered head reach
+    csrc/flash_extend8.hip.  CPU tensors and ``backend='torch'`` run ``xdot.parallel._ref.decode_paged``."""
     from ..parallel import _ref  # (xdot.parallel imports this module)
 
     B, Rn, C = rows.shape
     hg = int(Hg) if Hg else int(H)
     D, Dv, window = C // H, vpool.shape[-1] // hg, int(window or 0)
+    fp8 = qscale is not None or vscale is not None
+    if fp8 and not (qscale is not None and vscale is not None and qpool.dtype == vpool.dtype == torch.float8_e4m3fn):
+        raise ValueError("flash.decode_paged: qscale and vscale go together, with float8_e4m3fn qpool and vpool")
     if not _ext.use_hip(rows, qpool, vpool):
-        o, lse = _ref.decode_paged(rows, qpool, vpool, pool_pos, table, npages, pos0, int(H), float(scale), window, Hg)
+        o, lse = _ref.decode_paged(rows, qpool, vpool, pool_pos, table, npages, pos0, int(H), float(scale), window, Hg,
+                                   qscale, vscale)
         return (o if out_fp32 else o.to(rows.dtype)), lse
-    if decode_paged_eligible(rows.dtype, D, Dv, H // hg, Rn, qpool.shape[1]):
+    if decode_paged_eligible(rows.dtype, D, Dv, H // hg, Rn, qpool.shape[1], torch.float8_e4m3fn if fp8 else None):
+        if fp8:
+            return _ext.ops().flash_decode_paged_fp8(rows.contiguous(), qpool, vpool, qscale, vscale, pool_pos, table, npages,
+                                                     pos0, window, int(H), float(scale), hg, int(nsplit), bool(out_fp32),
+                                                     int(max_pages or 0))
         return _ext.ops().flash_decode_paged(rows.contiguous(), qpool, vpool, pool_pos, table, npages, pos0, window, int(H),
                                              float(scale), hg, int(nsplit), bool(out_fp32), int(max_pages or 0))
-    return _decode_paged_gathered(rows, qpool, vpool, pool_pos, table, npages, pos0, H, scale, window, Hg, nsplit, out_fp32)
+    return _decode_paged_gathered(rows, qpool, vpool, pool_pos, table, npages, pos0, H, scale, window, Hg, nsplit, out_fp32,
+                                  qscale, vscale)
 
 
 def _decode_paged_gathered(rows, qpool, vpool, pool_pos, table, npages, pos0, H, scale, window=0, Hg=None, nsplit=0,
-                           out_fp32=False):
-    """:func:`decode_paged` without its kernel: gather to a dense cache, shift the positions, :func:`decode`."""
+                           out_fp32=False, qscale=None, vscale=None):
+    """:func:`decode_paged` without its kernel: gather to a dense cache (an fp8 pool to a dense fp8 cache, bytes
+    and scales), shift the positions, :func:`decode`."""
     from ..parallel import _ref
 
-    qc, vc, pos = _ref.paged_gather(qpool, vpool, pool_pos, table, npages)
+    qc, vc, pos, *sc = _ref.paged_gather(qpool, vpool, pool_pos, table, npages, qscale, vscale)
     p0 = pos0.to(torch.int64).view(-1, 1)
     pos = torch.where((pos >= 0) & (p0 >= 0), pos + (_POS_SHIFT - p0), pos.new_full((), -1)).to(torch.int32)
-    return decode(rows, qc, vc, pos, _POS_SHIFT, H, scale, window, Hg, nsplit, out_fp32)
+    return decode(rows, qc, vc, pos, _POS_SHIFT, H, scale, window, Hg, nsplit, out_fp32, *sc)
 
 
-def decode_paged_plan(B: int, Hg: int, G: int, Rn: int, max_pages: int, page_size: int) -> int:
-    """Column spans an automatic :func:`decode_paged` launch takes on the current device."""
+def decode_paged_plan(B: int, Hg: int, G: int, Rn: int, max_pages: int, page_size: int, fp8_head_dim: int = 0) -> int:
+    """Column spans an automatic :func:`decode_paged` launch takes on the current device; ``fp8_head_dim``: over
+    an fp8 pool of that head dim (``plan_decode_paged_fp8``)."""
+    if fp8_head_dim:
+        return int(_ext.ops().flash_decode_paged_fp8_plan(int(B), int(Hg), int(G), int(Rn), int(fp8_head_dim), int(max_pages),
+                                                          int(page_size)))
     return int(_ext.ops().flash_decode_paged_plan(int(B), int(Hg), int(G), int(Rn), int(max_pages), int(page_size)))
 
 

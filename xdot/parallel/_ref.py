@@ -78,24 +78,41 @@ def decode(rows, qc, vc, col_pos, pos0: int, H: int, scale: float, window: int =
     return block_fwd(rows, qc, vc, decode_mask(col_pos, pos0, rows.shape[1], window), H, scale, Hg)
 
 
-def paged_gather(qpool, vpool, pool_pos, table, npages):
+def paged_gather(qpool, vpool, pool_pos, table, npages, qscale=None, vscale=None):
     """A paged cache as the dense one every sequence would have: ``qpool`` / ``vpool`` (P, S, Hg*d) and
     ``pool_pos`` (P, S) gathered by ``table`` (B, maxp) -> (qc, vc (B, maxp*S, Hg*d), col_pos (B, maxp*S) int64);
     the slots of a hole (-1), of an entry outside the pool and of the entries at or past ``npages[b]`` are empty
-    (-1).  No host synchronisation."""
+    (-1).  No host synchronisation.  An fp8 pool's ``qscale`` / ``vscale`` (P, Hg, S) come along as the dense fp8
+    cache's (B, Hg, maxp*S): five results."""
     (B, maxp), (P, S) = table.shape, pool_pos.shape
     t = table.to(torch.int64)
     live = (t >= 0) & (t < P) & (torch.arange(maxp, device=table.device).unsqueeze(0) < npages.to(torch.int64).unsqueeze(1))
     idx = t.clamp(0, P - 1).reshape(-1)
-    qc, vc = (x.index_select(0, idx).reshape(B, maxp * S, x.shape[-1]) for x in (qpool, vpool))
+
+    def pages(x):  # one-byte dtypes are gathered as bytes
+        if x.element_size() == 1:
+            return x.view(torch.uint8).index_select(0, idx).view(x.dtype)
+        return x.index_select(0, idx)
+
+    qc, vc = (pages(x).reshape(B, maxp * S, x.shape[-1]) for x in (qpool, vpool))
     pos = pool_pos.index_select(0, idx).reshape(B, maxp, S).to(torch.int64)
-    return qc, vc, torch.where(live.unsqueeze(-1), pos, pos.new_full((), -1)).reshape(B, maxp * S)
+    pos = torch.where(live.unsqueeze(-1), pos, pos.new_full((), -1)).reshape(B, maxp * S)
+    if qscale is None:
+        return qc, vc, pos
+    qs, vs = (x.index_select(0, idx).reshape(B, maxp, -1, S).transpose(1, 2).reshape(B, -1, maxp * S) for x in (qscale, vscale))
+    return qc, vc, pos, qs, vs
 
 
-def decode_paged(rows, qpool, vpool, pool_pos, table, npages, pos0, H: int, scale: float, window: int = 0, Hg=None):
+def decode_paged(rows, qpool, vpool, pool_pos, table, npages, pos0, H: int, scale: float, window: int = 0, Hg=None,
+                 qscale=None, vscale=None):
     """:func:`decode` per sequence of a ragged batch over a paged cache (:func:`paged_gather`), sequence ``b``'s
-    rows at ``pos0[b], pos0[b] + 1, ...``; a sequence with a negative ``pos0`` sees nothing."""
-    qc, vc, pos = paged_gather(qpool, vpool, pool_pos, table, npages)
+    rows at ``pos0[b], pos0[b] + 1, ...``; a sequence with a negative ``pos0`` sees nothing.  ``qscale`` / ``vscale``
+    (P, Hg, S): the pool is fp8 and is dequantised in the compute dtype after the gather."""
+    qc, vc, pos, *sc = paged_gather(qpool, vpool, pool_pos, table, npages, qscale, vscale)
+    if sc:
+        cdt, hg = compute_dtype(rows), sc[0].shape[1]
+        qc, vc = ((x.to(cdt).reshape(*x.shape[:2], hg, -1) * s.to(cdt).transpose(1, 2).unsqueeze(-1)).reshape(x.shape)
+                  for x, s in ((qc, sc[0]), (vc, sc[1])))
     outs = []
     for b, p0 in enumerate(int(p) for p in pos0.tolist()):
         cp = pos[b:b + 1] if p0 >= 0 else torch.full_like(pos[b:b + 1], -1)

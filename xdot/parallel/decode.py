@@ -15,11 +15,14 @@ A ragged batch (sequences of different lengths that come and go) keeps its slots
 (:class:`PagedAttnCache`): one pool shared by the sequences, reached through a block table, with every
 sequence's length and row position on the device (:func:`xdot.ops.flash.decode_paged`,
 ``csrc/flash_paged.hip``).  A sequence that ends gives its pages to the next one, and a generation step is
-one launch whose arguments do not change, so it can be captured.
+one launch whose arguments do not change, so it can be captured.  The pool, too, holds the compute dtype or
+fp8 (``cache_dtype="fp8"``): the dense fp8 format per page, scales ``(num_pages, 2*Hg, page_size)``, filled by
+one quantise-and-scatter launch per append and read by a block-table sweep over the bytes
+(``csrc/flash_paged8.hip``).
 
 Forward only, no autograd.  Not covered: document masks at decode time, eviction of single slots (a
-sequence frees all its pages or none), an fp8 paged pool, a paged chunked-prefill kernel (more than 64 rows
-per gathered head over pages gather them into a dense cache per call), a device-side ``pos0`` for the dense
+sequence frees all its pages or none), a paged chunked-prefill kernel (more than 64 rows per gathered head
+over pages gather them, bytes and scales of an fp8 pool as they are, into a dense cache per call), a device-side ``pos0`` for the dense
 :class:`AttnCache`, per-channel scales, fp8 rows, and an fp8 kernel for the
 shapes neither fp8 kernel takes (fp32 rows, D > 128, Dv != D, more than 128 row heads per gathered head:
 they dequantise the whole cache per call).
@@ -128,15 +131,28 @@ class PagedAttnCache:
     logical block of each sequence (-1 past its pages) and ``npages`` (batch,) int32 the entries in use: the
     format of :func:`xdot.ops.flash.decode_paged`, which reads the last three on the device.  The free list and
     the sequences' lengths are kept on the host, so appending and freeing never wait for the device.  A
-    sequence takes a page when its last one is full and gives all of them back with :meth:`free`."""
+    sequence takes a page when its last one is full and gives all of them back with :meth:`free`.
 
-    def __init__(self, batch: int, num_pages: int, page_size: int, Hg: int, D: int, dtype: torch.dtype, device=None):
+    ``cache_dtype`` ``"fp8"`` / ``torch.float8_e4m3fn``: ``qv`` holds e4m3fn bytes and ``scales`` (num_pages,
+    2*Hg, page_size) fp32 one factor per slot and chunk, the slot innermost within its page (rows ``0..Hg-1`` the
+    ``q`` heads, ``Hg..2*Hg-1`` the ``v`` heads): :class:`AttnCache`'s fp8 format and quantisation rule, bit for
+    bit, page by page.  ``dtype`` stays the compute dtype.  :meth:`free` leaves bytes and scales as they are
+    (finite); only the positions go to -1."""
+
+    def __init__(self, batch: int, num_pages: int, page_size: int, Hg: int, D: int, dtype: torch.dtype, device=None,
+                 cache_dtype=None):
         if min(int(batch), int(num_pages), int(Hg), int(D)) < 1 or int(page_size) not in flash.PAGE_SIZES:
             raise ValueError("PagedAttnCache: batch, num_pages, Hg and D must be positive and page_size one of "
                              f"{flash.PAGE_SIZES}, got {(batch, num_pages, page_size, Hg, D)}")
+        if cache_dtype not in (None, "fp8", torch.float8_e4m3fn):
+            raise ValueError(f"PagedAttnCache: cache_dtype must be None, 'fp8' or torch.float8_e4m3fn, got {cache_dtype!r}")
         self.Hg, self.D, self.page_size, self.num_pages, self.dtype = int(Hg), int(D), int(page_size), int(num_pages), dtype
-        # zeros: the kernel multiplies empty slots' v by a probability of 0
-        self.qv = torch.zeros(self.num_pages, self.page_size, 2 * self.Hg * self.D, device=device, dtype=dtype)
+        self.fp8 = cache_dtype is not None
+        # zeros (and scales of 1): the kernels multiply empty slots' v by a probability of 0 and a finite scale
+        self.qv = torch.zeros(self.num_pages, self.page_size, 2 * self.Hg * self.D, device=device,
+                              dtype=torch.float8_e4m3fn if self.fp8 else dtype)
+        self.scales = (torch.ones(self.num_pages, 2 * self.Hg, self.page_size, dtype=torch.float32, device=device)
+                       if self.fp8 else None)
         self.pos = torch.full((self.num_pages, self.page_size), -1, dtype=torch.int32, device=device)
         self.table = torch.full((int(batch), self.num_pages), -1, dtype=torch.int32, device=device)
         self.npages = torch.zeros(int(batch), dtype=torch.int32, device=device)
@@ -151,6 +167,22 @@ class PagedAttnCache:
     @property
     def v(self) -> Tensor:
         return self.qv[..., self.Hg * self.D:]
+
+    @property
+    def qscale(self) -> Optional[Tensor]:
+        """(num_pages, Hg, page_size): the scales of :attr:`q` (None for a pool in the compute dtype)."""
+        return self.scales[:, :self.Hg] if self.fp8 else None
+
+    @property
+    def vscale(self) -> Optional[Tensor]:
+        return self.scales[:, self.Hg:] if self.fp8 else None
+
+    def dequant(self) -> Tuple[Tensor, Tensor]:
+        """``(q, v)`` (num_pages, page_size, Hg*D) in the compute dtype: the stored halves, times their scales."""
+        if not self.fp8:
+            return self.q, self.v
+        qv = _ref.cache_dequant(self.qv, self.scales.transpose(1, 2), self.Hg, self.dtype)
+        return qv[..., :self.Hg * self.D], qv[..., self.Hg * self.D:]
 
     def _take(self, seqs, n: int) -> Tensor:
         """Give each sequence of ``seqs`` the pages its next ``n`` rows need (all of them or, on a full pool,
@@ -182,8 +214,18 @@ class PagedAttnCache:
             return
         p = torch.stack([f.reshape(n).to("cpu", torch.int64) if isinstance(f, Tensor) else torch.arange(int(f), int(f) + n)
                          for f in first]).reshape(-1)
-        at = torch.stack([self._take(seqs, n), p]).to(self.qv.device)  # one copy to the device
-        self.qv.view(-1, self.qv.shape[-1]).index_copy_(0, at[0], rows.to(self.dtype))
+        at = torch.stack([self._take(seqs, n), p])
+        if self.fp8 and _ext.use_hip(rows) and rows.dtype in (torch.bfloat16, torch.float16) and self.D in (32, 64, 96, 128):
+            at = at.to(torch.int32).to(self.qv.device)  # one copy to the device, one launch: bytes, scales, positions
+            _ext.ops().cache_quant_paged(rows, self.qv, self.scales, self.pos, at[0], at[1], self.Hg)
+            return
+        at = at.to(self.qv.device)  # one copy to the device
+        if self.fp8:
+            b8, s = _ref.cache_quant(rows, self.Hg)
+            self.qv.view(torch.uint8).view(-1, self.qv.shape[-1]).index_copy_(0, at[0], b8.view(torch.uint8))
+            self.scales[at[0] // self.page_size, :, at[0] % self.page_size] = s
+        else:
+            self.qv.view(-1, self.qv.shape[-1]).index_copy_(0, at[0], rows.to(self.dtype))
         self.pos.view(-1).index_copy_(0, at[0], at[1].to(torch.int32))
 
     def _rows(self, qv: Tensor, B: int, who: str) -> Tensor:
@@ -235,13 +277,13 @@ def decode_attention(rows: Tensor, cache: Union[AttnCache, PagedAttnCache], pos0
 
     With a :class:`PagedAttnCache` the batch is ragged: ``pos0`` is a list of ``B`` ints or a ``(B,)`` int32
     tensor on the rows' device (negative: the sequence is inactive), and each rank runs
-    :func:`xdot.ops.flash.decode_paged` over its pool."""
+    :func:`xdot.ops.flash.decode_paged` over its pool (with its scales, if it is fp8)."""
     comm = comm if comm is not None else _comm.get_comm()
     H, n = int(num_heads), comm.world_size
     if isinstance(cache, PagedAttnCache):
         p0 = pos0 if isinstance(pos0, Tensor) else torch.tensor([int(p) for p in pos0], dtype=torch.int32).to(rows.device)
         o, lse = flash.decode_paged(rows, cache.q, cache.v, cache.pos, cache.table, cache.npages, p0, H, scale,
-                                    int(window or 0), Hg=cache.Hg, out_fp32=n > 1)
+                                    int(window or 0), Hg=cache.Hg, out_fp32=n > 1, qscale=cache.qscale, vscale=cache.vscale)
     else:
         o, lse = flash.decode(rows, cache.q, cache.v, cache.pos, int(pos0), H, scale, int(window or 0), Hg=cache.Hg,
                               out_fp32=n > 1, qscale=cache.qscale, vscale=cache.vscale)
